@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- read-pairs/s through the barcode feature path + VAE encode (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs P] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 One "step" = one pass of the hot path over one batch of synthetic barcoded read pairs that are already resident
 in HBM in packed form: clear + build the global canonical 21-mer table (K2), exchange it between ranks (N > 1),
@@ -9,6 +9,10 @@ count TNF + abundance rows for every barcode (K1+K3), L1-normalise, VAE encode -
 Workload at N=1 = BASELINE.json configs[1]: 10 M 150 bp pairs, 50 k barcodes, k=21, k_tnf=4, V=400, W=10.
 For N > 1 every rank holds its own 10 M-pair shard of one N x 10 M-pair data set (weak scaling); launched as
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...``.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the steps and prints the line.  ``--full`` adds what takes runs of its own: the CPU
+baseline (``cpu_baseline``) and the FASTQ file -> mu leg (``e2e``).  ``--dump-outputs DIR`` writes what the last timed
+step computed (rank 0's) as DIR/<name>.npy, for an output-for-output comparison of two builds (``dump_outputs``).
 """
 from __future__ import annotations
 
@@ -49,9 +53,12 @@ def parse_args():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--pairs", type=int, default=10_000_000, help="read pairs per GPU (default: BASELINE config 2)")
     ap.add_argument("--barcodes", type=int, default=0, help="barcodes per GPU (default pairs/200)")
-    ap.add_argument("--cpu-sample", type=int, default=100_000, help="pairs in the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--e2e-pairs", type=int, default=-1, help="pairs of the end-to-end leg (FASTQ file -> mu); default: the whole workload; 0 = skip")
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline and the end-to-end leg (FASTQ file -> mu), reported beside the line's value")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--cpu-sample", type=int, default=100_000, help="pairs in the CPU-baseline sample (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--e2e-pairs", type=int, default=-1, help="pairs of the end-to-end leg (--full; FASTQ file -> mu); default: the whole workload; 0 = skip")
     ap.add_argument("--rehearse-dist", type=int, default=0, metavar="N",
                     help="one GPU: run the N-rank code path (deferred count, exchange over a one-rank RCCL group, table sized for N shards) -- not a result")
     ap.add_argument("--load", type=float, default=0.6, help="highest load of the hash table (its size is the next power of two)")
@@ -64,7 +71,33 @@ def parse_args():
                          "before the timed steps (valid only because the bench repeats one batch: a comparison figure, never the default)")
     ap.add_argument("--no-defer", action="store_true", help="N > 1: write every rank's own table and compact it (instead of the deferred count)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (gloo lets several ranks rehearse on one GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+# --dump-outputs: mu for at most 2^16 rows (8.4 MB), the TNF and abundance rows for at most 2^13 (35.1 MB) -- under 64 MB in all
+DUMP_MU_ROWS, DUMP_FEATURE_ROWS, DUMP_SEED = 1 << 16, 1 << 13, 2022
+
+
+def dump_rows(n: int, cap: int) -> np.ndarray:
+    """the rows a dump keeps: all n when n <= cap, else a fixed seeded sample of cap rows (sorted; the same for the same n)"""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir: str, mu, tnf, abd) -> None:
+    """what the caller of one step receives: mu (float32, as computed) and the TNF / abundance rows it was encoded from (int32
+    counts, written as float64: exact), each row-sampled by ``dump_rows`` when the batch is large"""
+    os.makedirs(out_dir, exist_ok=True)
+    n = mu.shape[0]
+    for name, x, cap, dt in (("mu", mu, DUMP_MU_ROWS, torch.float32), ("tnf", tnf, DUMP_FEATURE_ROWS, torch.float64),
+                             ("abd", abd, DUMP_FEATURE_ROWS, torch.float64)):
+        assert x.shape[0] == n
+        idx = torch.from_numpy(dump_rows(n, cap)).to(x.device)
+        np.save(os.path.join(out_dir, f"{name}.npy"), x.index_select(0, idx).to(dt).cpu().numpy())
 
 
 def cpu_baseline(stream, cfg, n_sample: int, state: dict) -> dict:
@@ -418,6 +451,8 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     assert tuple(mu.shape) == (len(rows), 32) and bool(torch.isfinite(mu).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, mu, tnf, abd)
 
     kern_ms = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}
     table_load = table.occupancy() if table.kind == "hash" else None
@@ -476,14 +511,14 @@ def main():
                          "alg_bytes_per_pair": alg[dominant]},
             "setup_ms": {k: round(v, 2) for k, v in setup.items()},
         }
-        if world == 1 and args.e2e_pairs != 0 and not args.rehearse_dist:
+        if args.full and world == 1 and args.e2e_pairs != 0 and not args.rehearse_dist:
             try:
                 del table                       # (the leg builds its own: two 8.6 GB tables and their workspaces need not coexist)
                 torch.cuda.empty_cache()
                 out["e2e"] = e2e_leg(stream, cfg, args.pairs if args.e2e_pairs < 0 else min(args.e2e_pairs, args.pairs), vae, dev)
             except Exception as e:          # reporting only
                 out["e2e"] = {"value": None, "unit": "pairs/s", "what": f"failed: {e!r}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             state = {k: v.detach().cpu().numpy() for k, v in vae.network.state_dict().items()}
             try:
                 out["cpu_baseline"] = cpu_baseline(stream, cfg, min(args.cpu_sample, args.pairs), state)

@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from .conftest import ROOT
@@ -13,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("extra", [[], ["--no-mini"], ["--no-fuse"], ["--rehearse-dist", "4"]])
 def test_bench_line_honours_the_contract(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "200000", "--steps", "2", "--warmup", "1", "--cpu-sample", "2000"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "200000", "--steps", "2", "--warmup", "1", "--full", "--cpu-sample", "2000"] + extra
     if extra:
         cmd.append("--no-cpu-baseline")
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
@@ -45,6 +46,33 @@ def test_bench_line_honours_the_contract(extra):
     if extra == ["--rehearse-dist", "4"]:
         p = j["config"]["pipeline"]
         assert "exchange" in j["kernel_ms"] and ("lookup half" in p or "lookups of the provisional words" in p)
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """without --full the line leaves out the CPU baseline and the FASTQ leg; --dump-outputs writes the last timed step's mu, TNF and
+    abundance rows (float32 / float64, under 64 MB), and two runs with the same arguments write the same rows"""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--pairs", "200000", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["warmup"] == 1 and "cpu_baseline" not in j and "e2e" not in j
+        assert abs(j["value"] - 200000 * 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+        files = sorted(os.listdir(d))
+        assert files == ["abd.npy", "mu.npy", "tnf.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        a = {f[:-4]: np.load(d / f) for f in files}
+        n = j["config"]["rows_per_gpu"]                 # 1 000 rows: every one of them is dumped
+        assert a["mu"].dtype == np.float32 and a["mu"].shape == (n, 32) and np.isfinite(a["mu"]).all()
+        assert a["tnf"].dtype == np.float64 and a["tnf"].shape == (n, 136) and a["abd"].dtype == np.float64 and a["abd"].shape == (n, 400)
+        assert a["tnf"].sum() > 0 and a["abd"].sum() > 0
+        dumps.append(a)
+    assert np.array_equal(dumps[0]["tnf"], dumps[1]["tnf"]) and np.array_equal(dumps[0]["abd"], dumps[1]["abd"])
+    np.testing.assert_allclose(dumps[0]["mu"], dumps[1]["mu"], rtol=1e-5, atol=1e-6)
 
 
 def test_bench_starts_its_own_ranks():

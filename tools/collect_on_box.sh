@@ -7,7 +7,7 @@ TAG=${1:-r03a}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $ROOT/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-python3 $ROOT/bench.py > $ROOT/gpurun_out/${TAG}_bench.json 2> $ROOT/gpurun_out/${TAG}_bench.err
+python3 $ROOT/bench.py --full > /tmp/${TAG}_bench.json          # (--full: the recorded line carries cpu_baseline and e2e)
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 $ROOT/bench.py --no-cpu-baseline --e2e-pairs 0 > $ROOT/gpurun_out/${TAG}_bench_under_rocprof.json 2>/dev/null
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/prof_fetch -- python3 $ROOT/bench.py --no-cpu-baseline --e2e-pairs 0 --steps 1 --warmup 0 > /dev/null 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/prof_write -- python3 $ROOT/bench.py --no-cpu-baseline --e2e-pairs 0 --steps 1 --warmup 0 > /dev/null 2>&1
@@ -19,7 +19,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_reh -- python3
 cd $ROOT
 python3 tools/collect_profiles.py rehearse $TAG /tmp/prof_reh
 grep "^{" gpurun_out/${TAG}_bench_rehearse_n8_path.json | tail -1 > profiles/${TAG}_bench_rehearse_n8_path.json
-grep "^{" gpurun_out/${TAG}_bench.json | tail -1 > profiles/${TAG}_bench.json
+grep "^{" /tmp/${TAG}_bench.json | tail -1 > profiles/${TAG}_bench.json
 grep "^{" gpurun_out/${TAG}_bench_under_rocprof.json | tail -1 > profiles/${TAG}_bench_under_rocprof.json
 python3 tools/collect_profiles.py $TAG /tmp/prof_stats /tmp/prof_fetch /tmp/prof_write
 python3 tools/fetch_calibration.py report /tmp/cal_f /tmp/cal_w > profiles/${TAG}_fetch_calibration.txt
