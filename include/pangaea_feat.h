@@ -489,6 +489,40 @@ int pg_mini_lookup_half(const pg_table *local, const pg_rows *rows, const void *
                         const void *half_ws, int64_t half_ws_bytes,
                         const uint16_t *bins_in, const int64_t *bin_elem, uint32_t *status, void *stream);
 
+/* ---- the count half in PIECES (N > 1 ranks): a rank whose share would not fit one piece of scratch counts it word range by word
+ * range, as one GPU does (pg_mini_count_piece above; the reference streams one barcode group at a time, count_tnf.cpp:257-271, and
+ * looks up in the finished table only, count_kmer.cpp:139-170).  The pieces count INTO the buckets of `local`, which has real slots
+ * here (2^log2_slots words of device memory; slots keep their places from piece to piece); the LAST piece ends as
+ * pg_mini_count_half ends: entries, occupancy and fill in half_ws, so that the exchange (pg_mini_gather_entries, pg_mini_merge_bins)
+ * is the same as for one piece.  The calls:
+ *   pg_mini_plan(codes, valid, w0, w1, local, ...)         the piece's plan (its own plan_ws, kept until its lookups)
+ *   pg_mini_count_half_piece(... first, last ...)           plan_ws, rec_ws, merge_ws of THIS piece; first != 0 for the first piece,
+ *                                                          last != 0 for the last (both: a single piece); fill zeroed by the caller
+ *   (keep: plan_ws, merge_ws and the second meta plane of rec_ws -- records x 4 bytes from pg_mini_records_meta_offset -- of every
+ *   piece; half_ws and fill until the lookups; the local slots may go after the last piece)
+ *   ... the exchange, as for one piece ...
+ *   pg_mini_lookup_begin(local, rows, n_words_total, vsize, shuffle_ws, ...)   once; shuffle_ws: pg_mini_shuffle_bytes_merged(n_words_total, ...)
+ *   pg_mini_lookup_half_piece(...)                         per piece, any order (a bucket without records of the piece: nothing)
+ *   pg_mini_abundance_from_emitted(local, rows, vsize, abd, <a plan_ws of pg_mini_plan_bytes(n_words_total)>, ..., n_words_total, ...)
+ * Counts clamp at PG_HASH_COUNT_SAT across pieces as across the adds of one.  Workspaces: half_ws = pg_mini_half_bytes(local); per
+ * piece pg_mini_plan_bytes(piece words), pg_mini_records_bytes(records) (reused from piece to piece), pg_mini_merge_words(...).
+ * A piece needs the merged lookups (pg_mini_merge_form_applies). */
+int pg_mini_count_half_piece(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
+                             const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                             int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
+                             int64_t *fill, int first, int last, uint32_t *status, void *stream);
+int pg_mini_lookup_half_piece(const pg_table *local, const pg_rows *rows, const void *plan_ws, int64_t plan_ws_bytes, int64_t n_words_piece,
+                              const uint32_t *meta, int64_t n_words_total, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes,
+                              const void *merge_ws, const void *half_ws, int64_t half_ws_bytes,
+                              const uint16_t *bins_in, const int64_t *bin_elem, uint32_t *status, void *stream);
+/* 1 where the merged lookups apply to n_rows rows with this vector size on the table's geometry (the slot form: fewer than
+ * 2^(32 - log2_bucket_slots) - 1 rows; fewer than 2^20 rows; row bits + bin bits + 6 <= 28, i.e. at most 2^19 rows at vsize 400;
+ * PG_MINI_MERGE=0 in the environment: never), 0 where they do not, < 0 for a bad table: the rule every pieces entry checks */
+int pg_mini_merge_form_applies(const pg_table *t, int64_t n_rows, int vsize);
+/* byte offset of the second meta plane ("meta B": the bucket-ordered records' meta words that the pieces keep) inside a record
+ * workspace of rec_ws_bytes bytes: [bases A | bases B | meta A | meta B] of the largest capacity that fits, a multiple of 256 */
+int64_t pg_mini_records_meta_offset(int64_t rec_ws_bytes, const pg_table *t);
+
 /* ----------------------------------------------------------------------------------------------
  * Row normalisation of a count matrix (a9: Data.__init__, src/data.py:16-21 -- sklearn normalize(norm="l1") in float64, the
  * sampling weight = (row maximum of the normalised abundance)^2, matrices narrowed to float32).  One pass over device int32

@@ -1237,12 +1237,16 @@ __device__ __forceinline__ void merged_lookup(const MergeCtx &c)
 // starts from an empty table: accum = 1), counted on, and written back; the slots keep their places from piece to piece (nothing
 // ever leaves a slot), so the provisional slots of every piece stay valid until mini_lookup_slice_merge_kernel has looked them up
 // in the final table.
+// PIECES ON N > 1 RANKS (pg_mini_count_half_piece): the pieces count into the rank's LOCAL table as above (accum 1, 2), and the
+// last one (accum 3; 4: a single piece, nothing to load) ends with the count half's epilogue instead of the write-back: entries,
+// occupancy and fill are then exactly what one count half leaves, and mini_lookup_half_merge_kernel<..., PIECE> looks up every
+// piece's provisional slots with the bins the owners sent back.
 struct HalfArgs {
     unsigned long long *ent;                                     // bucket b: entries from b << log2 bucket slots
     unsigned long long *occ;                                     // bucket b: max(1, bucket slots / 64) words from b * that
     long long *fill;                                             // [buckets]
     uint32_t *ring_cnt;                                          // [buckets]
-    int accum;                                                   // 0: N-rank count half; 1, 2: a piece (see above)
+    int accum;                                                   // 0: N-rank count half; 1, 2: a piece; 3, 4: the last piece of a count half (see above)
 };
 template <int CAP, bool SLOTS, bool WIDE, int BLK, int DIG, bool MERGE = false, bool HALF = false>
 __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__restrict__ bases, const uint32_t *__restrict__ meta,
@@ -1308,7 +1312,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
 #define PG_STAMP(K) do { } while (0)
 #define PG_WLAP(K) do { } while (0)
 #endif
-    if (HALF && hv.accum == 2) {                                 // (a later piece: the bucket as the pieces before left it)
+    if (HALF && (hv.accum == 2 || hv.accum == 3)) {              // (a later piece: the bucket as the pieces before left it)
         for (uint32_t i = threadIdx.x; i < tab_units; i += BLK) tab[i] = i < n_slots ? (unsigned long long)slice[i] : 0ull;
     } else {
         for (uint32_t i = threadIdx.x; i < tab_units; i += BLK) tab[i] = 0ull;
@@ -1594,7 +1598,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
         if (lane == 0 && mine) atomicAdd(&n_lookups, mine);
     }
     __syncthreads();
-    if (HALF && hv.accum) {
+    if (HALF && (hv.accum == 1 || hv.accum == 2)) {
         // a piece: the slice back (counts clamped: the adds stop at SAT, the overshoot of concurrent ones is cut here)
         const uint64_t slice0 = (uint64_t)blockIdx.x << t.log2_bucket;
         for (uint32_t i = threadIdx.x; i < n_slots; i += BLK) {
@@ -1607,6 +1611,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
         return;
     }
     if (HALF) {
+        // (also the LAST piece of an N-rank count half in pieces, accum 3 or 4: the bucket leaves what one count half leaves)
         // the bucket's occupied slots, in slot order: a bitmap of the occupancy (64 consecutive slots = the lanes of one wavefront:
         // a ballot), ranks from the popcounts of its words, the entries written to consecutive places (coalesced).  The LDS table
         // stays as it is until every slot has been read (the bitmap and its scan live behind it, where the rings were).
@@ -2041,8 +2046,10 @@ __global__ __launch_bounds__(BLK, 4) void mini_lookup_half_kernel(const unsigned
     wordwise_lookup<BLK, DIG>(wc);
 }
 
-// the merged form of the lookup half: the count half left its provisional words in fixed slots (MergeArgs)
-template <int CAP, int BLK, int DIG>
+// the merged form of the lookup half: the count half left its provisional words in fixed slots (MergeArgs).  PIECE (a count half
+// in pieces, pg_mini_lookup_half_piece): off / n_short / wbeg / mprov / meta are ONE piece's, and a bucket without records of
+// that piece leaves at once (as mini_lookup_slice_merge_kernel does)
+template <int CAP, int BLK, int DIG, bool PIECE = false>
 __global__ __launch_bounds__(BLK, 4) void mini_lookup_half_merge_kernel(const unsigned long long *__restrict__ off, const unsigned long long *__restrict__ n_short,
                                                                       const unsigned long long *__restrict__ wbeg, const uint32_t *__restrict__ ring_cnt,
                                                                       const unsigned long long *__restrict__ occ,
@@ -2055,6 +2062,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_lookup_half_merge_kernel(const un
     const uint32_t n_slots = 1u << log2_bucket, smask = n_slots - 1u;
     const uint32_t n_occ = n_slots >= 64u ? n_slots >> 6 : 1u;
     const int64_t r0 = (int64_t)off[blockIdx.x], r1 = (int64_t)off[blockIdx.x + 1];
+    if (PIECE && r1 == r0) return;                               // (uniform: the piece has no record of this bucket)
     const int64_t rs = n_short && CAP > SHORT_MAX ? r0 + (int64_t)n_short[blockIdx.x] : r0;
     uint16_t *bins16 = reinterpret_cast<uint16_t *>(lds);
     const uint16_t *bi = bins_in + bin_elem[blockIdx.x];
@@ -2289,6 +2297,27 @@ extern "C" int64_t pg_mini_records_bytes(int64_t n_records, const pg_table *t)
     if (rc) return rc;
     const size_t n = ((size_t)n_records + 255) / 256 * 256 + 256;
     return (int64_t)mini_rec_layout(n, (size_t)1 << (t->log2_slots - t->log2_bucket_slots)).total;
+}
+
+// where the second meta plane of a record workspace of rec_ws_bytes starts: [bases A | bases B | meta A | meta B], cap records each
+extern "C" int64_t pg_mini_records_meta_offset(int64_t rec_ws_bytes, const pg_table *t)
+{
+    int rc = check_mini(t, "pg_mini_records_meta_offset");
+    if (rc) return rc;
+    const size_t cap = mini_rec_cap(rec_ws_bytes, (size_t)1 << (t->log2_slots - t->log2_bucket_slots));
+    if (cap < 256) return pg_fail(PG_EINVAL, "pg_mini_records_meta_offset: record workspace of %lld bytes (pg_mini_records_bytes)", (long long)rec_ws_bytes);
+    return (int64_t)(20 * cap);
+}
+
+// the library's own rule for the merged lookups (mini_merge_form): 1 where they apply to n_rows rows of this geometry, else 0
+extern "C" int pg_mini_merge_form_applies(const pg_table *t, int64_t n_rows, int vsize)
+{
+    int rc = check_mini(t, "pg_mini_merge_form_applies");
+    if (rc) return rc;
+    if (n_rows < 0) return pg_fail(PG_EINVAL, "pg_mini_merge_form_applies: negative row count");
+    if (t->kind != PG_TABLE_MINI) return 0;                       // (the merged lookups work on packed slots)
+    const pg_rows r{nullptr, nullptr, n_rows, nullptr};
+    return mini_merge_form(t, &r, vsize) ? 1 : 0;
 }
 
 extern "C" int64_t pg_mini_shuffle_bytes(int64_t n_words, int64_t n_rows, int vsize)
@@ -2853,6 +2882,82 @@ extern "C" int pg_mini_lookup_half(const pg_table *local, const pg_rows *rows, c
     else PG_LOOKUP_HALF(BIG_BLOCK, 1024);
 #undef PG_LOOKUP_HALF
     return check_launch("pg_mini_lookup_half");
+}
+
+// ---- the count half in pieces (N > 1 ranks; see HalfArgs): `local` has real slots here (2^log2_slots words), which the pieces
+// count into; the last piece leaves entries, occupancy and fill in half_ws as one pg_mini_count_half would
+extern "C" int pg_mini_count_half_piece(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
+                                        const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                        int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
+                                        int64_t *fill, int first, int last, uint32_t *status, void *stream)
+{
+    int rc = check_mini(local, "pg_mini_count_half_piece");
+    if (rc) return rc;
+    if (local->kind != PG_TABLE_MINI) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: packed mini tables (13 <= k <= %d)", PG_HASH_MAX_K);
+    if (window < 1 || vsize < 1 || !merge_ws || merge_ws_words <= 0) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: needs the abundance parameters and the slot buffer");
+    if (!half_ws || !fill) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: null argument");
+    const MiniHalfLayout hl = mini_half_layout(local);
+    if ((int64_t)hl.total > half_ws_bytes || (reinterpret_cast<uintptr_t>(half_ws) & 255) != 0)
+        return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: workspace of %lld bytes (256-byte aligned), %lld needed", (long long)half_ws_bytes, (long long)hl.total);
+    char *hw = (char *)half_ws;
+    const int accum = first ? (last ? 4 : 1) : (last ? 3 : 2);
+    const HalfArgs hv{(unsigned long long *)(hw + hl.ent_off), (unsigned long long *)(hw + hl.occ_off), (long long *)fill, (uint32_t *)(hw + hl.ring_off), accum};
+    return mini_count_impl(codes, valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize, nullptr, 0,
+                           status, stream, &hv, merge_ws, merge_ws_words);
+}
+
+// the lookups of one piece of a count half in pieces, once the bins are back: plan_ws / meta / merge_ws of that piece (as for
+// pg_mini_lookup_piece), half_ws / bins_in / bin_elem as for pg_mini_lookup_half; the row shuffle's regions of the whole stream
+// were prepared by pg_mini_lookup_begin(local, rows, n_words_total, ...)
+extern "C" int pg_mini_lookup_half_piece(const pg_table *local, const pg_rows *rows, const void *plan_ws, int64_t plan_ws_bytes, int64_t n_words_piece,
+                                         const uint32_t *meta, int64_t n_words_total, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes,
+                                         const void *merge_ws, const void *half_ws, int64_t half_ws_bytes,
+                                         const uint16_t *bins_in, const int64_t *bin_elem, uint32_t *status, void *stream)
+{
+    int rc = check_mini(local, "pg_mini_lookup_half_piece");
+    if (rc) return rc;
+    if (local->kind != PG_TABLE_MINI || !rows || !plan_ws || !meta || !shuffle_ws || !merge_ws || !half_ws || !bins_in || !bin_elem || !status || vsize < 1)
+        return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: bad argument");
+    if ((rc = check_mini_rows(rows, "pg_mini_lookup_half_piece"))) return rc;
+    if (!mini_merge_form(local, rows, vsize)) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: the merged lookups do not apply to these rows");
+    MiniPlan p;
+    plan_mini(local, n_words_piece, &p);
+    if ((int64_t)p.total > plan_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: plan workspace does not match n_words_piece");
+    if (!p.bits2) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: needs more than 256 buckets");
+    const MiniHalfLayout hl = mini_half_layout(local);
+    if ((int64_t)hl.total > half_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: workspace does not match the table");
+    pg_shuffle_ctx ctx;
+    if ((rc = pg_internal_shuffle_prepare(n_words_total * 32, rows, vsize, shuffle_ws, shuffle_ws_bytes, stream, &ctx, MINI_ONE_PASS_BITS, 1, 1))) return rc;
+    if (ctx.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: %d first-pass digits of the row shuffle", ctx.gb1);
+    const ShufArgs sh{ctx.goff, ctx.gcur1, ctx.words_out, ctx.gb1, ctx.gb2, ctx.dshift, 0, ctx.words_cap};
+    const char *ws = (const char *)plan_ws;
+    const auto *off = (const unsigned long long *)(ws + p.off_off);
+    const auto *cur2 = (const unsigned long long *)(ws + p.cur2_off);
+    const auto *wbeg = (const unsigned long long *)(ws + p.wbeg_off);
+    const auto *occ = (const unsigned long long *)((const char *)half_ws + hl.occ_off);
+    const auto *ring = (const uint32_t *)((const char *)half_ws + hl.ring_off);
+    const int cap_k = mini_cap(local->k);
+    const unsigned long long *n_short = cap_k > SHORT_MAX ? cur2 : (const unsigned long long *)nullptr;
+    const unsigned nb = 1u << p.bits;
+    hipStream_t s = (hipStream_t)stream;
+    // (the workgroup geometry of pg_mini_lookup_half's merged form)
+#define PG_LOOKUP_HALF_P(CAP_, BLK_, DIG_)                                                                                  \
+    do {                                                                                                                    \
+        const size_t lds_ = MergeLds<BLK_, DIG_>::END;                                                                      \
+        if ((rc = raise_lds_limit((const void *)(mini_lookup_half_merge_kernel<CAP_, BLK_, DIG_, true>), lds_, "pg_mini_lookup_half_piece"))) return rc; \
+        hipLaunchKernelGGL((mini_lookup_half_merge_kernel<CAP_, BLK_, DIG_, true>), dim3(nb), dim3(BLK_), lds_, s, off, n_short, wbeg, ring, occ, \
+                           bins_in, (const long long *)bin_elem, local->log2_bucket_slots, ctx.vbits, (const uint32_t *)merge_ws, meta, sh, status); \
+    } while (0)
+#define PG_LOOKUP_HALF_PC(CAP_) do { if (ctx.gb1 > 10) PG_LOOKUP_HALF_P(CAP_, BIG_BLOCK, 2048); else if (local->log2_bucket_slots <= 13 && !getenv("PG_LOOKUP_HALF_1024")) PG_LOOKUP_HALF_P(CAP_, 512, 1024); else PG_LOOKUP_HALF_P(CAP_, BIG_BLOCK, 1024); } while (0)
+    switch (cap_k) {
+    case 1: case 2: case 3: case 4: PG_LOOKUP_HALF_PC(4); break;
+    case 5: case 6: PG_LOOKUP_HALF_PC(6); break;
+    case 7: case 8: PG_LOOKUP_HALF_PC(8); break;
+    default: PG_LOOKUP_HALF_PC(9); break;
+    }
+#undef PG_LOOKUP_HALF_PC
+#undef PG_LOOKUP_HALF_P
+    return check_launch("pg_mini_lookup_half_piece");
 }
 
 extern "C" int pg_mini_abundance_from_emitted(const pg_table *t, const pg_rows *rows, int vsize, int32_t *abd_out,

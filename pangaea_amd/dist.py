@@ -573,16 +573,46 @@ class MiniSharded:
         self.local = KmerTable(k, "mini", torch.zeros(1, dtype=torch.int64, device=device), bits + local_log2_bucket, local_log2_bucket)
         self.bytes_sent = self.bytes_received = 0
 
+    @property
+    def pieces(self) -> int:
+        """word ranges this rank's last count half was done in (1: one piece; more where its scratch would not fit, or
+        PANGAEA_MINI_PIECE_WORDS forced a piece size)"""
+        return self.local._mini_pieces
+
     @staticmethod
-    def geometry(union_distinct: int, local_distinct: int, union_load: float = 0.6, local_load: float = 0.45):
-        """(union_log2_slots, union_log2_bucket, local_log2_bucket) for these HyperLogLog estimates"""
+    def max_local_log2_bucket(n_rows: int | None) -> int:
+        """the largest local bucket whose slot numbers fit beside a row number of ``n_rows`` rows in one 32-bit word (the
+        count half's slot form: rows < 2^(32 - log2 bucket slots) - 1)"""
+        from . import _lib
+        lb = _lib.BUCKET_MAX_LOG2_SLOTS
+        while n_rows is not None and lb > 4 and not int(n_rows) < (1 << (32 - lb)) - 1:
+            lb -= 1
+        return lb
+
+    @staticmethod
+    def rows_apply(k: int, n_rows: int, vsize: int) -> bool:
+        """may the count half take ``n_rows`` rows: up to 2^17 - 1 as always, beyond where the library's merged lookups apply
+        (``pg_mini_merge_form_applies`` on the local bucket ``geometry`` gives these rows: at most 2^19 rows at vsize 400)"""
+        from . import _lib
+        import ctypes as C
+        if 0 < n_rows < (1 << 17):
+            return True
+        lb = MiniSharded.max_local_log2_bucket(n_rows)
+        bits = MiniSharded.MIN_LOG2_BUCKETS
+        desc = _lib.pg_table(_lib.TABLE_MINI, int(k), bits + lb, lb, 1)      # (geometry only: the data pointer is never read)
+        return _lib.check(_lib.load().pg_mini_merge_form_applies(C.byref(desc), int(n_rows), int(vsize))) == 1
+
+    @staticmethod
+    def geometry(union_distinct: int, local_distinct: int, union_load: float = 0.6, local_load: float = 0.45, n_rows: int | None = None):
+        """(union_log2_slots, union_log2_bucket, local_log2_bucket) for these HyperLogLog estimates (``n_rows``: the local
+        bucket stays within ``max_local_log2_bucket``)"""
         from . import _lib
         import math
         log2_u = max(MiniSharded.MIN_LOG2_BUCKETS + 4, math.ceil(math.log2(max(1024.0, union_distinct / union_load))))
         lb_u = min(_lib.BUCKET_MAX_LOG2_SLOTS, log2_u - MiniSharded.MIN_LOG2_BUCKETS)
         bits = log2_u - lb_u
         need = max(16.0, local_distinct / local_load / (1 << bits))
-        lb_l = min(lb_u, max(4, math.ceil(math.log2(need))))
+        lb_l = min(lb_u, max(4, math.ceil(math.log2(need))), MiniSharded.max_local_log2_bucket(n_rows))
         return log2_u, lb_u, lb_l
 
     def count(self, stream: ReadStream, plan, check: bool = True) -> "MiniSharded":
@@ -593,12 +623,27 @@ class MiniSharded:
         self.lookup_half()
         if check:
             bits = self.status_bits()
+            if bits & self._overflow_bit() and self.local.can_reexchange():
+                # (a count half in pieces keeps its entries, fills and pieces: the exchange and the lookups again, no recount)
+                self._cap1 = None
+                keep = ~self._overflow_bit()
+                self.local.status.bitwise_and_(keep); self.union.status.zero_()
+                self.union.reset()
+                self.exchange()
+                self.lookup_half()
+                return self.count_checked()
             if bits & self._overflow_bit():
                 # the parts of this batch did not fit the size kept from an earlier one (``exchange``): ask again, count again
                 self._cap1 = None
                 self.local.status.zero_(); self.union.status.zero_()
                 return self.count(stream, plan, check=True)
             self.check_status(bits)
+        return self
+
+    def count_checked(self) -> "MiniSharded":
+        """``check_status`` of a count that has been exchanged again (an exchange that overflows even with the size just read is
+        not retried a second time: raised)"""
+        self.check_status()
         return self
 
     @staticmethod
@@ -609,7 +654,7 @@ class MiniSharded:
     def count_half(self, stream: ReadStream, plan) -> None:
         """plan -> first and second scatter pass -> the bucket workgroups' count half (this rank's reads only)"""
         self.local.reset(); self.union.reset()
-        self.local.count_half(stream, plan, (self.window, self.vsize), check=False)
+        self.local.count_half(stream, plan, (self.window, self.vsize), check=False, world=dist.get_world_size(self.group))
 
     def exchange(self) -> None:
         """entries -> owners (all-to-all, 8 bytes per distinct k-mer of this rank) -> merged inside LDS by the owners, which keep the
@@ -739,7 +784,8 @@ def features_sharded_mini(stream: ReadStream, plan, k: int, k_tnf: int | None, w
     loc = loc.to(stream.device) if dist.get_backend(group) == "nccl" else loc
     dist.all_reduce(loc, op=dist.ReduceOp.MAX, group=group)
     from . import _lib
-    log2_u, lb_u, lb_l = MiniSharded.geometry(total, int(loc.item()))
+    log2_u, lb_u, lb_l = MiniSharded.geometry(total, int(loc.item()), n_rows=plan.n_rows)
+    lb_top = MiniSharded.max_local_log2_bucket(plan.n_rows)
 
     def key_partitioned():
         # a union that the super-k-mer geometry cannot hold (more than 2^16 buckets of 2^14 slots): the key-partitioned exchange,
@@ -757,7 +803,7 @@ def features_sharded_mini(stream: ReadStream, plan, k: int, k_tnf: int | None, w
             tnf, abd = kmer.features(stream, plan, k_tnf=k_tnf, table=ms.local, window=window, vsize=vsize)
             return tnf, abd, ms
         del ms
-        lb_l = min(lb_l + 1, lb_u)
+        lb_l = min(lb_l + 1, lb_u, lb_top)
         log2_u += 1
         lb_u = min(_lib.BUCKET_MAX_LOG2_SLOTS, lb_u + 1)
     raise _lib.PangaeaError(_lib.PG_ETABLEFULL, "the sharded super-k-mer tables stayed full")

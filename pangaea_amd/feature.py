@@ -107,10 +107,13 @@ def _ingest(reads1: str, reads2: str | None, world: int, stream_cache: str | Non
 
 def _sharded_mini_applies(stream, plan, k, window, vsize, lowercase_is_base) -> bool:
     """may the multi-rank super-k-mer form (``dist.MiniSharded``) take this input?  Packed slots (13 <= k <= 21), rows the
-    partition records can name, exact bins, no soft-masked / quality-masked planes -- and the SAME answer on every rank."""
+    partition records can name, exact bins, no soft-masked / quality-masked planes -- and the SAME answer on every rank.
+    Rows: up to 2^17 - 1 in any form of the lookups; beyond, where the library's merged lookups apply to the local geometry
+    (``MiniSharded.rows_apply`` asks ``pg_mini_merge_form_applies``: at most 2^19 rows at -v 400), the row shuffle then taking
+    two scatter passes.  A share too large for one piece of scratch is counted in pieces (``KmerTable.count_half``)."""
     from . import _lib
-    ok = (_lib.MINI_MIN_K <= k <= _lib.HASH_MAX_K and plan.shuffle_ok and 0 < plan.n_rows < (1 << 17)
-          and 1 <= vsize <= _lib.SHUFFLE_MAX_VSIZE and window >= 1 and window * vsize <= _lib.HASH_COUNT_SAT
+    ok = (_lib.MINI_MIN_K <= k <= _lib.HASH_MAX_K and plan.shuffle_ok and plan.n_rows > 0
+          and 1 <= vsize <= _lib.SHUFFLE_MAX_VSIZE and pdist.MiniSharded.rows_apply(k, plan.n_rows, vsize) and window >= 1 and window * vsize <= _lib.HASH_COUNT_SAT
           and stream.table_valid(lowercase_is_base) is stream.valid and stream.rows_inside_table
           and os.environ.get("PANGAEA_NO_MINI", "0") in ("", "0"))
     return pdist.everyone(ok)

@@ -66,6 +66,8 @@ class KmerTable:
         self._mini_pieces = 1            # word ranges the last count of a mini table was done in (``_count_mini_pieces``)
         self._half = None                # (fill, n_words, rows, window, vsize) between count_half and lookup_half (N > 1 ranks)
         self._half_ws = None
+        self._half_pieces = None         # ([(plan ws, slot buffer, meta words, words) per piece], held tensors) of a count half in pieces
+        self._half_world = 1             # ranks the count half's exchange goes to (its buffers count in the pieces decision)
         self._merge_ws = None            # the provisional words of the merged lookups (fixed slots per record)
 
     # ------------------------------------------------------------------ construction
@@ -343,16 +345,18 @@ class KmerTable:
         return (codes.data_ptr(), codes._version, plane.data_ptr(), plane._version, word_begin, word_end, id(keep), bool(lenient),
                 log2_slots, log2_bucket)
 
-    def count_half(self, stream: ReadStream, rows: "Plan", emit: tuple, check: bool = True) -> "KmerTable":
+    def count_half(self, stream: ReadStream, rows: "Plan", emit: tuple, check: bool = True, world: int = 1) -> "KmerTable":
         """N > 1 ranks (``dist.MiniSharded``): the COUNT half of the super-k-mer pipeline on this rank's reads.  This table object
         only carries the rank's LOCAL geometry (the union's bucket count, slots for the rank's own k-mers): its slots are never
-        written.  Left behind for ``dist``: the buckets' entries and occupancy (``_half``), the provisional words of the rows."""
+        written -- except by a count in pieces (``_count_half_pieces``; ``world`` sizes the exchange's buffers in that decision).
+        Left behind for ``dist``: the buckets' entries and occupancy (``_half``), the provisional words of the rows."""
         if self.kind != "mini":
             raise ValueError("count_half() is for packed mini tables (13 <= k <= 21)")
         _require_gpu(stream.codes, "the read stream")
         plane = stream.table_valid(False)
         if plane is not stream.valid or not stream.rows_inside_table:
             raise ValueError("count_half() takes plain streams (no soft-masked / quality-masked planes)")
+        self._half_world = int(world)
         return self._count_mini(stream, 0, stream.n_words, plane, rows, lambda plan: C.byref(plan.rows_desc), emit, False, check, half=True)
 
     def _count_mini(self, stream, word_begin, word_end, table_plane, rows, rows_arg, emit, lenient, check, half=False):
@@ -373,6 +377,10 @@ class KmerTable:
         piece_words = self._piece_words(n_words, fuse and not half)
         if piece_words is not None:
             return self._count_mini_pieces(stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check)
+        self._half_pieces = None
+        piece_words = self._half_piece_words(n_words, keep, int(emit[1])) if half and fuse else None
+        if piece_words is not None:
+            return self._count_half_pieces(stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check)
         key = self._plan_key(stream.codes, table_plane, word_begin, word_end, keep, lenient, self.log2_slots, self.log2_bucket)
         held = (stream.codes, table_plane)               # (kept with the plan: see _plan_key)
         with torch.cuda.device(self.device):
@@ -529,8 +537,8 @@ class KmerTable:
                                                  rec_ws.data_ptr(), rec_ws.numel(), window, vsize, merge_ws.data_ptr(), merge_ws.numel(),
                                                  1 if idx == 0 else 0, self.status.data_ptr(), sp))
                 # the bucket-ordered records' meta words (lengths, rows): the second meta plane of [bases A | bases B | meta A | meta B]
-                cap = rec_ws.numel() // 24 // 256 * 256
-                meta = rec_ws[20 * cap: 20 * cap + 4 * n_records].view(torch.int32).clone()
+                moff = _lib.check(L.pg_mini_records_meta_offset(rec_ws.numel(), self.desc()))
+                meta = rec_ws[moff: moff + 4 * n_records].view(torch.int32).clone()
                 kept.append((plan_ws, merge_ws, meta, w1 - w0))
             rec_ws = None
             need = _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, keep.n_rows, vsize, self.desc()))
@@ -554,6 +562,83 @@ class KmerTable:
             self.check_status()
         return self
 
+    def _half_piece_words(self, n_words: int, keep: "Plan", vsize: int):
+        """``_piece_words`` for a count half (N > 1 ranks): None (one piece) or the words per piece.  PANGAEA_MINI_PIECE_WORDS forces
+        a piece size as on one GPU; otherwise ``half_piece_words`` decides from the free device memory, to which the workspaces this
+        table holds from an earlier count are added back (they are reused or replaced)."""
+        L = _lib.load()
+        if (self.kind != "mini" or self.n_buckets <= 256 or os.environ.get("PG_MINI_MERGE", "1") in ("", "0")
+                or _lib.check(L.pg_mini_merge_form_applies(self.desc(), keep.n_rows, vsize)) != 1):
+            return None                                          # (the pieces' kernels: packed slots, both scatter passes, the merged lookups)
+        forced = os.environ.get("PANGAEA_MINI_PIECE_WORDS")
+        if forced:
+            w = max(_lib.WORD_ALIGN, int(forced) // _lib.WORD_ALIGN * _lib.WORD_ALIGN)
+            return w if w < n_words else None
+        free, _ = torch.cuda.mem_get_info(self.device)
+        free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # (cached blocks count as free)
+        held = [self._mini_rec_ws, self._shuffle_ws, self._merge_ws, self._half_ws] + ([self.data] if self.data.numel() > 1 else [])
+        free += sum(int(t.numel()) * t.element_size() for t in held if t is not None)
+        w = half_piece_words(free, n_words, self.log2_slots, self.log2_bucket, keep.n_rows, getattr(self, "_half_world", 1))
+        return w if w is not None and w < n_words else None
+
+    def _count_half_pieces(self, stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check):
+        """the count half (``count_half``) of a stream counted in word ranges of ``piece_words`` (include/pangaea_feat.h:
+        pg_mini_count_half_piece): every piece -> its plan, both scatter passes, the count INTO this table's own slots (allocated
+        here: 8 bytes x 2^log2_slots), its 2-byte provisional slots and its records' meta words kept; the last piece leaves entries,
+        occupancy and fill as one count half does.  ``lookup_half`` then looks every piece up with the bins the owners sent back."""
+        L = _lib.load()
+        valid_ptr = table_plane.data_ptr()
+        window, vsize = int(emit[0]), int(emit[1])
+        n_words = word_end - word_begin
+        ranges = [(w0, min(word_end, w0 + piece_words)) for w0 in range(word_begin, word_end, piece_words)]
+        slack = (lambda n: n + n // 32 + 4096)
+        sp = _stream_ptr(self.device)
+        if self.data.numel() != 1 << self.log2_slots:            # (the slots the pieces count into: every slot is written by the first piece)
+            self.data = torch.empty(1 << self.log2_slots, dtype=torch.int64, device=self.device)
+            self._desc.data = self.data.data_ptr()
+        # (the one-piece workspaces are not used on this path: their memory goes back to the allocator)
+        self._mini_rec_ws = self._merge_ws = None
+        self._mini_plan = None
+        kept = []
+        with torch.cuda.device(self.device):
+            need = _lib.check(L.pg_mini_half_bytes(self.desc()))
+            if self._half_ws is None or self._half_ws.numel() != need:
+                self._half_ws = None
+                self._half_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            fill = torch.zeros(self.n_buckets, dtype=torch.int64, device=self.device)
+            rec_ws = None
+            for idx, (w0, w1) in enumerate(ranges):
+                need = _lib.check(L.pg_mini_plan_bytes(w1 - w0, self.desc()))
+                plan_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), sp))
+                head = plan_ws[:24].view(torch.int64).cpu()                 # (host wait, once per piece: records, -, long records)
+                n_records, n_long = int(head[0]), int(head[2])
+                need = _lib.check(L.pg_mini_records_bytes(slack(n_records), self.desc()))
+                if rec_ws is None or rec_ws.numel() < need:
+                    rec_ws = None
+                    rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                need = _lib.check(L.pg_mini_merge_words(w1 - w0, n_records, n_long, self.desc()))
+                merge_ws = torch.empty(need, dtype=torch.int32, device=self.device)
+                _lib.check(L.pg_mini_count_half_piece(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep),
+                                                      plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
+                                                      merge_ws.data_ptr(), merge_ws.numel(), self._half_ws.data_ptr(), self._half_ws.numel(),
+                                                      fill.data_ptr(), 1 if idx == 0 else 0, 1 if idx == len(ranges) - 1 else 0,
+                                                      self.status.data_ptr(), sp))
+                moff = _lib.check(L.pg_mini_records_meta_offset(rec_ws.numel(), self.desc()))
+                meta = rec_ws[moff: moff + 4 * n_records].view(torch.int32).clone()
+                kept.append((plan_ws, merge_ws, meta, w1 - w0))
+            rec_ws = None
+        self._half = (fill, n_words, keep, window, vsize)
+        self._half_pieces = (kept, (stream.codes, table_plane))
+        self._mini_pieces = len(ranges)
+        self._mini_optimistic = None
+        self._empty = False
+        self._records = None
+        self._emitted = None
+        if check:
+            self.check_status()
+        return self
+
     def plan_counts(self) -> tuple:
         """(records, records of more than four k-mers) of the partition plan in use -- read from the device on first use (a plan
         picked up without a host wait keeps them there)"""
@@ -571,6 +656,9 @@ class KmerTable:
         fill, n_words, keep, window, vsize = self._half
         assert bins.dtype == torch.int16 and bin_elem.dtype == torch.int64 and bin_elem.numel() == self.n_buckets
         L = _lib.load()
+        if getattr(self, "_half_pieces", None) is not None:
+            self._lookup_half_pieces(bins, bin_elem)
+            return
         plan_ws = self._mini_plan[1]
         with torch.cuda.device(self.device):
             _lib.check(L.pg_mini_lookup_half(self.desc(), C.byref(keep.rows_desc), plan_ws.data_ptr(), plan_ws.numel(),
@@ -583,6 +671,37 @@ class KmerTable:
         self._records = (keep, n_words)
         self._emitted = (window, vsize)
         self._half = None
+
+    def _lookup_half_pieces(self, bins: torch.Tensor, bin_elem: torch.Tensor) -> None:
+        """``lookup_half`` after a count half in pieces: the row shuffle's regions of the whole stream prepared once, then every
+        piece's provisional slots looked up with the bins.  The pieces stay kept: an exchange done again (``MiniSharded.count`` after
+        PG_STATUS_OVERFLOW_LIST) is looked up again without a recount."""
+        fill, n_words, keep, window, vsize = self._half
+        kept, held = self._half_pieces
+        L = _lib.load()
+        sp = _stream_ptr(self.device)
+        with torch.cuda.device(self.device):
+            need = _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, keep.n_rows, vsize, self.desc()))
+            if self._shuffle_ws is None or self._shuffle_ws.numel() < need:
+                self._shuffle_ws = None
+                self._shuffle_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            sws = self._shuffle_ws
+            _lib.check(L.pg_mini_lookup_begin(self.desc(), C.byref(keep.rows_desc), n_words, vsize, sws.data_ptr(), sws.numel(), sp))
+            for plan_ws, merge_ws, meta, nw in kept:
+                _lib.check(L.pg_mini_lookup_half_piece(self.desc(), C.byref(keep.rows_desc), plan_ws.data_ptr(), plan_ws.numel(), nw, meta.data_ptr(),
+                                                       n_words, vsize, sws.data_ptr(), sws.numel(), merge_ws.data_ptr(),
+                                                       self._half_ws.data_ptr(), self._half_ws.numel(), bins.data_ptr(), bin_elem.data_ptr(),
+                                                       self.status.data_ptr(), sp))
+            # (``abundance_from_records`` hands a plan workspace of the whole range to pg_mini_abundance_from_emitted, which only checks its size)
+            whole = torch.empty(_lib.check(L.pg_mini_plan_bytes(n_words, self.desc())), dtype=torch.uint8, device=self.device)
+        self._mini_plan = (("pieces", len(kept)), whole, sum(int(m.numel()) for _, _, m, _ in kept), keep, held, 0)
+        self._records = (keep, n_words)
+        self._emitted = (window, vsize)
+
+    def can_reexchange(self) -> bool:
+        """does this table still hold what the exchange sends (a count half in pieces keeps its entries, fills and pieces until
+        the next count)?"""
+        return self._half is not None and getattr(self, "_half_pieces", None) is not None
 
     def prefetch_plan(self, stream: ReadStream, rows: "Plan | None", side: "torch.cuda.Stream",
                       after: "torch.cuda.Event | None" = None) -> None:
@@ -922,6 +1041,32 @@ class KmerTable:
         codes, counts = key42_inverse(s >> np.uint64(_lib.HASH_COUNT_BITS)), s & np.uint64((1 << _lib.HASH_COUNT_BITS) - 1)
         order = np.argsort(codes)
         return codes[order], counts[order]
+
+
+def half_piece_words(free_bytes: int, n_words: int, local_log2_slots: int, local_log2_bucket: int, n_rows: int, world: int):
+    """words per piece of an N-rank count half (``KmerTable.count_half``): ``n_words`` (one piece) when everything the rank holds
+    across the exchange fits 85 % of ``free_bytes``, fewer when only pieces fit, None when not even pieces do.  Per word of the
+    stream: the record workspace (one piece at a time), the merged lookups' 2-byte slots and the records' meta words (kept for every
+    piece), the piece plans and the row shuffle's word buffers (two of them when the rows take two scatter passes: more than 2^11
+    groups of 64).  Fixed: ``pg_mini_half_bytes`` (entry slabs, occupancy), the exchange's send and receive buffers and both bins
+    buffers (at most every local slot is an entry, padded to the longest part), and -- in pieces -- the local slots themselves."""
+    rec, slots, words = KmerTable._PIECE_BYTES_PER_WORD
+    meta, plan = 4 * 7, 4
+    groups = max(1, (int(n_rows) + 63) // 64)
+    if (groups - 1).bit_length() > 11:
+        words *= 2
+    n_slots = 1 << int(local_log2_slots)
+    n_buckets = n_slots >> int(local_log2_bucket)
+    half = 8 * n_slots + 8 * n_buckets * max(1, (1 << int(local_log2_bucket)) // 64) + 4 * n_buckets
+    parts = int(1.04 * n_slots) + 8 * int(world)
+    exchange = (8 + 8 + 2 + 2) * parts
+    budget = 0.85 * free_bytes
+    if (rec + slots + words + plan) * n_words + half + exchange <= budget:
+        return int(n_words)
+    room = budget - half - exchange - 8 * n_slots - (slots + meta + words + plan) * n_words
+    if room <= rec * 4 * _lib.WORD_ALIGN:
+        return None
+    return max(_lib.WORD_ALIGN, int(room / rec) // _lib.WORD_ALIGN * _lib.WORD_ALIGN)
 
 
 _KEY_MASK = np.uint64((1 << 42) - 1)
