@@ -224,6 +224,11 @@ enum { PG_TABLE_DENSE = 1, PG_TABLE_HASH = 2, PG_TABLE_WIDE = 3, PG_TABLE_MINI =
 #define PG_MINI_MAX_LOG2_BUCKETS 16
 #define PG_MINI_MAX_ROWS ((1 << 20) - 2)
 #define PG_MINI_WIDE_MAX_LOG2_BUCKET_SLOTS 13
+/* the bucket size of packed mini tables (k <= 21) whose caller names none, once they have 2^(PG_MINI_MAX_LOG2_BUCKETS +
+ * PG_MINI_LARGE_LOG2_BUCKET_SLOTS) slots or more: buckets of 2^13 slots (64 KiB: two counting workgroups per CU) instead of the
+ * largest that LDS holds, as many as PG_MINI_MAX_LOG2_BUCKETS allows -- a 2^29-slot table has 2^16 buckets of 2^13 slots, not
+ * 2^15 of 2^14; smaller tables keep buckets of min(2^log2_slots, 2^PG_BUCKET_MAX_LOG2_SLOTS) slots */
+#define PG_MINI_LARGE_LOG2_BUCKET_SLOTS 13
 #define PG_DENSE_MAX_K 16
 #define PG_HASH_MAX_K 21
 #define PG_WIDE_MAX_K 31

@@ -561,36 +561,47 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
 
 // ---- A2': region -> buckets.  tiles_x workgroups per region (all of them on one XCD, see below), its records are
 // [off[region << bits2], off[(region + 1) << bits2]);
-// digit = the low bits2 bits of meta (+ 128 for a LONG record: more than short_max k-mers).  Inside its bucket's range
+// digit = the low bits2 bits of meta (+ DIG / 2 for a LONG record: more than short_max k-mers).  Inside its bucket's range
 // [off[b], off[b + 1]) the short records fill from the front (cursor[b]) and the long ones from the back (cursor_l[b]): the
 // bucket workgroups treat a record in as many unrolled steps as its class can have k-mers, so sorting the two classes apart
 // saves them the steps that short records would leave idle.  cursor[b] is the number of short records afterwards.
-constexpr int S2_RPL = 16;
-constexpr int S2_TILE = BLOCK * S2_RPL;
-// DIG digits: 2 classes x 128 buckets of a region (tables of up to 2^15 buckets), or x 256 (2^16 buckets: the geometry of several
-// ranks -- until round 4 those tables had 512 first-pass regions instead, whose runs of six records per round cost that pass 1.6 ms)
-template <int DIG> struct Scatter2Lds {
-    uint64_t bases[S2_TILE];
-    uint32_t meta[S2_TILE];
+// DIG digits: 2 classes x 128 buckets of a region (tables of up to 2^15 buckets), or x 256 (2^16 buckets).  A tile is BLK x RPL
+// records staged in LDS (12 bytes each); what the pass costs beyond a device copy is the partial 128-byte lines at the ends of
+// the runs a tile appends to its digits, so both forms keep 16 or more records per digit and tile: 256 x 16 records for 256
+// digits, 512 x 24 for 512 (until round 5 4096 records there too: runs of eight, 3.75 against 2.77 ms).  The larger tile takes
+// 154 KiB of the CU's 160 KiB of LDS, one workgroup per CU, so its workgroups walk several tiles each and load the next tile
+// into registers before they store the current one (PREFETCH).
+template <int DIG, int BLK, int RPL> struct S2Geom {
+    static constexpr int TILE = BLK * RPL;
+    // kwords rides in the high half of the rank counters when a tile's k-mers stay below 2^16, else it has counters of its own
+    static constexpr bool PACK_KW = TILE * MINI_MAX_WINDOW < 65536;
+};
+template <int DIG, int BLK, int RPL> struct Scatter2Lds {
+    uint64_t bases[S2Geom<DIG, BLK, RPL>::TILE];
+    uint32_t meta[S2Geom<DIG, BLK, RPL>::TILE];
     uint32_t cnt[DIG];
+    uint32_t kw[S2Geom<DIG, BLK, RPL>::PACK_KW ? 1 : DIG];
     uint32_t start[DIG + 1];
     unsigned long long gbase[DIG];
-    uint32_t wave_tot[WAVES];
+    uint32_t wave_tot[BLK / 64];
 };
-template <int DIG>
-__global__ __launch_bounds__(BLOCK) void mini_scatter2_kernel(const uint64_t *__restrict__ in_bases, const uint32_t *__restrict__ in_meta,
-                                                              const unsigned long long *__restrict__ off, int bits2, int tiles_x, int short_max,
-                                                              uint64_t *__restrict__ out_bases, uint32_t *__restrict__ out_meta,
-                                                              unsigned long long *__restrict__ cursor, unsigned long long *__restrict__ cursor_l,
-                                                              unsigned long long *__restrict__ kwords,
-                                                              const unsigned long long *__restrict__ header, unsigned long long rec_cap, uint32_t *status)
+template <int DIG, int BLK, int RPL, bool PREFETCH>
+__global__ __launch_bounds__(BLK) void mini_scatter2_kernel(const uint64_t *__restrict__ in_bases, const uint32_t *__restrict__ in_meta,
+                                                            const unsigned long long *__restrict__ off, int bits2, int tiles_x, int short_max,
+                                                            uint64_t *__restrict__ out_bases, uint32_t *__restrict__ out_meta,
+                                                            unsigned long long *__restrict__ cursor, unsigned long long *__restrict__ cursor_l,
+                                                            unsigned long long *__restrict__ kwords,
+                                                            const unsigned long long *__restrict__ header, unsigned long long rec_cap, uint32_t *status)
 {
     if (header[0] > rec_cap || (*status & PG_STATUS_PLAN_MISMATCH)) return;      // (a plan of another stream: see mini_count_kernel)
-    // kwords[b] += the k-mers of bucket b that lie inside a row (= the words its workgroup will emit): they ride in the high
-    // half of the tile's rank counters -- a tile has 4096 records of at most 9 k-mers, both halves stay below 2^16
-    static_assert(S2_TILE * MINI_MAX_WINDOW < 65536, "two 16-bit halves per rank counter");
-    __shared__ Scatter2Lds<DIG> L;
-    constexpr int DPT = DIG / BLOCK;                            // digits per lane: threadIdx.x * DPT + q
+    constexpr int TILE = S2Geom<DIG, BLK, RPL>::TILE;
+    constexpr bool PACK_KW = S2Geom<DIG, BLK, RPL>::PACK_KW;
+    // kwords[b] += the k-mers of bucket b that lie inside a row (= the words its workgroup will emit)
+    static_assert(TILE < 65536 && DIG <= 65536, "rank and digit share a 32-bit word");
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+    Scatter2Lds<DIG, BLK, RPL> &L = *reinterpret_cast<Scatter2Lds<DIG, BLK, RPL> *>(lds_raw);
+    constexpr int DPT = DIG / BLK;                              // digits per lane: threadIdx.x * DPT + q
+    static_assert(DPT >= 1 && DPT * BLK == DIG, "whole digits per lane");
     constexpr uint32_t CLS = DIG / 2;                           // the class bit of a digit
     const int n_dig = 1 << bits2;
     const uint32_t dmask = (uint32_t)n_dig - 1u;
@@ -602,40 +613,56 @@ __global__ __launch_bounds__(BLOCK) void mini_scatter2_kernel(const uint64_t *__
     const int64_t region = by_xcd ? (int64_t)(blockIdx.x % 8u) + 8 * (int64_t)((blockIdx.x / 8u) / (unsigned)tiles_x) : (int64_t)(blockIdx.x / tiles_x);
     const int64_t b0 = region << bits2;
     const int64_t r0 = (int64_t)off[b0], r1 = (int64_t)off[b0 + n_dig];
-    const int64_t n_tiles = (r1 - r0 + S2_TILE - 1) / S2_TILE;
+    const int64_t n_tiles = (r1 - r0 + TILE - 1) / TILE;
     auto digit_of = [&](uint32_t m) -> uint32_t {
         const int n = (int)((m >> META_D2_BITS) & (MINI_MAX_LEN - 1)) + 1;
         return (m & dmask) | (n > short_max ? CLS : 0u);
     };
-    for (int64_t tile = by_xcd ? (blockIdx.x / 8u) % (unsigned)tiles_x : blockIdx.x % tiles_x; tile < n_tiles; tile += tiles_x) {
+    uint64_t rb[RPL];
+    uint32_t rm[RPL], dr[RPL];
+    auto load_tile = [&](int64_t t0) {                          // all loads of the lane in flight together
 #pragma unroll
-        for (int q = 0; q < DPT; ++q) L.cnt[threadIdx.x * DPT + q] = 0;
-        lds_sync();
-        const int64_t t0 = r0 + tile * S2_TILE;
-        uint64_t rb[S2_RPL];
-        uint32_t rm[S2_RPL], dr[S2_RPL];
-#pragma unroll
-        for (int j = 0; j < S2_RPL; ++j) {                          // all loads of the lane in flight together
-            const int64_t i = t0 + j * BLOCK + threadIdx.x;
+        for (int j = 0; j < RPL; ++j) {
+            const int64_t i = t0 + j * BLK + threadIdx.x;
             rb[j] = i < r1 ? in_bases[i] : 0ull;
             rm[j] = i < r1 ? in_meta[i] : 0u;
         }
+    };
+    int64_t tile = by_xcd ? (blockIdx.x / 8u) % (unsigned)tiles_x : blockIdx.x % tiles_x;
+    if (PREFETCH && tile < n_tiles) load_tile(r0 + tile * TILE);
+    for (; tile < n_tiles; tile += tiles_x) {
 #pragma unroll
-        for (int j = 0; j < S2_RPL; ++j) {
-            const int64_t i = t0 + j * BLOCK + threadIdx.x;
+        for (int q = 0; q < DPT; ++q) {
+            L.cnt[threadIdx.x * DPT + q] = 0;
+            if constexpr (!PACK_KW) L.kw[threadIdx.x * DPT + q] = 0;
+        }
+        lds_sync();
+        const int64_t t0 = r0 + tile * TILE;
+        if (!PREFETCH) load_tile(t0);
+#pragma unroll
+        for (int j = 0; j < RPL; ++j) {
+            const int64_t i = t0 + j * BLK + threadIdx.x;
             if (i < r1) {
                 const uint32_t d = digit_of(rm[j]);
                 // (kwords == NULL: the merged lookups do not need the tally)
                 const uint32_t kw = kwords && (rm[j] >> META_ROW_SHIFT) != MINI_ROW_NONE ? ((rm[j] >> META_D2_BITS) & (MINI_MAX_LEN - 1)) + 1u : 0u;
-                dr[j] = (d << 16) | (atomicAdd(&L.cnt[d], 1u | (kw << 16)) & 0xffffu);
+                if constexpr (PACK_KW) {
+                    dr[j] = (d << 16) | (atomicAdd(&L.cnt[d], 1u | (kw << 16)) & 0xffffu);
+                } else {
+                    dr[j] = (d << 16) | atomicAdd(&L.cnt[d], 1u);
+                    if (kw) atomicAdd(&L.kw[d], kw);
+                }
             }
         }
         lds_sync();
         uint32_t kw_mine[DPT];                                      // (this lane's digits; the scan reads the same entries next)
 #pragma unroll
-        for (int q = 0; q < DPT; ++q) { kw_mine[q] = L.cnt[threadIdx.x * DPT + q] >> 16; L.cnt[threadIdx.x * DPT + q] &= 0xffffu; }
+        for (int q = 0; q < DPT; ++q) {
+            if constexpr (PACK_KW) { kw_mine[q] = L.cnt[threadIdx.x * DPT + q] >> 16; L.cnt[threadIdx.x * DPT + q] &= 0xffffu; }
+            else kw_mine[q] = L.kw[threadIdx.x * DPT + q];
+        }
         if constexpr (DPT == 1) scan_digits<DIG, true>(L.cnt, L.start, L.wave_tot);
-        else { lds_sync(); scan_digits_blk<DIG, BLOCK, true>(L.cnt, L.start, L.wave_tot); }
+        else { lds_sync(); scan_digits_blk<DIG, BLK, true>(L.cnt, L.start, L.wave_tot); }
         // the returning cursor adds (one per digit and tile) are issued first and consumed after the placement
         unsigned long long gpos[DPT];
 #pragma unroll
@@ -651,19 +678,21 @@ __global__ __launch_bounds__(BLOCK) void mini_scatter2_kernel(const uint64_t *__
             }
         }
 #pragma unroll
-        for (int j = 0; j < S2_RPL; ++j) {
-            const int64_t i = t0 + j * BLOCK + threadIdx.x;
+        for (int j = 0; j < RPL; ++j) {
+            const int64_t i = t0 + j * BLK + threadIdx.x;
             if (i < r1) {
                 const uint32_t at = L.start[dr[j] >> 16] + (dr[j] & 0xffffu);
                 L.bases[at] = rb[j];
                 L.meta[at] = rm[j];
             }
         }
+        // (the lane's records are in LDS: its registers take the next tile while the workgroup stores this one)
+        if (PREFETCH && tile + tiles_x < n_tiles) load_tile(r0 + (tile + tiles_x) * TILE);
 #pragma unroll
         for (int q = 0; q < DPT; ++q) L.gbase[threadIdx.x * DPT + q] = gpos[q];
         lds_sync();
         const uint32_t total = L.start[DIG];
-        for (uint32_t i = threadIdx.x; i < total; i += BLOCK) {     // flat sweep: the digit is in the record
+        for (uint32_t i = threadIdx.x; i < total; i += BLK) {       // flat sweep: the digit is in the record
             const uint32_t m = L.meta[i];
             const unsigned long long g = L.gbase[digit_of(m)] + i;
             gstore(out_bases, g, rec_cap, L.bases[i], status);
@@ -2523,19 +2552,26 @@ static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t
     const bool merge_a2 = window > 0 && merge_ws && merge_ws_words > 0 && mini_merge_form(t, rows, vsize);
     if (word_end > word_begin) {
         if (p.bits2) {
-            // about one workgroup per tile of a region (from the record capacity: the count itself is on the device): with the regions'
-            // workgroups on one XCD each, 96 workgroups per region walking a dozen tiles each took 3.32 ms where 576 to 1152 take 3.05
-            const int tiles_x = (int)std::min<size_t>(2048, std::max<size_t>(8, cap / ((size_t)S2_TILE << p.bits1) + 1));
-            if (p.bits2 > 7)
-                hipLaunchKernelGGL(mini_scatter2_kernel<512>, dim3((unsigned)(tiles_x << p.bits1)), dim3(BLOCK), 0, s, (const uint64_t *)bases_a, (const uint32_t *)meta_a,
-                                   (const unsigned long long *)off, p.bits2, tiles_x, mini_cap(t->k) > SHORT_MAX ? SHORT_MAX : 0, bases_b, meta_b, cur2, cur2l,
-                                   merge_a2 ? (unsigned long long *)nullptr : kwords,
-                                   (const unsigned long long *)header, (unsigned long long)cap, status);
-            else
-                hipLaunchKernelGGL(mini_scatter2_kernel<256>, dim3((unsigned)(tiles_x << p.bits1)), dim3(BLOCK), 0, s, (const uint64_t *)bases_a, (const uint32_t *)meta_a,
-                                   (const unsigned long long *)off, p.bits2, tiles_x, mini_cap(t->k) > SHORT_MAX ? SHORT_MAX : 0, bases_b, meta_b, cur2, cur2l,
-                                   merge_a2 ? (unsigned long long *)nullptr : kwords,
-                                   (const unsigned long long *)header, (unsigned long long)cap, status);
+            // 256 digits: about one workgroup per tile of a region (from the record capacity: the count itself is on the device); with
+            // the regions' workgroups on one XCD each, 96 workgroups per region walking a dozen tiles each took 3.32 ms where 576 to 1152
+            // take 3.05.  512 digits: one workgroup per CU fits, so 16 per region walk a dozen tiles each with the next one
+            // prefetched (tiles of 512 x 16 records: 2.99 ms with 16 per region; 8: 3.30, 32 to 64: 2.99-3.01, 128: 3.12, one tile
+            // per workgroup without the prefetch: 3.29.  512 x 20: 2.89-3.00, 512 x 24: 2.82-2.95)
+            const bool dig512 = p.bits2 > 7;
+            const size_t tile = dig512 ? (size_t)S2Geom<512, 512, 24>::TILE : (size_t)S2Geom<256, BLOCK, 16>::TILE;
+            const int tiles_x = (int)std::min<size_t>(dig512 ? 16 : 2048, std::max<size_t>(8, cap / (tile << p.bits1) + 1));
+#define PG_MINI_LAUNCH_S2(DIG_, BLK_, RPL_, PF_)                                                                                   \
+            do {                                                                                                            \
+                const size_t lds2 = sizeof(Scatter2Lds<DIG_, BLK_, RPL_>);                                                  \
+                if ((rc = raise_lds_limit((const void *)(mini_scatter2_kernel<DIG_, BLK_, RPL_, PF_>), lds2, "pg_mini_count"))) return rc; \
+                hipLaunchKernelGGL((mini_scatter2_kernel<DIG_, BLK_, RPL_, PF_>), dim3((unsigned)(tiles_x << p.bits1)), dim3(BLK_), lds2, s,   \
+                                   (const uint64_t *)bases_a, (const uint32_t *)meta_a, (const unsigned long long *)off, p.bits2, tiles_x, \
+                                   mini_cap(t->k) > SHORT_MAX ? SHORT_MAX : 0, bases_b, meta_b, cur2, cur2l,                \
+                                   merge_a2 ? (unsigned long long *)nullptr : kwords, (const unsigned long long *)header, (unsigned long long)cap, status); \
+            } while (0)
+            if (dig512) PG_MINI_LAUNCH_S2(512, 512, 24, true);
+            else PG_MINI_LAUNCH_S2(256, BLOCK, 16, false);
+#undef PG_MINI_LAUNCH_S2
         }
     }
     const bool slots_form = window > 0 && mini_slots_form(t, rows);

@@ -121,26 +121,42 @@ __global__ __launch_bounds__(BIG_BLOCK) void digit_scan_kernel(unsigned long lon
     for (int64_t i = a; i < b; ++i) { const unsigned long long v = row[i]; row[i] = run; run += v; }
 }
 
-// exclusive prefix sum of hist[n] -> off[n+1] (one workgroup)
+// exclusive prefix sum of hist[n] -> off[n+1] (one workgroup).  Tiles of BIG_BLOCK x SCAN_PER consecutive entries, SCAN_PER of
+// them per lane, scanned by wavefront shuffles: 65 536 bucket counts take 56 us, 32 768 take 30 (a lane walking n / 1024 entries
+// of its own and one lane adding up the 1024 partial sums: 150 and 80 us; 32 entries per lane: 78 and 41 us)
+constexpr int SCAN_PER = 8;
 __global__ __launch_bounds__(BIG_BLOCK) void scan_kernel(const unsigned long long *__restrict__ hist, int64_t n, unsigned long long *__restrict__ off)
 {
-    __shared__ unsigned long long part[BIG_BLOCK];
-    const int64_t per = (n + BIG_BLOCK - 1) / BIG_BLOCK;
-    const int64_t a = threadIdx.x * per, b = a + per < n ? a + per : n;
-    unsigned long long s = 0;
-    for (int64_t i = a; i < b; ++i) s += hist[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long run = 0;
-        for (int i = 0; i < BIG_BLOCK; ++i) { unsigned long long v = part[i]; part[i] = run; run += v; }
-        off[n] = run;
+    __shared__ unsigned long long wave_tot[BIG_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long carry = 0;                                   // (the same in every lane)
+    for (int64_t t0 = 0; t0 < n; t0 += (int64_t)BIG_BLOCK * SCAN_PER) {
+        const int64_t a = t0 + (int64_t)threadIdx.x * SCAN_PER;
+        unsigned long long v[SCAN_PER], sum = 0;
+#pragma unroll
+        for (int q = 0; q < SCAN_PER; ++q) { v[q] = a + q < n ? hist[a + q] : 0ull; sum += v[q]; }
+        unsigned long long incl = sum;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long o = __shfl_up(incl, d);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        unsigned long long run = carry + incl - sum, tile_tot = 0;
+#pragma unroll
+        for (int w = 0; w < BIG_BLOCK / 64; ++w) {
+            const unsigned long long t = wave_tot[w];
+            if (w < wave) run += t;
+            tile_tot += t;
+        }
+#pragma unroll
+        for (int q = 0; q < SCAN_PER; ++q) { if (a + q < n) off[a + q] = run; run += v[q]; }
+        carry += tile_tot;
+        __syncthreads();                                            // (wave_tot is rewritten by the next tile)
     }
-    __syncthreads();
-    unsigned long long run = part[threadIdx.x];
-    for (int64_t i = a; i < b; ++i) { off[i] = run; run += hist[i]; }
+    if (threadIdx.x == 0) off[n] = carry;
 }
-
 
 // -------------------------------------------------------------------------------- minimizer buckets (PG_TABLE_MINI)
 //

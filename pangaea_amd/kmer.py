@@ -119,6 +119,16 @@ class KmerTable:
         return _lib.BUCKET_MAX_LOG2_SLOTS if k <= _lib.HASH_MAX_K else _lib.MINI_WIDE_MAX_LOG2_BUCKET_SLOTS
 
     @staticmethod
+    def mini_default_log2_bucket(k: int, log2_slots: int) -> int:
+        """bucket size of a mini table whose caller names none: the largest that LDS holds, except for packed tables (k <= 21) of
+        2^(16 + 13) slots and more, which take buckets of 2^13 slots (two counting workgroups per CU), as many as the bucket count
+        allows (PG_MINI_LARGE_LOG2_BUCKET_SLOTS)"""
+        top = KmerTable.mini_max_log2_bucket(k)
+        if k <= _lib.HASH_MAX_K and log2_slots >= _lib.MINI_MAX_LOG2_BUCKETS + _lib.MINI_LARGE_LOG2_BUCKET_SLOTS:
+            return min(top, max(_lib.MINI_LARGE_LOG2_BUCKET_SLOTS, log2_slots - _lib.MINI_MAX_LOG2_BUCKETS))
+        return min(top, log2_slots)
+
+    @staticmethod
     def mini_applies(k: int, log2_slots: int, log2_bucket: int | None = None) -> bool:
         """can a MINI table (minimizer buckets, built from super-k-mers) hold 2^log2_slots slots for this k?"""
         if not _lib.MINI_MIN_K <= k <= _lib.WIDE_MAX_K:
@@ -131,10 +141,10 @@ class KmerTable:
     def mini_with_slots(cls, k: int, device, log2_slots: int, log2_bucket: int | None = None) -> "KmerTable":
         """``mini`` (k <= 21: packed 8-byte slots) or ``miniw`` (22 <= k <= 31: keys + counts planes, as ``wide``)"""
         top = cls.mini_max_log2_bucket(k)
-        lb = min(top, log2_slots) if log2_bucket is None else log2_bucket
+        lb = cls.mini_default_log2_bucket(k, log2_slots) if log2_bucket is None else log2_bucket
         want = os.environ.get("PG_MINI_LOG2_BUCKET")            # tuning / comparison: bucket size of tables whose caller named none
-        if log2_bucket is None and want and cls.mini_applies(k, log2_slots, min(int(want), lb)):
-            lb = min(int(want), lb)
+        if log2_bucket is None and want and cls.mini_applies(k, log2_slots, min(int(want), top, log2_slots)):
+            lb = min(int(want), top, log2_slots)
         if not cls.mini_applies(k, log2_slots, lb):
             raise ValueError(f"mini tables need {_lib.MINI_MIN_K} <= k <= {_lib.WIDE_MAX_K} and at most 2^{_lib.MINI_MAX_LOG2_BUCKETS} buckets "
                              f"of at most 2^{top} slots (k {k}, 2^{log2_slots} slots, buckets of 2^{lb})")
@@ -1205,8 +1215,9 @@ def prewarm_workspaces(device, n_pairs: int, k: int, vsize: int, read_len: int =
     w = min(k - m + 1, 9)
     records = int(n_words * (32.0 / ((w + 1) / 2.0) + 1.0) * 0.9)     # (k = 21: 6.7 per word; measured 6.45)
     kind = _lib.TABLE_MINI if k <= _lib.HASH_MAX_K else _lib.TABLE_MINI_WIDE
-    lb = _lib.BUCKET_MAX_LOG2_SLOTS if k <= _lib.HASH_MAX_K else _lib.MINI_WIDE_MAX_LOG2_BUCKET_SLOTS
-    desc = _lib.pg_table(kind, k, lb + 15, lb, None)
+    log2 = (_lib.BUCKET_MAX_LOG2_SLOTS if k <= _lib.HASH_MAX_K else _lib.MINI_WIDE_MAX_LOG2_BUCKET_SLOTS) + 15
+    lb = KmerTable.mini_default_log2_bucket(k, log2)
+    desc = _lib.pg_table(kind, k, log2, lb, None)
     n_rows = max(1, n_pairs // 100)
     sizes = []
     try:
