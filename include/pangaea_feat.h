@@ -223,6 +223,8 @@ enum { PG_TABLE_DENSE = 1, PG_TABLE_HASH = 2, PG_TABLE_WIDE = 3, PG_TABLE_MINI =
 #define PG_MINI_MIN_K 13
 #define PG_MINI_MAX_LOG2_BUCKETS 16
 #define PG_MINI_MAX_ROWS ((1 << 20) - 2)
+/* rows per rank of the masked count half (pg_mini_count_half_masked): a row-only record's flag rides on top of its row */
+#define PG_MINI_MASKED_MAX_ROWS ((1 << 19) - 2)
 #define PG_MINI_WIDE_MAX_LOG2_BUCKET_SLOTS 13
 /* the bucket size of packed mini tables (k <= 21) whose caller names none, once they have 2^(PG_MINI_MAX_LOG2_BUCKETS +
  * PG_MINI_LARGE_LOG2_BUCKET_SLOTS) slots or more: buckets of 2^13 slots (64 KiB: two counting workgroups per CU) instead of the
@@ -527,6 +529,33 @@ int pg_mini_merge_form_applies(const pg_table *t, int64_t n_rows, int vsize);
 /* byte offset of the second meta plane ("meta B": the bucket-ordered records' meta words that the pieces keep) inside a record
  * workspace of rec_ws_bytes bytes: [bases A | bases B | meta A | meta B] of the largest capacity that fits, a multiple of 256 */
 int64_t pg_mini_records_meta_offset(int64_t rec_ws_bytes, const pg_table *t);
+
+/* ---- the super-k-mer form on N > 1 ranks for MASKED input: soft-masked reads counted with lower-case bases (jellyfish count -C,
+ * feature.py:94) and paired reads whose bases below the quality threshold jellyfish reads as N (--min-qual-char=?, feature.py:76-83),
+ * while the reference's own row counters take neither rule (count_kmer.cpp:55-108).  Two planes then decide about a k-mer:
+ *   T  its bases are valid under `table_valid`: it counts +1 in the multiplicity table;
+ *   R  its bases are valid under rows->strict_valid (NULL: `valid`): it belongs to the row it lies in and its bin is looked up.
+ * `valid` is the plane U = table_valid | strict plane.  A k-mer is kept if T holds, or R inside a row; records are also cut where T
+ * changes.  A record of R-and-not-T k-mers takes local slots as any record but adds 0 to their counts, so the count half's entries
+ * may carry count 0; the owner merge of this form inserts every entry with count > 0, then LOOKS UP the count-0 ones: a key that no
+ * rank counted has no bin (count_kmer.cpp:87 skips a k-mer missing from the dump).  The merged slices hold counted k-mers only.
+ * The calls and workspaces are those of the plain form (pg_mini_plan / pg_mini_count_half / pg_mini_merge_bins, pieces included)
+ * with the _masked entries below in their places; table_valid = NULL is the plain form.  The masked count half needs the merged
+ * lookups (pg_mini_merge_form_applies) and at most PG_MINI_MASKED_MAX_ROWS rows, else PG_EINVAL.  It clears the row-only flag in the
+ * meta plane it leaves (meta B), which the lookup half and the kept meta words of pieces read as usual.  The owner merge must be the
+ * masked one on EVERY rank as soon as any rank's count half is: pg_mini_merge_bins_masked also takes plain parts. */
+int pg_mini_plan_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
+                        const pg_table *t, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *stream);
+int pg_mini_count_half_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
+                              const pg_table *local, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                              int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
+                              void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream);
+int pg_mini_count_half_piece_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
+                                    const pg_table *local, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                    int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
+                                    int64_t *fill, int first, int last, uint32_t *status, void *stream);
+int pg_mini_merge_bins_masked(const uint64_t *recv, int64_t part_stride, const int64_t *seg, int n_parts, const pg_table *t,
+                              int64_t bucket_begin, int64_t bucket_end, int window, int vsize, uint16_t *bins_out, uint32_t *status, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
  * Row normalisation of a count matrix (a9: Data.__init__, src/data.py:16-21 -- sklearn normalize(norm="l1") in float64, the

@@ -34,6 +34,7 @@ WORD_ALIGN = 256
 BUCKET_MAX_LOG2_SLOTS, BUCKET_MAX_LOG2_BUCKETS = 14, 17
 ABI_VERSION = 9
 MINI_MIN_K, MINI_MAX_LOG2_BUCKETS, MINI_MAX_ROWS, MINI_WIDE_MAX_LOG2_BUCKET_SLOTS = 13, 16, (1 << 20) - 2, 13
+MINI_MASKED_MAX_ROWS = (1 << 19) - 2    # PG_MINI_MASKED_MAX_ROWS: rows per rank of the masked count half
 MINI_LARGE_LOG2_BUCKET_SLOTS = 13   # PG_MINI_LARGE_LOG2_BUCKET_SLOTS: the default bucket of packed mini tables of >= 2^29 slots
 SHUFFLE_MAX_VSIZE = 512
 DEFERRED_MAX_GROUP_LOG2 = 3
@@ -154,6 +155,10 @@ def load() -> C.CDLL:
         "pg_mini_merge_bins": (i32, [vp, i64, vp, i32, tp, i64, i64, i32, i32, vp, vp, vp]),
         "pg_mini_lookup_half": (i32, [tp, rp, vp, i64, vp, i64, i64, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp]),
         "pg_mini_count_half_piece": (i32, [vp, vp, i64, i64, tp, rp, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp]),
+        "pg_mini_plan_masked": (i32, [vp, vp, vp, i64, i64, tp, rp, vp, i64, vp]),
+        "pg_mini_count_half_masked": (i32, [vp, vp, vp, i64, i64, tp, rp, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, i64, vp, vp, vp]),
+        "pg_mini_count_half_piece_masked": (i32, [vp, vp, vp, i64, i64, tp, rp, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, i32, i32, vp, vp]),
+        "pg_mini_merge_bins_masked": (i32, [vp, i64, vp, i32, tp, i64, i64, i32, i32, vp, vp, vp]),
         "pg_mini_lookup_half_piece": (i32, [tp, rp, vp, i64, i64, vp, i64, i32, vp, i64, vp, vp, i64, vp, vp, vp, vp]),
         "pg_mini_merge_form_applies": (i32, [tp, i64, i32]),
         "pg_mini_records_meta_offset": (i64, [i64, tp]),
@@ -188,6 +193,7 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_kmer_count_bucketed", "pg_kmer_merge", "pg_kmer_merge_bucketed", "pg_kmer_rebuild_bucketed", "pg_kmer_rebuild_bucketed_range", "pg_table_bucket_fill", "pg_kmer_count_deferred", "pg_deferred_gather", "pg_deferred_gather_planes", "pg_kmer_rebuild_planes_range", "pg_table_bucket_fill_range", "pg_table_compact_planes_range", "pg_table_compact", "pg_kmer_merge_wide", "pg_abundance_workspace_bytes",
            "pg_abundance_from_records", "pg_abundance_from_emitted", "pg_kmer_count_bucketed_emit",
            "pg_mini_plan_bytes", "pg_mini_plan", "pg_mini_records_bytes", "pg_mini_shuffle_bytes", "pg_mini_shuffle_bytes_merged", "pg_mini_merge_words", "pg_mini_count_piece", "pg_mini_lookup_begin", "pg_mini_lookup_piece", "pg_mini_count", "pg_mini_half_bytes", "pg_mini_count_half", "pg_mini_gather_entries", "pg_mini_merge_bins", "pg_mini_lookup_half", "pg_mini_count_half_piece", "pg_mini_lookup_half_piece", "pg_mini_merge_form_applies", "pg_mini_records_meta_offset", "pg_mini_wait_first_pass", "pg_mini_abundance_from_emitted",
+           "pg_mini_plan_masked", "pg_mini_count_half_masked", "pg_mini_count_half_piece_masked", "pg_mini_merge_bins_masked",
            "pg_features", "pg_normalize_rows", "pg_write_csv_gz", "pg_extract_reads"]
 
 

@@ -36,6 +36,11 @@ constexpr int ROUNDS_PER_CHUNK = MINI_CHUNK_WORDS / ROUND_WORDS;
 constexpr int STAGE_CAP = 8 * S1_BLOCK;                // records of a (sub-)round staged in LDS: 8 positions x 512 lanes always fit
 constexpr int META_D2_BITS = 8, META_LEN_BITS = 4, META_ROW_SHIFT = META_D2_BITS + META_LEN_BITS;
 constexpr uint32_t MINI_ROW_NONE = (1u << (32 - META_ROW_SHIFT)) - 1u;
+// MASKED forms (pg_mini_plan_masked / pg_mini_count_half_masked): a record whose k-mers are valid for the rows but not for the table
+// (bases below the quality threshold) carries this bit on top of its row -- rows stay below PG_MINI_MASKED_MAX_ROWS + 1 there, so a
+// flagged row is never MINI_ROW_NONE -- and the count half adds nothing for it (the bit is cleared in the meta plane it leaves)
+constexpr uint32_t MINI_ROW_NOTAB = 1u << (31 - META_ROW_SHIFT);
+static_assert(PG_MINI_MASKED_MAX_ROWS < (int)MINI_ROW_NOTAB - 1, "a flagged row is never MINI_ROW_NONE");
 constexpr int MINI_MAX_LEN = 1 << META_LEN_BITS;       // k-mers per record
 constexpr int MINI_BITS1 = 8;                          // first-pass digits (regions); a table of 2^16 buckets: 2^8 regions x 2^8 buckets each
 constexpr int MINI_MAX_BITS1 = 8;
@@ -95,6 +100,13 @@ struct RowBits {
         }
     }
     __device__ __forceinline__ uint32_t cuts() const { return starts | ends; }
+    // bit p: character p lies inside a row (at(p) != MINI_ROW_NONE) -- a prefix XOR of the positions where that changes
+    __device__ __forceinline__ uint32_t inside() const
+    {
+        uint32_t x = starts ^ ends;                             // (a row that ends where the next one starts changes nothing)
+        x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8; x ^= x << 16;
+        return inside0 ? ~x : x;
+    }
     // row of character p, MINI_ROW_NONE outside every row
     __device__ __forceinline__ uint32_t at(int p) const
     {
@@ -212,18 +224,32 @@ __device__ __forceinline__ LaneWord load_lane_word(const uint64_t *__restrict__ 
     return lw;
 }
 
+// MASKED (the segmented plane `valid` is U = table plane | strict plane): a lane's k-mer ends of U split by the two rules.  T: valid
+// under the table plane (counts in the table); R: valid under the strict plane (ok_row, belongs to the row it lies in).  A k-mer is
+// kept if T holds, or if R holds inside a row (a row-only k-mer is looked up, not counted); one that mixes a base only the table
+// takes with a base only the rows take is neither.  Records are also cut where T changes, so a record is all T or all not-T.
+// Returns the lane's T ends; lw.ok becomes the kept ends, cuts gains the T changes.
+__device__ __forceinline__ uint32_t mask_lane_word(LaneWord &lw, const RowBits &rb, uint32_t &cuts, const uint32_t *__restrict__ tabv, int64_t w, int k)
+{
+    const uint32_t tv = tabv[w], tp = w > 0 ? tabv[w - 1] : 0u;
+    const uint32_t ok_tab = lw.ok & (uint32_t)(runs_of(((uint64_t)tv << 32) | tp, k) >> 32);
+    lw.ok = ok_tab | (lw.ok_row & rb.inside());
+    cuts |= ok_tab ^ (ok_tab << 1);
+    return ok_tab;
+}
+
 // ---- plan: per chunk, records per first-pass region (chunk_hist[d * n_chunks + slot(chunk)]).  Nothing else: the per-bucket
 // counts are taken from the records themselves once the first pass has written them (mini_bucket_hist_kernel).  With 2 KB of
 // LDS, 256 threads and ~48 registers this kernel fits beside the workgroups of the other kernels on a CU -- beside the count
 // kernel, which fills LDS but leaves half of the VALU issue slots and a third of the registers idle: KmerTable.prefetch_plan
 // runs the next batch's plan on a side stream UNDER this batch's second scatter pass and count instead of in front of them
-template <int W, bool DELAY, int M>
+template <int W, bool DELAY, int M, bool MASKED = false>
 __global__ __launch_bounds__(BLOCK) void mini_plan_kernel(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid,
                                                           int64_t word_begin, int64_t word_end, int k, int woff, int bits, int bits2, int cap,
                                                           const int64_t *__restrict__ row_start, const int64_t *__restrict__ row_end, int64_t n_rows,
                                                           const uint32_t *__restrict__ strict, const int32_t *__restrict__ round_row,
                                                           unsigned long long *__restrict__ chunk_hist, int64_t n_chunks, int64_t chunk_stride,
-                                                          unsigned long long *__restrict__ class_totals)
+                                                          unsigned long long *__restrict__ class_totals, const uint32_t *__restrict__ tabv)
 {
     __shared__ uint32_t coarse[1 << MINI_MAX_BITS1];
     __shared__ uint32_t n_long_here;                             // records of more than SHORT_MAX k-mers in this chunk
@@ -237,17 +263,19 @@ __global__ __launch_bounds__(BLOCK) void mini_plan_kernel(const uint64_t *__rest
             const int64_t wi = chunk * MINI_CHUNK_WORDS + i;        // word index inside the range
             const int64_t w = word_begin + wi;
             if (w >= word_end) continue;
-            const LaneWord lw = load_lane_word(codes, valid, strict, w, k);
+            LaneWord lw = load_lane_word(codes, valid, strict, w, k);
             if (lw.ok == 0) continue;
             RowBits rb;
             rb.init(row_start, row_end, n_rows, row_start ? round_row[wi / ROUND_WORDS] : 0, w << 5);
+            uint32_t cuts = rb.cuts();
+            if constexpr (MASKED) mask_lane_word(lw, rb, cuts, tabv, w, k);
             uint32_t eq = 0, prev = 0;
             mini_minimizers<W, DELAY, M>(lw.x, woff, [&](int p, uint32_t mv) {
                 eq |= mv == prev ? 1u << p : 0u;
                 prev = mv;
                 col[p * BLOCK + threadIdx.x] = (uint16_t)mini_bucket(mv, bits);
             });
-            const uint32_t has = mini_record_ends(lw.ok, lw.ok_row, rb.cuts(), eq, cap);
+            const uint32_t has = mini_record_ends(lw.ok, lw.ok_row, cuts, eq, cap);
             // (the column is the lane's own: no barrier between its writes and these reads)
             for (uint32_t m = has; m; m &= m - 1u)
                 atomicAdd(&coarse[(uint32_t)col[(uint32_t)__builtin_ctz(m) * BLOCK + threadIdx.x] >> bits2], 1u);
@@ -401,8 +429,12 @@ template <int N1> struct Scatter1Lds {                              // N1 region
 };
 
 static_assert(2 * sizeof(Scatter1Lds<256>) <= 160 * 1024, "two first-pass workgroups share a CU's LDS");
+template <int N1> struct Scatter1LdsMasked : Scatter1Lds<N1> {
+    uint32_t ok_tab[S1_BLOCK];                                      // MASKED: k-mer ends that count in the table (the rest are row-only)
+};
+static_assert(2 * sizeof(Scatter1LdsMasked<256>) <= 160 * 1024, "two first-pass workgroups share a CU's LDS");
 
-template <int W, bool DELAY, int M, int N1>
+template <int W, bool DELAY, int M, int N1, bool MASKED = false>
 __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid,
                                                                  int64_t word_begin, int64_t word_end, int k, int woff, int bits, int bits2, int cap,
                                                                  const int64_t *__restrict__ row_start, const int64_t *__restrict__ row_end, int64_t n_rows,
@@ -410,7 +442,7 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
                                                                  uint64_t *__restrict__ out_bases, uint32_t *__restrict__ out_meta,
                                                                  const unsigned long long *__restrict__ chunk_off, int64_t n_chunks, int64_t chunk_stride,
                                                                  const unsigned long long *__restrict__ header, const unsigned long long *__restrict__ region_off,
-                                                                 unsigned long long rec_cap, uint32_t *status)
+                                                                 unsigned long long rec_cap, uint32_t *status, const uint32_t *__restrict__ tabv)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     static_assert(N1 <= S1_BLOCK, "one lane per region");
@@ -418,7 +450,8 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
         if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(status, PG_STATUS_PLAN_MISMATCH);
         return;
     }
-    Scatter1Lds<N1> &L = *reinterpret_cast<Scatter1Lds<N1> *>(lds_raw);
+    using Lds = std::conditional_t<MASKED, Scatter1LdsMasked<N1>, Scatter1Lds<N1>>;
+    Lds &L = *reinterpret_cast<Lds *>(lds_raw);
     const int n_dig = 1 << (bits - bits2);
     const uint32_t d2mask = (1u << bits2) - 1u;
     const int64_t chunk = blockIdx.x;
@@ -439,15 +472,18 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
         RowBits rb;
         rb.starts = rb.ends = rb.r0 = 0; rb.inside0 = false;
         uint16_t *const mycol = L.col + threadIdx.x;
+        uint32_t ok_tab = 0;
         if (lw.ok) {
             rb.init(row_start, row_end, n_rows, row_start ? round_row[round] : 0, w << 5);
+            uint32_t cuts = rb.cuts();
+            if constexpr (MASKED) ok_tab = mask_lane_word(lw, rb, cuts, tabv, w, k);
             uint32_t eq = 0, prev = 0;
             mini_minimizers<W, DELAY, M>(lw.x, woff, [&](int p, uint32_t mv) {
                 eq |= mv == prev ? 1u << p : 0u;
                 prev = mv;
                 mycol[p * S1_BLOCK] = (uint16_t)mini_bucket(mv, bits);
             });
-            has = mini_record_ends(lw.ok, lw.ok_row, rb.cuts(), eq, cap);
+            has = mini_record_ends(lw.ok, lw.ok_row, cuts, eq, cap);
             for (uint32_t m = has; m; m &= m - 1u)
                 __hip_atomic_fetch_add(&L.cnt[(uint32_t)mycol[(uint32_t)__builtin_ctz(m) * S1_BLOCK] >> bits2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -458,6 +494,7 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
         L.pw[threadIdx.x] = lw.x.pw;
         L.nonk[threadIdx.x] = has | ~lw.ok;
         L.ok_row[threadIdx.x] = lw.ok_row;
+        if constexpr (MASKED) L.ok_tab[threadIdx.x] = ok_tab;
         L.starts[threadIdx.x] = rb.starts;
         L.ends[threadIdx.x] = rb.ends;
         L.r0[threadIdx.x] = rb.r0 | (rb.inside0 ? 0x80000000u : 0u);
@@ -513,7 +550,7 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
                     rf[u] = L.ref[i < tot ? i : 0u];                 // (tot > 0 here: ref[0] is a record)
                 }
                 uint64_t cwv[2], pwv[2];
-                uint32_t nonk[2], okr[2], st[2], en[2], r0v[2];
+                uint32_t nonk[2], okr[2], st[2], en[2], r0v[2], okt[2];
                 unsigned long long gb[2];
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
@@ -521,6 +558,7 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
                     cwv[u] = L.cw[ln]; pwv[u] = L.pw[ln];
                     nonk[u] = L.nonk[ln]; okr[u] = L.ok_row[ln];
                     st[u] = L.starts[ln]; en[u] = L.ends[ln]; r0v[u] = L.r0[ln];
+                    if constexpr (MASKED) okt[u] = L.ok_tab[ln]; else okt[u] = 0u;
                     const uint32_t d = (rf[u] & 0xffffu) >> bits2;
                     if constexpr (N1 <= 256) gb[u] = L.gbase[d];
                     else gb[u] = L.cur[d] - L.start[d + 1];
@@ -538,6 +576,8 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
                         const int in0 = (int)(r0v[u] >> 31);
                         if (in0 + sc - ec > 0) row = (r0v[u] & 0x7fffffffu) + (uint32_t)sc - (in0 ? 0u : 1u);
                     }
+                    // (a row-only record lies inside a row by construction: mask_lane_word)
+                    if (MASKED && !((okt[u] >> e) & 1u)) row |= MINI_ROW_NOTAB;
                     // the 32 characters ending at position e of the word
                     const uint64_t rec = e == 31u ? cwv[u] : (cwv[u] << (2u * (31u - e))) | (pwv[u] >> (2u * (e + 1u)));
                     const unsigned long long g = gb[u] + i;
@@ -1276,8 +1316,12 @@ struct HalfArgs {
     long long *fill;                                             // [buckets]
     uint32_t *ring_cnt;                                          // [buckets]
     int accum;                                                   // 0: N-rank count half; 1, 2: a piece; 3, 4: the last piece of a count half (see above)
+    uint32_t *meta_w;                                            // MASKED: the meta plane the kernel reads, written back without MINI_ROW_NOTAB
 };
-template <int CAP, bool SLOTS, bool WIDE, int BLK, int DIG, bool MERGE = false, bool HALF = false>
+// MASKED (pg_mini_count_half_masked; HALF and MERGE only): records flagged MINI_ROW_NOTAB take their slots as every record does
+// but add 0 to the counts.  So that such a slot -- an all-A k-mer is code 0 -- never reads as empty, the count field of this form is
+// biased by one (a claimed slot holds count + 1); the epilogues take the bias off, the entries then may have count 0.
+template <int CAP, bool SLOTS, bool WIDE, int BLK, int DIG, bool MERGE = false, bool HALF = false, bool MASKED = false>
 __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__restrict__ bases, const uint32_t *__restrict__ meta,
                                                                const unsigned long long *__restrict__ off,
                                                                const unsigned long long *__restrict__ n_short,
@@ -1289,6 +1333,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
 {
     static_assert(!MERGE || SLOTS, "merged words are a form of the slot lookups");
     static_assert(!HALF || (SLOTS && !WIDE), "the count half is a form of the slot lookups on packed slots");
+    static_assert(!MASKED || (HALF && MERGE), "the masked form is a count half with the merged lookups");
 #ifdef PG_MINI_GAPS                                              // (variant build for tools/wg_gaps.py: when a workgroup began and ended, and where)
     const unsigned long long gap_t0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1435,8 +1480,10 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
         } else {
             const uint64_t code = c_ & RING_CODE;
             const uint32_t s0 = (uint32_t)(c_ >> RING_SLOT_SHIFT) & smask, s1 = (s0 + 1u) & smask;
-            const uint32_t turns = (uint32_t)(c_ >> RING_TURN_SHIFT);
-            const unsigned long long fresh = (unsigned long long)((code << HASH_CBITS) | 1ull);
+            // (MASKED: bit 63 = a row-only k-mer, the turns keep 7 bits)
+            const uint32_t turns = MASKED ? (uint32_t)(c_ >> RING_TURN_SHIFT) & 0x7fu : (uint32_t)(c_ >> RING_TURN_SHIFT);
+            const bool notab = MASKED && (c_ >> 63) != 0ull;
+            const unsigned long long fresh = (unsigned long long)((code << HASH_CBITS) | (MASKED && !notab ? 2ull : 1ull));
             const unsigned long long cur0 = tab[s0], cur1 = tab[s1];
             bool todo = act;
             sl = act ? 0xffffffffu : 0u;
@@ -1447,20 +1494,21 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
                 const bool claimed = todo && cur == 0;
                 const bool match = todo && cur != 0 && (cur >> HASH_CBITS) == code;
                 // stop growing at SAT; the overshoot is bounded by the lanes in flight and clamped when the slice is packed
-                if (match && (uint32_t)(cur & HASH_CMASK) < HASH_SAT) atomicAdd(reinterpret_cast<uint32_t *>(&tab[slot]), 1u);   // (the count is in the low dword)
+                const bool room = MASKED ? !notab && (uint32_t)(cur & HASH_CMASK) <= HASH_SAT : (uint32_t)(cur & HASH_CMASK) < HASH_SAT;
+                if (match && room) atomicAdd(reinterpret_cast<uint32_t *>(&tab[slot]), 1u);   // (the count is in the low dword)
                 if (claimed || match) { sl = slot; todo = false; }
             };
             visit(s0, cur0);
             visit(s1, cur1);
             // (a bucket with fewer slots than a lane may visit: it has seen them all)
-            const bool give_up = todo && (turns == 255u || 2u * (turns + 1u) >= limit);
+            const bool give_up = todo && (turns == (MASKED ? 127u : 255u) || 2u * (turns + 1u) >= limit);
             const bool again = todo && !give_up;
             settled = act && !again;
             const unsigned long long am = __ballot(again);
             if (am) {                                            // (uniform; the round's own 64 places are free: they were read above)
                 if (again) {
                     const uint32_t to = (tail + lanes_below(am)) & (RING - 1);
-                    ring[to] = code | ((uint64_t)((s0 + 2u) & smask) << RING_SLOT_SHIFT) | ((uint64_t)(turns + 1u) << RING_TURN_SHIFT);
+                    ring[to] = code | ((uint64_t)((s0 + 2u) & smask) << RING_SLOT_SHIFT) | ((uint64_t)(turns + 1u) << RING_TURN_SHIFT) | (notab ? 1ull << 63 : 0ull);
                     if (emit_slots) ring_row[to] = rw;
                 }
                 tail += (uint32_t)__popcll(am);
@@ -1491,7 +1539,15 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
             PG_WLAP(0);                                          // (loop top: the record has arrived, last batch's stores are out)
             const bool live = i0 + lane < rb;
             const int n = live ? (int)((m >> META_D2_BITS) & (MINI_MAX_LEN - 1)) + 1 : 0;
-            const uint32_t row = m >> META_ROW_SHIFT;
+            uint32_t row = m >> META_ROW_SHIFT;
+            bool notab = false;                                  // (MASKED) a row-only record: its k-mers add nothing
+            if constexpr (MASKED) {
+                notab = row != MINI_ROW_NONE && (row & MINI_ROW_NOTAB) != 0u;
+                if (notab) {
+                    row &= ~MINI_ROW_NOTAB;
+                    gstore(hv.meta_w, (uint64_t)(i0 + lane), (uint64_t)rec_cap, m & ~(MINI_ROW_NOTAB << META_ROW_SHIFT), status);
+                }
+            }
             const bool in_row = live && row != MINI_ROW_NONE;
             // (MERGE) the lane's first halfword in the bucket's range: k-mer j of its record has place0 + 64 j
             const uint32_t place0 = (CX < CAP ? 0u : long_base) + (uint32_t)((i0 - ra) >> 6) * (64u * CX) + lane;
@@ -1528,6 +1584,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
             // (ballots of single comparisons, combined as scalars: the ballot of a compound predicate is compiled as
             // v_cndmask + v_cmp on top of the scalar logic)
             const unsigned long long in_row_m = __builtin_amdgcn_ballot_w64(row != MINI_ROW_NONE);
+            const unsigned long long notab_m = MASKED ? __builtin_amdgcn_ballot_w64(notab) : 0ull;
             PG_WLAP(1);                                          // (codes, hashes, first probes back)
             unsigned long long pm[CX], qm[CX];                   // lanes whose j-th k-mer was settled by the first probe inside a row / is still pending
 #pragma unroll
@@ -1540,7 +1597,9 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
                 } else {
                     hit = act & __builtin_amdgcn_ballot_w64(cur[j] != 0) & __builtin_amdgcn_ballot_w64((cur[j] >> HASH_CBITS) == code[j]);
                     // (the count sits in the low 22 bits of the slot's low dword and stops far below 2^22: a 32-bit LDS add is enough)
-                    const unsigned long long room = __builtin_amdgcn_ballot_w64(((uint32_t)cur[j] & HASH_SAT) == 0);
+                    // (MASKED: the field holds count + 1 of an occupied slot; a row-only k-mer adds nothing)
+                    const unsigned long long room = MASKED ? __builtin_amdgcn_ballot_w64((((uint32_t)cur[j] - 1u) & HASH_SAT) == 0) & ~notab_m
+                                                           : __builtin_amdgcn_ballot_w64(((uint32_t)cur[j] & HASH_SAT) == 0);
                     __hip_atomic_fetch_add(reinterpret_cast<uint32_t *>(&tab[sl[j]]), __builtin_amdgcn_inverse_ballot_w64(hit & room) ? 1u : 0u,
                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
@@ -1565,7 +1624,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
                         // (a slot that is not empty and not a hit holds another key, and nothing ever leaves a slot: the search
                         // starts behind it)
                         if constexpr (WIDE) ring[at] = code[j] | (cur[j] != 0ull ? 1ull << 63 : 0ull);
-                        else ring[at] = code[j] | ((uint64_t)((sl[j] + (cur[j] != 0ull ? 1u : 0u)) & smask) << RING_SLOT_SHIFT);
+                        else ring[at] = code[j] | ((uint64_t)((sl[j] + (cur[j] != 0ull ? 1u : 0u)) & smask) << RING_SLOT_SHIFT) | (notab ? 1ull << 63 : 0ull);
                         // (MERGE: the general insert writes the slot to the k-mer's own place: the ring carries that place)
                         if (emit_slots) ring_row[at] = MERGE ? ring_place0 + 64u * j : row;
                     }
@@ -1633,7 +1692,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
         for (uint32_t i = threadIdx.x; i < n_slots; i += BLK) {
             const unsigned long long v = tab[i];
             uint32_t c = (uint32_t)(v & HASH_CMASK);
-            if (c > HASH_SAT) c = HASH_SAT;
+            if (c > HASH_SAT + (MASKED ? 1u : 0u)) c = HASH_SAT + (MASKED ? 1u : 0u);      // (MASKED: the slices keep the bias)
             gstore(t.slots, slice0 + i, 1ull << t.log2_slots, v ? (v & ~(unsigned long long)HASH_CMASK) | c : 0ull, status);
         }
         if (threadIdx.x == 0) wbeg[blockIdx.x] = wbase;
@@ -1653,13 +1712,14 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
         for (int q = 0; q < 16; ++q) {
             const uint32_t i = q * BLK + threadIdx.x;
             unsigned long long x = i < n_slots ? tab[i] : 0ull;
+            const bool occupied = x != 0ull;
             if (x) {                                             // (the count stops at SAT; the overshoot of concurrent adds is clamped here)
-                uint32_t c = (uint32_t)(x & HASH_CMASK);
+                uint32_t c = (uint32_t)(x & HASH_CMASK) - (MASKED ? 1u : 0u);     // (MASKED: the bias off -- a row-only k-mer has count 0)
                 if (c > HASH_SAT) c = HASH_SAT;
                 x = (x & ~(unsigned long long)HASH_CMASK) | c;
             }
             v[q] = x;
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(x != 0ull);
+            const unsigned long long m = __builtin_amdgcn_ballot_w64(occupied);
             if (lane == 0 && q * BLK + wave * 64u < (n_slots >= 64u ? n_slots : 64u)) occ_l[(q * BLK + wave * 64u) >> 6] = m;
         }
         __syncthreads();
@@ -1685,7 +1745,7 @@ __global__ __launch_bounds__(BLK, 4) void mini_count_kernel(const uint64_t *__re
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const uint32_t i = q * BLK + threadIdx.x;
-            if (i < n_slots && v[q]) {
+            if (i < n_slots && (MASKED ? ((occ_l[i >> 6] >> (i & 63u)) & 1ull) != 0ull : v[q] != 0ull)) {    // (MASKED: an entry may be 0)
                 const unsigned long long m = occ_l[i >> 6];
                 gstore(hv.ent, ent0 + rank_l[i >> 6] + (uint32_t)__popcll(m & ((1ull << (i & 63u)) - 1ull)), ent_cap, v[q], status);
             }
@@ -1928,7 +1988,11 @@ __global__ __launch_bounds__(BLOCK) void mini_gather_entries_kernel(const unsign
 
 // one workgroup per OWNED bucket: part p's entries of owned bucket i lie at recv[p * part_stride + seg[p * (n_owned + 1) + i] ..
 // seg[... + i + 1]) (slot format: canonical code << 22 | count, counts <= SAT); bins_out has the same layout in uint16:
-// bin + 1 of the entry's k-mer in the MERGED table, 0xffff when the bin lies beyond the vector
+// bin + 1 of the entry's k-mer in the MERGED table, 0xffff when the bin lies beyond the vector.
+// MASKED (pg_mini_merge_bins_masked): an entry of count 0 (a k-mer that only rows of its sender saw: pg_mini_count_half_masked) is
+// not inserted: once every counted entry is in, it is LOOKED UP -- its slot if some rank counted the k-mer, else no bin (0xffff).
+// The slices then hold counted k-mers only: no zero entries, no holes in probe chains (count_kmer.cpp:87 skips what the dump lacks).
+template <bool MASKED = false>
 __global__ __launch_bounds__(BIG_BLOCK) void mini_merge_bins_kernel(const unsigned long long *__restrict__ recv, long long part_stride,
                                                                     const long long *__restrict__ seg, int n_parts, int n_owned,
                                                                     MiniView t, long long bucket0, uint32_t window, uint32_t vsize,
@@ -1966,6 +2030,7 @@ __global__ __launch_bounds__(BIG_BLOCK) void mini_merge_bins_kernel(const unsign
                 if (e >= b) continue;
                 const uint64_t code = x[u] >> HASH_CBITS;
                 const uint32_t c = (uint32_t)(x[u] & HASH_CMASK);
+                if (MASKED && c == 0u) continue;                 // (looked up below)
                 uint32_t at = s[u];
                 unsigned long long cv = cur[u];
                 bool done = false;
@@ -1996,6 +2061,25 @@ __global__ __launch_bounds__(BIG_BLOCK) void mini_merge_bins_kernel(const unsign
     }
     if (full) atomicOr(status, PG_STATUS_TABLE_FULL);
     __syncthreads();
+    if constexpr (MASKED) {
+        // the count-0 entries: found or not, nothing is inserted (every lane again treats the entries it treated above)
+        for (int p = 0; p < n_parts; ++p) {
+            const long long a = seg[(long long)p * (n_owned + 1) + blockIdx.x], b = seg[(long long)p * (n_owned + 1) + blockIdx.x + 1];
+            for (long long e = a + threadIdx.x; e < b; e += BIG_BLOCK) {
+                const unsigned long long x = recv[(long long)p * part_stride + e];
+                if ((x & HASH_CMASK) != 0ull) continue;
+                const uint64_t code = x >> HASH_CBITS;
+                uint32_t at = mini_slot_hash<false>(code) & smask, found = 0xffffu;
+                for (uint32_t i = 0; i < limit; ++i) {
+                    const unsigned long long cv = tab[at];
+                    if (cv == 0ull) break;
+                    if ((cv >> HASH_CBITS) == code) { found = at; break; }
+                    at = (at + 1) & smask;
+                }
+                gstore(bins_out, (uint64_t)((long long)p * part_stride + e), out_cap, (uint16_t)found, status);
+            }
+        }
+    }
     const uint64_t slice0 = (uint64_t)(bucket0 + blockIdx.x) << t.log2_bucket;
     for (uint32_t i = threadIdx.x; i < n_slots; i += BIG_BLOCK) gstore(t.slots, slice0 + i, 1ull << t.log2_slots, tab[i], status);
     // slots -> bins (every lane reads back what it wrote itself: the same entries in the same order)
@@ -2406,8 +2490,9 @@ extern "C" int64_t pg_mini_shuffle_bytes_merged(int64_t n_words, int64_t n_rows,
         }                                                                                                                   \
     }
 
-extern "C" int pg_mini_plan(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *t,
-                            const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *stream)
+// tabv: the table plane of the masked form (pg_mini_plan_masked), NULL otherwise
+static int mini_plan_impl(const uint64_t *codes, const uint32_t *valid, const uint32_t *tabv, int64_t word_begin, int64_t word_end, const pg_table *t,
+                          const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *stream)
 {
     if (!codes || !valid || !plan_ws) return pg_fail(PG_EINVAL, "pg_mini_plan: null argument");
     if (word_begin < 0 || word_end < word_begin) return pg_fail(PG_EINVAL, "pg_mini_plan: bad word range");
@@ -2434,11 +2519,15 @@ extern "C" int pg_mini_plan(const uint64_t *codes, const uint32_t *valid, int64_
             hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)((p.n_rounds + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, rows->row_end, rows->n_rows,
                                word_begin, p.n_rounds, round_row);
         const int grid = (int)(p.n_chunks < 4096 ? p.n_chunks : 4096);
-        PG_MINI_DISPATCH_W(t->k,
-            hipLaunchKernelGGL((mini_plan_kernel<W, DELAY, M>), dim3(grid), dim3(BLOCK), 0, s, codes, valid, word_begin, word_end, t->k, woff, p.bits, p.bits2, mini_cap(t->k),
-                               with_rows ? rows->row_start : (const int64_t *)nullptr, with_rows ? rows->row_end : (const int64_t *)nullptr,
-                               with_rows ? rows->n_rows : (int64_t)0, with_rows ? rows->strict_valid : (const uint32_t *)nullptr,
-                               (const int32_t *)round_row, chunk_tab, p.n_chunks, p.chunk_stride, header + 2))
+#define PG_MINI_LAUNCH_PLAN(MASKED_)                                                                                        \
+        PG_MINI_DISPATCH_W(t->k,                                                                                            \
+            hipLaunchKernelGGL((mini_plan_kernel<W, DELAY, M, MASKED_>), dim3(grid), dim3(BLOCK), 0, s, codes, valid, word_begin, word_end, t->k, woff, p.bits, p.bits2, mini_cap(t->k), \
+                               with_rows ? rows->row_start : (const int64_t *)nullptr, with_rows ? rows->row_end : (const int64_t *)nullptr, \
+                               with_rows ? rows->n_rows : (int64_t)0, with_rows ? rows->strict_valid : (const uint32_t *)nullptr, \
+                               (const int32_t *)round_row, chunk_tab, p.n_chunks, p.chunk_stride, header + 2, tabv))
+        if (tabv) PG_MINI_LAUNCH_PLAN(true)
+        else PG_MINI_LAUNCH_PLAN(false)
+#undef PG_MINI_LAUNCH_PLAN
     }
     // records per region -> where the regions start -> exact offset of every (chunk, region) run; total -> header[0]
     hipLaunchKernelGGL(digit_totals_kernel, dim3((unsigned)n_regions), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)chunk_tab, p.n_chunks, region_tot);
@@ -2447,6 +2536,18 @@ extern "C" int pg_mini_plan(const uint64_t *codes, const uint32_t *valid, int64_
                        0, (unsigned long long *)nullptr);
     hipLaunchKernelGGL(mini_total_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)region_off, n_regions, header);
     return check_launch("pg_mini_plan");
+}
+
+extern "C" int pg_mini_plan(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *t,
+                            const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *stream)
+{
+    return mini_plan_impl(codes, valid, nullptr, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, stream);
+}
+
+extern "C" int pg_mini_plan_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
+                                   const pg_table *t, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *stream)
+{
+    return mini_plan_impl(codes, valid, table_valid, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, stream);
 }
 
 static thread_local hipEvent_t first_pass_event = nullptr;         // recorded by every pg_mini_count behind its first scatter pass
@@ -2466,7 +2567,7 @@ extern "C" int pg_mini_wait_first_pass(void *stream)
 static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *t,
                            const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
                            int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, uint32_t *status, void *stream, const HalfArgs *half,
-                           void *merge_ws = nullptr, int64_t merge_ws_words = 0)
+                           void *merge_ws = nullptr, int64_t merge_ws_words = 0, const uint32_t *tabv = nullptr)
 {
     if (!codes || !valid || !plan_ws || !rec_ws || !status) return pg_fail(PG_EINVAL, "pg_mini_count: null argument");
     if (word_begin < 0 || word_end < word_begin) return pg_fail(PG_EINVAL, "pg_mini_count: bad word range");
@@ -2522,16 +2623,17 @@ static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t
     const size_t table_lds = (size_t)(wide ? 12 : 8) << t->log2_bucket_slots;
     const size_t slice_lds = table_lds + (size_t)COUNT_WAVES * RING * 12;      // table + the wavefronts' rings (1024 threads)
     if (word_end > word_begin) {
-#define PG_MINI_LAUNCH_SCATTER(N1_)                                                                                          \
+#define PG_MINI_LAUNCH_SCATTER(N1_, MASKED_)                                                                                 \
         PG_MINI_DISPATCH_W(t->k,                                                                                            \
-            const size_t lds1 = sizeof(Scatter1Lds<N1_>);                                                                   \
-            if ((rc = raise_lds_limit((const void *)(mini_scatter_kernel<W, DELAY, M, N1_>), lds1, "pg_mini_count"))) return rc; \
-            hipLaunchKernelGGL((mini_scatter_kernel<W, DELAY, M, N1_>), dim3((unsigned)p.n_chunks), dim3(S1_BLOCK), lds1, s, codes, valid, word_begin, word_end, t->k, woff, p.bits, \
+            const size_t lds1 = MASKED_ ? sizeof(Scatter1LdsMasked<N1_>) : sizeof(Scatter1Lds<N1_>);                         \
+            if ((rc = raise_lds_limit((const void *)(mini_scatter_kernel<W, DELAY, M, N1_, MASKED_>), lds1, "pg_mini_count"))) return rc; \
+            hipLaunchKernelGGL((mini_scatter_kernel<W, DELAY, M, N1_, MASKED_>), dim3((unsigned)p.n_chunks), dim3(S1_BLOCK), lds1, s, codes, valid, word_begin, word_end, t->k, woff, p.bits, \
                                p.bits2, mini_cap(t->k), with_rows ? rows->row_start : (const int64_t *)nullptr, with_rows ? rows->row_end : (const int64_t *)nullptr, \
                                with_rows ? rows->n_rows : (int64_t)0, with_rows ? rows->strict_valid : (const uint32_t *)nullptr, \
                                (const int32_t *)round_row, bases_a, meta_a, (const unsigned long long *)chunk_tab, p.n_chunks, p.chunk_stride, \
-                               (const unsigned long long *)header, (const unsigned long long *)region_off, (unsigned long long)cap, status))
-        PG_MINI_LAUNCH_SCATTER(256)
+                               (const unsigned long long *)header, (const unsigned long long *)region_off, (unsigned long long)cap, status, tabv))
+        if (tabv) PG_MINI_LAUNCH_SCATTER(256, true)
+        else PG_MINI_LAUNCH_SCATTER(256, false)
 #undef PG_MINI_LAUNCH_SCATTER
     }
     // (for pg_mini_wait_first_pass: what is enqueued on another stream behind this event runs beside the second pass and the count)
@@ -2587,7 +2689,10 @@ static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t
         return pg_fail(PG_EINVAL, "pg_mini_count_half: needs packed slots (k <= %d), rows and fewer than 2^(32 - log2 bucket slots) of them", PG_HASH_MAX_K);
     if (half && !p.bits2) return pg_fail(PG_EINVAL, "pg_mini_count_half: needs more than 256 buckets");
     if (piece && !merge) return pg_fail(PG_EINVAL, "pg_mini_count_piece: needs the merged lookups (fewer than 2^20 rows, their slot buffer given)");
-    const HalfArgs hv = half ? *half : HalfArgs{nullptr, nullptr, nullptr, nullptr, 0};
+    if (tabv && !(half && merge && rows->n_rows <= PG_MINI_MASKED_MAX_ROWS))
+        return pg_fail(PG_EINVAL, "pg_mini_count_half_masked: needs the merged lookups (their slot buffer given) and at most %d rows", PG_MINI_MASKED_MAX_ROWS);
+    HalfArgs hv = half ? *half : HalfArgs{nullptr, nullptr, nullptr, nullptr, 0, nullptr};
+    hv.meta_w = tabv ? (p.bits2 ? meta_b : meta_a) : nullptr;    // (the plane the count kernel reads: the lookup half reads it again)
     size_t count_lds = slice_lds;
     // Buckets of at most 2^13 8-byte slots (64 KiB): 512-thread workgroups, TWO per CU -- one can be in its count loop (VALU, waits)
     // while the other is in its lookup phase (LDS throughput).  PG_COUNT_BLOCK=1024: the one-workgroup form for such tables too.
@@ -2608,10 +2713,11 @@ static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t
         if (count_lds < lookup_lds && !half) count_lds = lookup_lds;
     }
     unsigned long long *emit_end = window && !piece ? (unsigned long long *)((char *)shuffle_ws + sl.emit_off) : (unsigned long long *)nullptr;
-#define PG_MINI_LAUNCH_COUNT__(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, LDS_)                                         \
+#define PG_MINI_LAUNCH_COUNT__(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, LDS_) PG_MINI_LAUNCH_COUNT_M(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, false, LDS_)
+#define PG_MINI_LAUNCH_COUNT_M(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, MASKED_, LDS_)                               \
     do {                                                                                                                    \
-        if ((rc = raise_lds_limit((const void *)(mini_count_kernel<CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_>), LDS_, "pg_mini_count"))) return rc; \
-        hipLaunchKernelGGL((mini_count_kernel<CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_>), dim3(nb), dim3(BLK_), LDS_, s, \
+        if ((rc = raise_lds_limit((const void *)(mini_count_kernel<CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, MASKED_>), LDS_, "pg_mini_count"))) return rc; \
+        hipLaunchKernelGGL((mini_count_kernel<CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, MASKED_>), dim3(nb), dim3(BLK_), LDS_, s, \
                            (const uint64_t *)(p.bits2 ? bases_b : bases_a), (const uint32_t *)(p.bits2 ? meta_b : meta_a),  \
                            (const unsigned long long *)off, n_short, p.bits2 ? (const unsigned long long *)kwords : (const unsigned long long *)nullptr, \
                            mini_view(t), (uint32_t)window, (uint32_t)vsize,                                                 \
@@ -2630,7 +2736,9 @@ static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t
     } while (0)
 #define PG_MINI_LAUNCH_COUNT(CAP_)                                                                                          \
     do {                                                                                                                    \
-        if (half) { if (half_block) { if (merge) PG_MINI_LAUNCH_COUNT__(CAP_, true, false, 512, 1024, true, true, count_lds);  \
+        if (tabv) { if (half_block) PG_MINI_LAUNCH_COUNT_M(CAP_, true, false, 512, 1024, true, true, true, count_lds);       \
+                    else PG_MINI_LAUNCH_COUNT_M(CAP_, true, false, BIG_BLOCK, 1024, true, true, true, count_lds); }         \
+        else if (half) { if (half_block) { if (merge) PG_MINI_LAUNCH_COUNT__(CAP_, true, false, 512, 1024, true, true, count_lds);  \
                                       else PG_MINI_LAUNCH_COUNT__(CAP_, true, false, 512, 1024, false, true, count_lds); }   \
                     else { if (merge) PG_MINI_LAUNCH_COUNT__(CAP_, true, false, BIG_BLOCK, 1024, true, true, count_lds);     \
                            else PG_MINI_LAUNCH_COUNT__(CAP_, true, false, BIG_BLOCK, 1024, false, true, count_lds); } }      \
@@ -2649,6 +2757,7 @@ static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t
 #undef PG_MINI_LAUNCH_SLOTS_
 #undef PG_MINI_LAUNCH_COUNT_
 #undef PG_MINI_LAUNCH_COUNT__
+#undef PG_MINI_LAUNCH_COUNT_M
     return check_launch("pg_mini_count");
 }
 
@@ -2781,10 +2890,10 @@ extern "C" int64_t pg_mini_half_bytes(const pg_table *local)
     return (int64_t)mini_half_layout(local).total;
 }
 
-extern "C" int pg_mini_count_half(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
-                                  const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
-                                  int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
-                                  void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream)
+static int mini_count_half_impl(const uint64_t *codes, const uint32_t *valid, const uint32_t *tabv, int64_t word_begin, int64_t word_end, const pg_table *local,
+                                const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
+                                void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream)
 {
     int rc = check_mini(local, "pg_mini_count_half");
     if (rc) return rc;
@@ -2793,9 +2902,27 @@ extern "C" int pg_mini_count_half(const uint64_t *codes, const uint32_t *valid, 
     if ((int64_t)hl.total > half_ws_bytes || (reinterpret_cast<uintptr_t>(half_ws) & 255) != 0)
         return pg_fail(PG_EINVAL, "pg_mini_count_half: workspace of %lld bytes (256-byte aligned), %lld needed", (long long)half_ws_bytes, (long long)hl.total);
     char *hw = (char *)half_ws;
-    const HalfArgs hv{(unsigned long long *)(hw + hl.ent_off), (unsigned long long *)(hw + hl.occ_off), (long long *)fill, (uint32_t *)(hw + hl.ring_off), 0};
+    const HalfArgs hv{(unsigned long long *)(hw + hl.ent_off), (unsigned long long *)(hw + hl.occ_off), (long long *)fill, (uint32_t *)(hw + hl.ring_off), 0, nullptr};
     return mini_count_impl(codes, valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize, shuffle_ws,
-                           shuffle_ws_bytes, status, stream, &hv, merge_ws, merge_ws_words);
+                           shuffle_ws_bytes, status, stream, &hv, merge_ws, merge_ws_words, tabv);
+}
+
+extern "C" int pg_mini_count_half(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
+                                  const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                  int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
+                                  void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream)
+{
+    return mini_count_half_impl(codes, valid, nullptr, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, status, stream);
+}
+
+extern "C" int pg_mini_count_half_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
+                                         const pg_table *local, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                         int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
+                                         void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream)
+{
+    return mini_count_half_impl(codes, valid, table_valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, status, stream);
 }
 
 extern "C" int pg_mini_gather_entries(const pg_table *local, const void *half_ws, int64_t half_ws_bytes, const int64_t *fill,
@@ -2813,8 +2940,8 @@ extern "C" int pg_mini_gather_entries(const pg_table *local, const void *half_ws
     return check_launch("pg_mini_gather_entries");
 }
 
-extern "C" int pg_mini_merge_bins(const uint64_t *recv, int64_t part_stride, const int64_t *seg, int n_parts, const pg_table *t,
-                                  int64_t bucket_begin, int64_t bucket_end, int window, int vsize, uint16_t *bins_out, uint32_t *status, void *stream)
+static int mini_merge_bins_impl(bool masked, const uint64_t *recv, int64_t part_stride, const int64_t *seg, int n_parts, const pg_table *t,
+                                int64_t bucket_begin, int64_t bucket_end, int window, int vsize, uint16_t *bins_out, uint32_t *status, void *stream)
 {
     int rc = check_mini(t, "pg_mini_merge_bins");
     if (rc) return rc;
@@ -2824,11 +2951,29 @@ extern "C" int pg_mini_merge_bins(const uint64_t *recv, int64_t part_stride, con
         return pg_fail(PG_EINVAL, "pg_mini_merge_bins: bad arguments");
     if (bucket_end == bucket_begin) return PG_OK;
     const size_t lds = (size_t)8 << t->log2_bucket_slots;
-    if ((rc = raise_lds_limit((const void *)mini_merge_bins_kernel, lds, "pg_mini_merge_bins"))) return rc;
-    hipLaunchKernelGGL(mini_merge_bins_kernel, dim3((unsigned)(bucket_end - bucket_begin)), dim3(BIG_BLOCK), lds, (hipStream_t)stream,
-                       (const unsigned long long *)recv, (long long)part_stride, (const long long *)seg, n_parts, (int)(bucket_end - bucket_begin),
-                       mini_view(t), (long long)bucket_begin, (uint32_t)window, (uint32_t)vsize, bins_out, status);
+#define PG_MINI_LAUNCH_MERGE(MASKED_)                                                                                       \
+    do {                                                                                                                    \
+        if ((rc = raise_lds_limit((const void *)mini_merge_bins_kernel<MASKED_>, lds, "pg_mini_merge_bins"))) return rc;    \
+        hipLaunchKernelGGL(mini_merge_bins_kernel<MASKED_>, dim3((unsigned)(bucket_end - bucket_begin)), dim3(BIG_BLOCK), lds, (hipStream_t)stream, \
+                           (const unsigned long long *)recv, (long long)part_stride, (const long long *)seg, n_parts, (int)(bucket_end - bucket_begin), \
+                           mini_view(t), (long long)bucket_begin, (uint32_t)window, (uint32_t)vsize, bins_out, status);    \
+    } while (0)
+    if (masked) PG_MINI_LAUNCH_MERGE(true);
+    else PG_MINI_LAUNCH_MERGE(false);
+#undef PG_MINI_LAUNCH_MERGE
     return check_launch("pg_mini_merge_bins");
+}
+
+extern "C" int pg_mini_merge_bins(const uint64_t *recv, int64_t part_stride, const int64_t *seg, int n_parts, const pg_table *t,
+                                  int64_t bucket_begin, int64_t bucket_end, int window, int vsize, uint16_t *bins_out, uint32_t *status, void *stream)
+{
+    return mini_merge_bins_impl(false, recv, part_stride, seg, n_parts, t, bucket_begin, bucket_end, window, vsize, bins_out, status, stream);
+}
+
+extern "C" int pg_mini_merge_bins_masked(const uint64_t *recv, int64_t part_stride, const int64_t *seg, int n_parts, const pg_table *t,
+                                         int64_t bucket_begin, int64_t bucket_end, int window, int vsize, uint16_t *bins_out, uint32_t *status, void *stream)
+{
+    return mini_merge_bins_impl(true, recv, part_stride, seg, n_parts, t, bucket_begin, bucket_end, window, vsize, bins_out, status, stream);
 }
 
 extern "C" int pg_mini_lookup_half(const pg_table *local, const pg_rows *rows, const void *plan_ws, int64_t plan_ws_bytes, const void *rec_ws, int64_t rec_ws_bytes,
@@ -2922,10 +3067,10 @@ extern "C" int pg_mini_lookup_half(const pg_table *local, const pg_rows *rows, c
 
 // ---- the count half in pieces (N > 1 ranks; see HalfArgs): `local` has real slots here (2^log2_slots words), which the pieces
 // count into; the last piece leaves entries, occupancy and fill in half_ws as one pg_mini_count_half would
-extern "C" int pg_mini_count_half_piece(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
-                                        const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
-                                        int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
-                                        int64_t *fill, int first, int last, uint32_t *status, void *stream)
+static int mini_count_half_piece_impl(const uint64_t *codes, const uint32_t *valid, const uint32_t *tabv, int64_t word_begin, int64_t word_end,
+                                      const pg_table *local, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                      int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
+                                      int64_t *fill, int first, int last, uint32_t *status, void *stream)
 {
     int rc = check_mini(local, "pg_mini_count_half_piece");
     if (rc) return rc;
@@ -2937,9 +3082,27 @@ extern "C" int pg_mini_count_half_piece(const uint64_t *codes, const uint32_t *v
         return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: workspace of %lld bytes (256-byte aligned), %lld needed", (long long)half_ws_bytes, (long long)hl.total);
     char *hw = (char *)half_ws;
     const int accum = first ? (last ? 4 : 1) : (last ? 3 : 2);
-    const HalfArgs hv{(unsigned long long *)(hw + hl.ent_off), (unsigned long long *)(hw + hl.occ_off), (long long *)fill, (uint32_t *)(hw + hl.ring_off), accum};
+    const HalfArgs hv{(unsigned long long *)(hw + hl.ent_off), (unsigned long long *)(hw + hl.occ_off), (long long *)fill, (uint32_t *)(hw + hl.ring_off), accum, nullptr};
     return mini_count_impl(codes, valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize, nullptr, 0,
-                           status, stream, &hv, merge_ws, merge_ws_words);
+                           status, stream, &hv, merge_ws, merge_ws_words, tabv);
+}
+
+extern "C" int pg_mini_count_half_piece(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
+                                        const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                        int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
+                                        int64_t *fill, int first, int last, uint32_t *status, void *stream)
+{
+    return mini_count_half_piece_impl(codes, valid, nullptr, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                      merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, first, last, status, stream);
+}
+
+extern "C" int pg_mini_count_half_piece_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
+                                               const pg_table *local, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                                               int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
+                                               int64_t *fill, int first, int last, uint32_t *status, void *stream)
+{
+    return mini_count_half_piece_impl(codes, valid, table_valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                      merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, first, last, status, stream);
 }
 
 // the lookups of one piece of a count half in pieces, once the bins are back: plan_ws / meta / merge_ws of that piece (as for

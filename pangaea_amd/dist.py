@@ -347,10 +347,25 @@ def _exchange_planes(table: KmerTable, group, me: int, world: int, seg, cuts, at
 OWNER_MIN_WORLD = 4          # from this many ranks on, partial tables are reduced at bucket-range owners before they are replicated
 
 
+# bytes per RCCL all-to-all call: one call with a 1.39 GB buffer (the entries of a 10 M-pair share, one-rank group) delivered
+# only the first 695 MiB of it, synchronised or not, while calls of up to 0.99 GB arrived whole (profiles/r06a_a2a_check.txt)
+A2A_CHUNK_BYTES = 1 << 29
+
+
 def _all_to_all_flat(out: torch.Tensor, inp: torch.Tensor, group=None) -> None:
-    """all-to-all of equal byte splits (the r-th slice of ``inp`` goes to rank r, into slot ``me`` of its ``out``)"""
+    """all-to-all of equal byte splits (the r-th slice of ``inp`` goes to rank r, into slot ``me`` of its ``out``).  RCCL: in
+    calls of at most ``A2A_CHUNK_BYTES`` -- a larger buffer goes as column ranges of the rank slices, each a contiguous view"""
     if dist.get_backend(group) == "nccl":
-        dist.all_to_all_single(out, inp, group=group)
+        world = dist.get_world_size(group)
+        if inp.numel() * inp.element_size() <= A2A_CHUNK_BYTES:
+            dist.all_to_all_single(out, inp, group=group)
+            return
+        per = inp.numel() // world
+        step = max(1, A2A_CHUNK_BYTES // (world * inp.element_size()))
+        for c0 in range(0, per, step):
+            c1 = min(per, c0 + step)
+            dist.all_to_all([out[r * per + c0:r * per + c1] for r in range(world)], [inp[r * per + c0:r * per + c1] for r in range(world)],
+                            group=group)
         return
     host = torch.empty(out.numel(), dtype=out.dtype)
     dist.all_to_all_single(host, inp.cpu().contiguous(), group=group)
@@ -559,7 +574,10 @@ class MiniSharded:
     MIN_LOG2_BUCKETS = 9                 # (two scatter passes; the lookup half reads the per-bucket word totals of the second)
 
     def __init__(self, k: int, device, union_log2_slots: int, local_log2_bucket: int, window: int, vsize: int, group=None,
-                 union_log2_bucket: int | None = None):
+                 union_log2_bucket: int | None = None, lowercase_is_base: bool = False, masked: bool = False):
+        """``lowercase_is_base``: count lower-case bases in the table (soft-masked input), as ``count_kmers_sharded``.  ``masked``:
+        SOME rank's count half takes the masked form (``KmerTable.half_masked``), so every owner merges with
+        ``pg_mini_merge_bins_masked`` -- the same value on every rank."""
         from . import _lib
         lb_u = min(_lib.BUCKET_MAX_LOG2_SLOTS, union_log2_slots) if union_log2_bucket is None else union_log2_bucket
         bits = union_log2_slots - lb_u
@@ -568,6 +586,7 @@ class MiniSharded:
         if not 4 <= local_log2_bucket <= lb_u:
             raise ValueError("local buckets hold between 2^4 slots and the union's")
         self.group, self.window, self.vsize = group, int(window), int(vsize)
+        self.lowercase_is_base, self.masked = bool(lowercase_is_base), bool(masked)
         self.union = KmerTable.mini_with_slots(k, device, union_log2_slots, lb_u)
         # (the local table object carries geometry, plan and workspaces; its slots are never written: one word stands in)
         self.local = KmerTable(k, "mini", torch.zeros(1, dtype=torch.int64, device=device), bits + local_log2_bucket, local_log2_bucket)
@@ -600,6 +619,18 @@ class MiniSharded:
         lb = MiniSharded.max_local_log2_bucket(n_rows)
         bits = MiniSharded.MIN_LOG2_BUCKETS
         desc = _lib.pg_table(_lib.TABLE_MINI, int(k), bits + lb, lb, 1)      # (geometry only: the data pointer is never read)
+        return _lib.check(_lib.load().pg_mini_merge_form_applies(C.byref(desc), int(n_rows), int(vsize))) == 1
+
+    @staticmethod
+    def masked_rows_apply(k: int, n_rows: int, vsize: int) -> bool:
+        """may the MASKED count half take ``n_rows`` rows: it needs the merged lookups (``pg_mini_merge_form_applies`` on the local
+        bucket ``geometry`` gives these rows; PG_MINI_MERGE=0: never) and at most PG_MINI_MASKED_MAX_ROWS rows"""
+        from . import _lib
+        import ctypes as C
+        if not 0 < n_rows <= _lib.MINI_MASKED_MAX_ROWS or os.environ.get("PG_MINI_MERGE", "1") in ("", "0"):
+            return False
+        lb = MiniSharded.max_local_log2_bucket(n_rows)
+        desc = _lib.pg_table(_lib.TABLE_MINI, int(k), MiniSharded.MIN_LOG2_BUCKETS + lb, lb, 1)     # (geometry only)
         return _lib.check(_lib.load().pg_mini_merge_form_applies(C.byref(desc), int(n_rows), int(vsize))) == 1
 
     @staticmethod
@@ -654,7 +685,8 @@ class MiniSharded:
     def count_half(self, stream: ReadStream, plan) -> None:
         """plan -> first and second scatter pass -> the bucket workgroups' count half (this rank's reads only)"""
         self.local.reset(); self.union.reset()
-        self.local.count_half(stream, plan, (self.window, self.vsize), check=False, world=dist.get_world_size(self.group))
+        self.local.count_half(stream, plan, (self.window, self.vsize), check=False, world=dist.get_world_size(self.group),
+                              lowercase_is_base=self.lowercase_is_base)
 
     def exchange(self) -> None:
         """entries -> owners (all-to-all, 8 bytes per distinct k-mer of this rank) -> merged inside LDS by the owners, which keep the
@@ -713,9 +745,10 @@ class MiniSharded:
         mine = (cuts[me], cuts[me + 1])
         seg_me = (seg[:, mine[0]:mine[1] + 1] - at[:, me:me + 1]).contiguous()        # [part, owned + 1]
         bins_out = torch.empty(world * cap1, dtype=torch.int16, device=dev)
+        merge = L.pg_mini_merge_bins_masked if self.masked else L.pg_mini_merge_bins       # (masked: count-0 entries are looked up)
         with torch.cuda.device(dev):
-            _lib.check(L.pg_mini_merge_bins(recv.data_ptr(), cap1, seg_me.data_ptr(), world, uni.desc(), mine[0], mine[1], self.window, self.vsize,
-                                            bins_out.data_ptr(), uni.status.data_ptr(), stream_ptr))
+            _lib.check(merge(recv.data_ptr(), cap1, seg_me.data_ptr(), world, uni.desc(), mine[0], mine[1], self.window, self.vsize,
+                             bins_out.data_ptr(), uni.status.data_ptr(), stream_ptr))
         uni._empty = False
         bins = torch.empty(world * cap1, dtype=torch.int16, device=dev)
         _all_to_all_flat(bins.view(torch.uint8), bins_out.view(torch.uint8), group)     # (as bytes: neither RCCL nor gloo moves int16)
@@ -770,12 +803,20 @@ class MiniSharded:
         return codes[order], counts[order]
 
 
-def features_sharded_mini(stream: ReadStream, plan, k: int, k_tnf: int | None, window: int, vsize: int, group=None, max_tries: int = 4):
+def features_sharded_mini(stream: ReadStream, plan, k: int, k_tnf: int | None, window: int, vsize: int, group=None, max_tries: int = 4,
+                          lowercase_is_base: bool = False):
     """(tnf, abd, MiniSharded) of this rank's rows with the k-mers of ALL ranks' reads counted: sketches -> geometry -> count,
-    exchange, lookups; a full bucket anywhere enlarges the geometry on every rank and counts again"""
+    exchange, lookups; a full bucket anywhere enlarges the geometry on every rank and counts again.
+
+    Masked input (soft-masked with ``lowercase_is_base``, bases below the quality threshold): the table is counted with
+    ``stream.table_valid(lowercase_is_base)`` -- the union's sketch is taken over that plane -- and the rows with ``stream.valid``;
+    the local estimate is taken over their union (``ReadStream.union_valid``), whose row-only k-mers hold local slots and travel
+    as entries too."""
     from . import kmer
-    regs = kmer.distinct_sketch(stream, k)
-    local = kmer.sketch_estimate(regs)
+    regs = kmer.distinct_sketch(stream, k, lowercase_is_base=lowercase_is_base)
+    masked_here = KmerTable.half_masked(stream, lowercase_is_base)
+    local = kmer.sketch_estimate(kmer.distinct_sketch(stream, k, plane=stream.union_valid(lowercase_is_base)) if masked_here else regs)
+    masked = not everyone(not masked_here, group)                 # (any rank masked: every owner merges in the masked form)
     union = _staged(regs.clone(), group)
     dist.all_reduce(union, op=dist.ReduceOp.MAX, group=group)
     total = max(1 << 13, int(1.05 * kmer.sketch_estimate(union)))
@@ -790,14 +831,15 @@ def features_sharded_mini(stream: ReadStream, plan, k: int, k_tnf: int | None, w
     def key_partitioned():
         # a union that the super-k-mer geometry cannot hold (more than 2^16 buckets of 2^14 slots): the key-partitioned exchange,
         # on every rank -- the estimates behind this decision were all-reduced, so it is the same everywhere
-        table = count_kmers_sharded(stream, k, rows=plan, group=group)
+        table = count_kmers_sharded(stream, k, rows=plan, group=group, lowercase_is_base=lowercase_is_base)
         tnf, abd = kmer.features(stream, plan, k_tnf=k_tnf, table=table, window=window, vsize=vsize)
         return tnf, abd, None
 
     for attempt in range(max_tries):
         if log2_u - lb_u > _lib.MINI_MAX_LOG2_BUCKETS:
             return key_partitioned()
-        ms = MiniSharded(k, stream.device, log2_u, lb_l, window, vsize, group, union_log2_bucket=lb_u)
+        ms = MiniSharded(k, stream.device, log2_u, lb_l, window, vsize, group, union_log2_bucket=lb_u,
+                         lowercase_is_base=lowercase_is_base, masked=masked)
         ms.count(stream, plan, check=False)
         if not ms.any_full():
             tnf, abd = kmer.features(stream, plan, k_tnf=k_tnf, table=ms.local, window=window, vsize=vsize)

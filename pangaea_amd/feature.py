@@ -107,14 +107,16 @@ def _ingest(reads1: str, reads2: str | None, world: int, stream_cache: str | Non
 
 def _sharded_mini_applies(stream, plan, k, window, vsize, lowercase_is_base) -> bool:
     """may the multi-rank super-k-mer form (``dist.MiniSharded``) take this input?  Packed slots (13 <= k <= 21), rows the
-    partition records can name, exact bins, no soft-masked / quality-masked planes -- and the SAME answer on every rank.
+    partition records can name, exact bins -- and the SAME answer on every rank.  Soft-masked / quality-masked input (a table
+    plane other than the rows' strict one) takes the masked count half, which needs the merged lookups and at most 2^19 - 2 rows
+    (``MiniSharded.masked_rows_apply``).
     Rows: up to 2^17 - 1 in any form of the lookups; beyond, where the library's merged lookups apply to the local geometry
     (``MiniSharded.rows_apply`` asks ``pg_mini_merge_form_applies``: at most 2^19 rows at -v 400), the row shuffle then taking
     two scatter passes.  A share too large for one piece of scratch is counted in pieces (``KmerTable.count_half``)."""
     from . import _lib
     ok = (_lib.MINI_MIN_K <= k <= _lib.HASH_MAX_K and plan.shuffle_ok and plan.n_rows > 0
           and 1 <= vsize <= _lib.SHUFFLE_MAX_VSIZE and pdist.MiniSharded.rows_apply(k, plan.n_rows, vsize) and window >= 1 and window * vsize <= _lib.HASH_COUNT_SAT
-          and stream.table_valid(lowercase_is_base) is stream.valid and stream.rows_inside_table
+          and (not KmerTable.half_masked(stream, lowercase_is_base) or pdist.MiniSharded.masked_rows_apply(k, plan.n_rows, vsize))
           and os.environ.get("PANGAEA_NO_MINI", "0") in ("", "0"))
     return pdist.everyone(ok)
 
@@ -156,7 +158,7 @@ def compute_features(reads1: str, reads2: str | None, k: int, k_tnf: int, window
     tnf = abd = None
     if want_abd and table is None and world > 1 and _sharded_mini_applies(stream, plan, k, window, vsize, lowercase_is_base):
         # several ranks: the super-k-mer pipeline on every rank's own reads, entries to bucket owners, bins back
-        tnf, abd, _ = pdist.features_sharded_mini(stream, plan, k, k_tnf if want_tnf else None, window, vsize)
+        tnf, abd, _ = pdist.features_sharded_mini(stream, plan, k, k_tnf if want_tnf else None, window, vsize, lowercase_is_base=lowercase_is_base)
     else:
         if want_abd and table is None:
             table = (pdist.count_kmers_sharded(stream, k, rows=plan, lowercase_is_base=lowercase_is_base) if world > 1

@@ -355,23 +355,47 @@ class KmerTable:
         return (codes.data_ptr(), codes._version, plane.data_ptr(), plane._version, word_begin, word_end, id(keep), bool(lenient),
                 log2_slots, log2_bucket)
 
-    def count_half(self, stream: ReadStream, rows: "Plan", emit: tuple, check: bool = True, world: int = 1) -> "KmerTable":
+    @staticmethod
+    def half_masked(stream: ReadStream, lowercase_is_base: bool = False) -> bool:
+        """does ``count_half`` of this stream take the masked form (a table plane other than the rows' strict one)?"""
+        return stream.table_valid(lowercase_is_base) is not stream.valid or not stream.rows_inside_table
+
+    def count_half(self, stream: ReadStream, rows: "Plan", emit: tuple, check: bool = True, world: int = 1,
+                   lowercase_is_base: bool = False) -> "KmerTable":
         """N > 1 ranks (``dist.MiniSharded``): the COUNT half of the super-k-mer pipeline on this rank's reads.  This table object
         only carries the rank's LOCAL geometry (the union's bucket count, slots for the rank's own k-mers): its slots are never
         written -- except by a count in pieces (``_count_half_pieces``; ``world`` sizes the exchange's buffers in that decision).
-        Left behind for ``dist``: the buckets' entries and occupancy (``_half``), the provisional words of the rows."""
+        Left behind for ``dist``: the buckets' entries and occupancy (``_half``), the provisional words of the rows.
+
+        Masked input (``half_masked``: soft-masked reads with ``lowercase_is_base``, bases below the quality threshold): the
+        table counts the k-mers of ``stream.table_valid(lowercase_is_base)``, the rows keep the strict plane ``stream.valid``, and
+        the kernels segment their union (include/pangaea_feat.h: pg_mini_count_half_masked).  A k-mer only a row sees takes a
+        local slot with count 0 -- its entry asks the owners for the bin of whatever the other ranks counted (the owners must
+        run ``pg_mini_merge_bins_masked``).  Needs the merged lookups and at most 2^19 - 2 rows."""
         if self.kind != "mini":
             raise ValueError("count_half() is for packed mini tables (13 <= k <= 21)")
         _require_gpu(stream.codes, "the read stream")
-        plane = stream.table_valid(False)
-        if plane is not stream.valid or not stream.rows_inside_table:
-            raise ValueError("count_half() takes plain streams (no soft-masked / quality-masked planes)")
         self._half_world = int(world)
-        return self._count_mini(stream, 0, stream.n_words, plane, rows, lambda plan: C.byref(plan.rows_desc), emit, False, check, half=True)
+        if not self.half_masked(stream, lowercase_is_base):
+            plane = stream.table_valid(False)
+            return self._count_mini(stream, 0, stream.n_words, plane, rows, lambda plan: C.byref(plan.rows_desc), emit, False, check, half=True)
+        if rows is None or rows.n_rows > _lib.MINI_MASKED_MAX_ROWS or os.environ.get("PG_MINI_MERGE", "1") in ("", "0"):
+            raise ValueError(f"count_half() of masked input needs the merged lookups and at most {_lib.MINI_MASKED_MAX_ROWS} rows")
+        tab = stream.table_valid(lowercase_is_base)
 
-    def _count_mini(self, stream, word_begin, word_end, table_plane, rows, rows_arg, emit, lenient, check, half=False):
+        def strict_rows(plan):
+            # (the rows' own rule: the strict plane rides along, as in ``count``)
+            desc = _lib.pg_rows(plan.row_start.data_ptr(), plan.row_end.data_ptr(), plan.n_rows, stream.valid.data_ptr())
+            self._rows_desc_keepalive = desc
+            return C.byref(desc)
+
+        return self._count_mini(stream, 0, stream.n_words, stream.union_valid(lowercase_is_base), rows, strict_rows, emit, True, check,
+                                half=True, tab_plane=tab)
+
+    def _count_mini(self, stream, word_begin, word_end, table_plane, rows, rows_arg, emit, lenient, check, half=False, tab_plane=None):
         """the super-k-mer pipeline (pg_mini_plan + pg_mini_count): a fresh table, one piece.  The partition plan depends on
-        the stream, the rows and the geometry only and is kept: counting the same range again skips pg_mini_plan."""
+        the stream, the rows and the geometry only and is kept: counting the same range again skips pg_mini_plan.
+        ``tab_plane`` (a masked count half): the table plane, ``table_plane`` then being the union plane the kernels segment."""
         valid_ptr = table_plane.data_ptr()
         if not self._empty:
             raise ValueError("mini tables are built by ONE count of a fresh (or reset) table")
@@ -390,9 +414,12 @@ class KmerTable:
         self._half_pieces = None
         piece_words = self._half_piece_words(n_words, keep, int(emit[1])) if half and fuse else None
         if piece_words is not None:
-            return self._count_half_pieces(stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check)
+            return self._count_half_pieces(stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check, tab_plane)
         key = self._plan_key(stream.codes, table_plane, word_begin, word_end, keep, lenient, self.log2_slots, self.log2_bucket)
         held = (stream.codes, table_plane)               # (kept with the plan: see _plan_key)
+        if tab_plane is not None:
+            key += (tab_plane.data_ptr(), tab_plane._version, stream.valid.data_ptr(), stream.valid._version)
+            held += (tab_plane, stream.valid)
         with torch.cuda.device(self.device):
             if (self._mini_plan is None or self._mini_plan[0] != key) and self._mini_next is not None and self._mini_next[0] == key:
                 # a plan computed ahead (``prefetch_plan``): the count waits for it ON THE DEVICE.  Its record counts size the
@@ -420,8 +447,12 @@ class KmerTable:
                 self._mini_spare = None
                 if ws is None:
                     ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
-                                          ws.data_ptr(), ws.numel(), _stream_ptr(self.device)))
+                if tab_plane is not None:
+                    _lib.check(L.pg_mini_plan_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), word_begin, word_end, self.desc(),
+                                                     rows_arg(keep), ws.data_ptr(), ws.numel(), _stream_ptr(self.device)))
+                else:
+                    _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
+                                              ws.data_ptr(), ws.numel(), _stream_ptr(self.device)))
                 head = ws[:24].view(torch.int64).cpu()                     # (host sync; once per plan: records, -, long records)
                 n_records = int(head[0])
                 if self._mini_plan is not None:
@@ -474,10 +505,17 @@ class KmerTable:
                 # (zeroed: a count half that refuses its plan -- PG_STATUS_PLAN_MISMATCH -- writes nothing, and the exchange sizes its
                 # buffers from these numbers before anybody has looked at the status word)
                 fill = torch.zeros(self.n_buckets, dtype=torch.int64, device=self.device)
-                _lib.check(L.pg_mini_count_half(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
-                                                plan_ws.data_ptr(), plan_ws.numel(), self._mini_rec_ws.data_ptr(), self._mini_rec_ws.numel(),
-                                                window, vsize, sws_ptr, sws_n, mws_ptr, mws_n, self._half_ws.data_ptr(), self._half_ws.numel(),
-                                                fill.data_ptr(), self.status.data_ptr(), _stream_ptr(self.device)))
+                if tab_plane is not None:
+                    _lib.check(L.pg_mini_count_half_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), word_begin, word_end, self.desc(),
+                                                           rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), self._mini_rec_ws.data_ptr(),
+                                                           self._mini_rec_ws.numel(), window, vsize, sws_ptr, sws_n, mws_ptr, mws_n,
+                                                           self._half_ws.data_ptr(), self._half_ws.numel(), fill.data_ptr(), self.status.data_ptr(),
+                                                           _stream_ptr(self.device)))
+                else:
+                    _lib.check(L.pg_mini_count_half(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
+                                                    plan_ws.data_ptr(), plan_ws.numel(), self._mini_rec_ws.data_ptr(), self._mini_rec_ws.numel(),
+                                                    window, vsize, sws_ptr, sws_n, mws_ptr, mws_n, self._half_ws.data_ptr(), self._half_ws.numel(),
+                                                    fill.data_ptr(), self.status.data_ptr(), _stream_ptr(self.device)))
                 self._half = (fill, n_words, keep, window, vsize)
             else:
                 _lib.check(L.pg_mini_count(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
@@ -591,7 +629,7 @@ class KmerTable:
         w = half_piece_words(free, n_words, self.log2_slots, self.log2_bucket, keep.n_rows, getattr(self, "_half_world", 1))
         return w if w is not None and w < n_words else None
 
-    def _count_half_pieces(self, stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check):
+    def _count_half_pieces(self, stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check, tab_plane=None):
         """the count half (``count_half``) of a stream counted in word ranges of ``piece_words`` (include/pangaea_feat.h:
         pg_mini_count_half_piece): every piece -> its plan, both scatter passes, the count INTO this table's own slots (allocated
         here: 8 bytes x 2^log2_slots), its 2-byte provisional slots and its records' meta words kept; the last piece leaves entries,
@@ -620,7 +658,11 @@ class KmerTable:
             for idx, (w0, w1) in enumerate(ranges):
                 need = _lib.check(L.pg_mini_plan_bytes(w1 - w0, self.desc()))
                 plan_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), sp))
+                if tab_plane is not None:
+                    _lib.check(L.pg_mini_plan_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), w0, w1, self.desc(), rows_arg(keep),
+                                                     plan_ws.data_ptr(), plan_ws.numel(), sp))
+                else:
+                    _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), sp))
                 head = plan_ws[:24].view(torch.int64).cpu()                 # (host wait, once per piece: records, -, long records)
                 n_records, n_long = int(head[0]), int(head[2])
                 need = _lib.check(L.pg_mini_records_bytes(slack(n_records), self.desc()))
@@ -629,17 +671,24 @@ class KmerTable:
                     rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
                 need = _lib.check(L.pg_mini_merge_words(w1 - w0, n_records, n_long, self.desc()))
                 merge_ws = torch.empty(need, dtype=torch.int32, device=self.device)
-                _lib.check(L.pg_mini_count_half_piece(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep),
-                                                      plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
-                                                      merge_ws.data_ptr(), merge_ws.numel(), self._half_ws.data_ptr(), self._half_ws.numel(),
-                                                      fill.data_ptr(), 1 if idx == 0 else 0, 1 if idx == len(ranges) - 1 else 0,
-                                                      self.status.data_ptr(), sp))
+                if tab_plane is not None:
+                    _lib.check(L.pg_mini_count_half_piece_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), w0, w1, self.desc(), rows_arg(keep),
+                                                                 plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
+                                                                 merge_ws.data_ptr(), merge_ws.numel(), self._half_ws.data_ptr(), self._half_ws.numel(),
+                                                                 fill.data_ptr(), 1 if idx == 0 else 0, 1 if idx == len(ranges) - 1 else 0,
+                                                                 self.status.data_ptr(), sp))
+                else:
+                    _lib.check(L.pg_mini_count_half_piece(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep),
+                                                          plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
+                                                          merge_ws.data_ptr(), merge_ws.numel(), self._half_ws.data_ptr(), self._half_ws.numel(),
+                                                          fill.data_ptr(), 1 if idx == 0 else 0, 1 if idx == len(ranges) - 1 else 0,
+                                                          self.status.data_ptr(), sp))
                 moff = _lib.check(L.pg_mini_records_meta_offset(rec_ws.numel(), self.desc()))
                 meta = rec_ws[moff: moff + 4 * n_records].view(torch.int32).clone()
                 kept.append((plan_ws, merge_ws, meta, w1 - w0))
             rec_ws = None
         self._half = (fill, n_words, keep, window, vsize)
-        self._half_pieces = (kept, (stream.codes, table_plane))
+        self._half_pieces = (kept, (stream.codes, table_plane) + (() if tab_plane is None else (tab_plane, stream.valid)))
         self._mini_pieces = len(ranges)
         self._mini_optimistic = None
         self._empty = False
@@ -1103,15 +1152,16 @@ def key42_inverse(keys: np.ndarray) -> np.ndarray:
 
 
 def distinct_sketch(stream: ReadStream, k: int, word_begin: int = 0, word_end: int | None = None,
-                    lowercase_is_base: bool = False) -> torch.Tensor:
+                    lowercase_is_base: bool = False, plane: torch.Tensor | None = None) -> torch.Tensor:
     """HyperLogLog registers (int32 [4096], on the device) of the stream's canonical k-mers.  The elementwise maximum of
-    two sketches is the sketch of the union -- how the ranks of a multi-GPU job size their common table."""
+    two sketches is the sketch of the union -- how the ranks of a multi-GPU job size their common table.  ``plane``: another
+    validity plane than the table's (``ReadStream.union_valid``: what a masked count half holds in its local slots)."""
     _require_gpu(stream.codes, "the read stream")
     dev = stream.device
     regs = torch.zeros(_lib.HLL_REGISTERS, dtype=torch.int32, device=dev)
     word_end = stream.n_words if word_end is None else word_end
     with torch.cuda.device(dev):
-        valid = stream.table_valid(lowercase_is_base)
+        valid = stream.table_valid(lowercase_is_base) if plane is None else plane
         _lib.check(_lib.load().pg_kmer_distinct_sketch(stream.codes.data_ptr(), valid.data_ptr(), word_begin, word_end, k,
                                                        regs.data_ptr(), _stream_ptr(dev)))
     return regs

@@ -92,6 +92,20 @@ class ReadStream:
             setattr(self, key, v & ~self.valid_lowq)
         return getattr(self, key)
 
+    def union_valid(self, lowercase_is_base: bool = True) -> torch.Tensor:
+        """``table_valid(lowercase_is_base) | valid``: the plane the multi-rank super-k-mer form segments masked input with (a
+        k-mer is kept there if the table counts it or a row looks it up).  ``valid`` itself where the table plane lies inside it
+        (quality masks alone), the table plane where it holds ``valid`` (no quality masks)"""
+        t = self.table_valid(lowercase_is_base)
+        if t is self.valid or self.valid_lowq is None:
+            return t
+        if not lowercase_is_base or self.valid_lower is None:
+            return self.valid
+        # (only lowercase_is_base=True reaches here; the key names it all the same, as table_valid's do)
+        if getattr(self, "_union_valid_lc", None) is None:
+            self._union_valid_lc = t | self.valid
+        return self._union_valid_lc
+
     @property
     def rows_inside_table(self) -> bool:
         """is every k-mer of a row also a k-mer of the table's view?  (not when qualities mask bases: then the abundance
