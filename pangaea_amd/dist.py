@@ -18,8 +18,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .kmer import KmerTable
-from .reads import ReadStream
+from .kmer import KmerTable, _merged_lookups
+from .reads import ReadStream, words_for
 
 
 def is_distributed() -> bool:
@@ -98,45 +98,30 @@ def shard_stream(stream: ReadStream, rank: int, world: int) -> ReadStream:
     c0 = int(stream.run_off[first])
     c1 = int(stream.run_off[last]) if rank < world - 1 else stream.n_chars
     w0, w1 = c0 // 32, (c1 + 31) // 32
-    codes = stream.codes[w0:w1].clone()
-    valid = stream.valid[w0:w1].clone()
-    # characters of neighbouring ranks that share the first / last word are masked out (they are counted there)
-    if codes.numel():
-        lo, hi = c0 - 32 * w0, c1 - 32 * (w1 - 1)
-        keep_first = ~((1 << lo) - 1) & 0xFFFFFFFF
-        keep_last = ((1 << hi) - 1) & 0xFFFFFFFF if hi < 32 else 0xFFFFFFFF
-        v = valid.to(torch.int64) & 0xFFFFFFFF
-        v[0] &= keep_first
-        v[-1] &= keep_last
-        valid = torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32)
-    from .reads import words_for
+    lo, hi = c0 - 32 * w0, c1 - 32 * (w1 - 1)
     pad = words_for((w1 - w0) * 32) - (w1 - w0)
+    codes = stream.codes[w0:w1].clone()
     if pad:
         codes = torch.cat([codes, codes.new_zeros(pad)])
-        valid = torch.cat([valid, valid.new_zeros(pad)])
     run_off = stream.run_off[first:last + 1] - 32 * w0
-    lower = None
-    if stream.valid_lower is not None:          # the lower-case plane is cut and masked exactly like `valid`
-        lower = stream.valid_lower[w0:w1].clone()
-        if lower.numel():
-            lv = lower.to(torch.int64) & 0xFFFFFFFF
-            lv[0] &= keep_first
-            lv[-1] &= keep_last
-            lower = torch.where(lv >= (1 << 31), lv - (1 << 32), lv).to(torch.int32)
-        if pad:
-            lower = torch.cat([lower, lower.new_zeros(pad)])
-    lowq = None
-    if stream.valid_lowq is not None:           # the quality plane too
-        lowq = stream.valid_lowq[w0:w1].clone()
-        if lowq.numel():
-            qv = lowq.to(torch.int64) & 0xFFFFFFFF
-            qv[0] &= keep_first
-            qv[-1] &= keep_last
-            lowq = torch.where(qv >= (1 << 31), qv - (1 << 32), qv).to(torch.int32)
-        if pad:
-            lowq = torch.cat([lowq, lowq.new_zeros(pad)])
+    valid, lower, lowq = (_cut_plane(p, w0, w1, lo, hi, pad) for p in (stream.valid, stream.valid_lower, stream.valid_lowq))
     return ReadStream(codes, valid, c1 - 32 * w0, run_off.astype(np.int64), stream.run_names[first:last], mode=stream.mode,
                       valid_lower=lower, valid_lowq=lowq)
+
+
+def _cut_plane(plane: "torch.Tensor | None", w0: int, w1: int, lo: int, hi: int, pad: int) -> "torch.Tensor | None":
+    """words [w0, w1) of a validity plane (strict, lower-case or quality: all are cut alike), followed by ``pad`` empty words.
+    Characters of neighbouring ranks that share the first / last word are masked out (they are counted there): the rank's own
+    start at bit ``lo`` of the first word and end before bit ``hi`` of the last."""
+    if plane is None:
+        return None
+    plane = plane[w0:w1].clone()
+    if plane.numel():
+        v = plane.to(torch.int64) & 0xFFFFFFFF
+        v[0] &= ~((1 << lo) - 1) & 0xFFFFFFFF
+        v[-1] &= ((1 << hi) - 1) & 0xFFFFFFFF if hi < 32 else 0xFFFFFFFF
+        plane = torch.where(v >= (1 << 31), v - (1 << 32), v).to(torch.int32)
+    return torch.cat([plane, plane.new_zeros(pad)]) if pad else plane
 
 
 def ingest_shard(reads1: str, reads2: str | None = None, group=None, device="cpu") -> ReadStream:
@@ -207,15 +192,20 @@ def gather_pairs(local: torch.Tensor, group=None) -> list[torch.Tensor]:
     return [o[:s].to(home) for o, s in zip(out, sizes)]
 
 
-def everyone(flag: bool, group=None) -> bool:
+def everyone(flag: bool, group=None, device=None) -> bool:
     """the same answer on every rank: did ALL ranks say yes?  (decisions that select between collectives -- or between doing
     one and not -- must not be taken rank by rank).  ``group=None``: the control plane when there is one, so that the
-    question may be asked right behind a long stretch of one rank's host work."""
-    if group is None and _CONTROL is not None:
-        group = _CONTROL
-    t = torch.tensor([1 if flag else 0], dtype=torch.int32)
-    if dist.get_backend(group) == "nccl":
-        t = t.to(torch.device("cuda", torch.cuda.current_device()))
+    question may be asked right behind a long stretch of one rank's host work.  With ``device`` the question is part of the data
+    path: the flag is built there (staged through the host for gloo) and the collective stays on ``group`` as handed, the
+    default group included."""
+    if device is not None:
+        t = _staged(torch.tensor([1 if flag else 0], dtype=torch.int32, device=device), group)
+    else:
+        if group is None and _CONTROL is not None:
+            group = _CONTROL
+        t = torch.tensor([1 if flag else 0], dtype=torch.int32)
+        if dist.get_backend(group) == "nccl":
+            t = t.to(torch.device("cuda", torch.cuda.current_device()))
     dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
     return bool(t.item())
 
@@ -276,15 +266,10 @@ def count_kmers_sharded(stream: ReadStream, k: int, rows=None, group=None, max_l
         dist.all_reduce(flag, op=dist.ReduceOp.MAX, group=group)
         return int(flag.item()) != 0
 
-    def everyone(flag: bool) -> bool:
-        t = _staged(torch.tensor([1 if flag else 0], dtype=torch.int32, device=stream.device), group)
-        dist.all_reduce(t, op=dist.ReduceOp.MIN, group=group)
-        return bool(t.item())
-
     while True:
         g = deferred_group_for(table, int(1.1 * local)) if kind == "hash" else None
         # the exchange takes different collectives for deferred and materialised counts: all ranks must take the same form
-        if everyone(g is not None and table.can_defer(stream.n_words)):
+        if everyone(g is not None and table.can_defer(stream.n_words), group, device=stream.device):
             table.count(stream, rows=rows, deferred_group=g, check=False, lowercase_is_base=lowercase_is_base)
         else:
             table.count(stream, rows=rows, check=False, lowercase_is_base=lowercase_is_base)
@@ -591,6 +576,9 @@ class MiniSharded:
         # (the local table object carries geometry, plan and workspaces; its slots are never written: one word stands in)
         self.local = KmerTable(k, "mini", torch.zeros(1, dtype=torch.int64, device=device), bits + local_log2_bucket, local_log2_bucket)
         self.bytes_sent = self.bytes_received = 0
+        self._cap1 = None                # entries per (sender, owner) part of the exchange: read once, kept with slack
+        self._exchange_const = None      # (key, bucket cuts, owner of every bucket) on the device: geometry only
+        self._bins = self._elem = None   # what the owners sent back, between exchange and lookup_half
 
     @property
     def pieces(self) -> int:
@@ -612,25 +600,22 @@ class MiniSharded:
     def rows_apply(k: int, n_rows: int, vsize: int) -> bool:
         """may the count half take ``n_rows`` rows: up to 2^17 - 1 as always, beyond where the library's merged lookups apply
         (``pg_mini_merge_form_applies`` on the local bucket ``geometry`` gives these rows: at most 2^19 rows at vsize 400)"""
-        from . import _lib
-        import ctypes as C
-        if 0 < n_rows < (1 << 17):
-            return True
-        lb = MiniSharded.max_local_log2_bucket(n_rows)
-        bits = MiniSharded.MIN_LOG2_BUCKETS
-        desc = _lib.pg_table(_lib.TABLE_MINI, int(k), bits + lb, lb, 1)      # (geometry only: the data pointer is never read)
-        return _lib.check(_lib.load().pg_mini_merge_form_applies(C.byref(desc), int(n_rows), int(vsize))) == 1
+        return 0 < n_rows < (1 << 17) or MiniSharded._merge_form_applies(k, n_rows, vsize)
 
     @staticmethod
     def masked_rows_apply(k: int, n_rows: int, vsize: int) -> bool:
         """may the MASKED count half take ``n_rows`` rows: it needs the merged lookups (``pg_mini_merge_form_applies`` on the local
         bucket ``geometry`` gives these rows; PG_MINI_MERGE=0: never) and at most PG_MINI_MASKED_MAX_ROWS rows"""
         from . import _lib
+        return 0 < n_rows <= _lib.MINI_MASKED_MAX_ROWS and _merged_lookups() and MiniSharded._merge_form_applies(k, n_rows, vsize)
+
+    @staticmethod
+    def _merge_form_applies(k: int, n_rows: int, vsize: int) -> bool:
+        """``pg_mini_merge_form_applies`` on the smallest local geometry that gives ``n_rows`` rows their bits"""
+        from . import _lib
         import ctypes as C
-        if not 0 < n_rows <= _lib.MINI_MASKED_MAX_ROWS or os.environ.get("PG_MINI_MERGE", "1") in ("", "0"):
-            return False
         lb = MiniSharded.max_local_log2_bucket(n_rows)
-        desc = _lib.pg_table(_lib.TABLE_MINI, int(k), MiniSharded.MIN_LOG2_BUCKETS + lb, lb, 1)     # (geometry only)
+        desc = _lib.pg_table(_lib.TABLE_MINI, int(k), MiniSharded.MIN_LOG2_BUCKETS + lb, lb, 1)      # (geometry only: the data pointer is never read)
         return _lib.check(_lib.load().pg_mini_merge_form_applies(C.byref(desc), int(n_rows), int(vsize))) == 1
 
     @staticmethod
@@ -649,38 +634,28 @@ class MiniSharded:
     def count(self, stream: ReadStream, plan, check: bool = True) -> "MiniSharded":
         """count half on this rank, entries to the owners, merged bins back, lookup half: afterwards ``kmer.features(stream, plan,
         table=self.local, window, vsize)`` reads the abundance rows from the shuffled words"""
+        from . import _lib
         self.count_half(stream, plan)
         self.exchange()
         self.lookup_half()
-        if check:
-            bits = self.status_bits()
-            if bits & self._overflow_bit() and self.local.can_reexchange():
-                # (a count half in pieces keeps its entries, fills and pieces: the exchange and the lookups again, no recount)
-                self._cap1 = None
-                keep = ~self._overflow_bit()
-                self.local.status.bitwise_and_(keep); self.union.status.zero_()
-                self.union.reset()
-                self.exchange()
-                self.lookup_half()
-                return self.count_checked()
-            if bits & self._overflow_bit():
-                # the parts of this batch did not fit the size kept from an earlier one (``exchange``): ask again, count again
-                self._cap1 = None
+        if not check:
+            return self
+        bits = self.status_bits()
+        if bits & _lib.STATUS_OVERFLOW_LIST:
+            # the parts of this batch did not fit the size kept from an earlier one (``exchange``): ask again, then ...
+            self._cap1 = None
+            if not self.local.can_reexchange():                # ... count again
                 self.local.status.zero_(); self.union.status.zero_()
                 return self.count(stream, plan, check=True)
-            self.check_status(bits)
+            # ... (a count half in pieces keeps its entries, fills and pieces) the exchange and the lookups again, no recount.  An
+            # exchange that overflows even with the size just read is not retried a second time: raised
+            self.local.status.bitwise_and_(~_lib.STATUS_OVERFLOW_LIST); self.union.status.zero_()
+            self.union.reset()
+            self.exchange()
+            self.lookup_half()
+            bits = None
+        self.check_status(bits)
         return self
-
-    def count_checked(self) -> "MiniSharded":
-        """``check_status`` of a count that has been exchanged again (an exchange that overflows even with the size just read is
-        not retried a second time: raised)"""
-        self.check_status()
-        return self
-
-    @staticmethod
-    def _overflow_bit() -> int:
-        from . import _lib
-        return _lib.STATUS_OVERFLOW_LIST
 
     def count_half(self, stream: ReadStream, plan) -> None:
         """plan -> first and second scatter pass -> the bucket workgroups' count half (this rank's reads only)"""
@@ -701,12 +676,12 @@ class MiniSharded:
         group = self.group
         world, me = dist.get_world_size(group), dist.get_rank(group)
         loc, uni = self.local, self.union
-        fill = loc._half[0]
+        fill = loc._half.fill
         nb = loc.n_buckets
         dev = fill.device
         L = _lib.load()
         cuts = [nb * o // world for o in range(world + 1)]
-        const = getattr(self, "_exchange_const", None)
+        const = self._exchange_const
         if const is None or const[0] != (nb, world, str(dev)):
             # (what depends on the geometry alone: built once, not copied to the device in every step)
             cut_idx = torch.tensor(cuts, device=dev, dtype=torch.int64)
@@ -723,7 +698,7 @@ class MiniSharded:
             return seg, at, at[:, 1:] - at[:, :-1]                                   # sizes: [part, owner]
 
         seg, at, sizes = parts(fills)
-        cap1 = getattr(self, "_cap1", None)
+        cap1 = self._cap1
         if cap1 is None:
             longest = int(sizes.max().item())                                        # host wait: once per object (or after an overflow)
             cap1 = self._cap1 = max(8, (longest + longest // 32 + 7) // 8 * 8)

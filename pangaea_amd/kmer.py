@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -27,6 +28,49 @@ def _require_gpu(t: torch.Tensor, what: str) -> None:
     if not t.is_cuda:
         raise RuntimeError(f"{what} must live on a GPU: the k-mer kernels have no CPU path "
                            f"(got a tensor on {t.device})")
+
+
+def _merged_lookups() -> bool:
+    """the merged form of the super-k-mer lookups (provisional words in fixed slots per record); PG_MINI_MERGE=0: word-wise"""
+    return os.environ.get("PG_MINI_MERGE", "1") not in ("", "0")
+
+
+def _slack(n: int) -> int:
+    """3 % of slack on a plan's counts: the next batch of the same size then finds room without asking"""
+    return n + n // 32 + 4096
+
+
+def _plan_head(ws: torch.Tensor) -> tuple:
+    """(records, records of more than four k-mers) from the head of a plan workspace: 1st and 3rd word.  A host wait."""
+    head = ws[:24].view(torch.int64).cpu()
+    return int(head[0]), int(head[2])
+
+
+# library calls that have a twin for a masked count half: the same arguments, the table plane's pointer behind the union plane's
+_MASKED_TWIN = {"pg_mini_plan": "pg_mini_plan_masked", "pg_mini_count_half": "pg_mini_count_half_masked",
+                "pg_mini_count_half_piece": "pg_mini_count_half_piece_masked"}
+
+
+def _plain_or_masked(name: str, stream: ReadStream, plane: torch.Tensor, tab_plane: "torch.Tensor | None", *rest) -> None:
+    """``name(codes, plane, *rest)`` or, where the table has a plane of its own (``tab_plane``: a masked count half, ``plane`` then
+    being the union plane the kernels segment), its masked twin"""
+    L = _lib.load()
+    if tab_plane is None:
+        _lib.check(getattr(L, name)(stream.codes.data_ptr(), plane.data_ptr(), *rest))
+    else:
+        _lib.check(getattr(L, _MASKED_TWIN[name])(stream.codes.data_ptr(), plane.data_ptr(), tab_plane.data_ptr(), *rest))
+
+
+# what a mini table keeps between calls.  Named tuples on purpose: callers read them by position too.
+# the plan in use: ``KmerTable._plan_key`` (("pieces", n) stands in after a count in pieces), the plan workspace, its record count,
+# the rows, the tensors the key names (kept with the plan: see ``_plan_key``), its records of more than four k-mers.  The two
+# counts are None while they are still on the device (``KmerTable.plan_counts`` reads them)
+_MiniPlan = namedtuple("_MiniPlan", "key ws n_records rows held n_long")
+_MiniNext = namedtuple("_MiniNext", "key ws event rows held")                  # a plan computed ahead on a side stream
+_Half = namedtuple("_Half", "fill n_words rows window vsize")                  # between count_half and lookup_half
+# a word range of a count in pieces: its plan, its 2-byte provisional slots, its bucket-ordered records' meta words, its words
+_Piece = namedtuple("_Piece", "plan_ws merge_ws meta n_words")
+_Optimistic = namedtuple("_Optimistic", "stream word_begin word_end rows emit half")   # the arguments of a count to do again
 
 
 class KmerTable:
@@ -57,16 +101,16 @@ class KmerTable:
         self._records = None             # (plan, n_words) while the workspace holds the row-tagged records of ONE count
         self._deferred = None            # (fill, n_words) after a deferred count: entries wait in the workspace, slots unwritten
         self._emitted = None             # (window, vsize) while the shuffle workspace holds the words of a fused count + lookup
-        self._mini_plan = None           # (key, plan workspace, n_records) of the last pg_mini_plan: reused while the key matches
-        self._mini_next = None           # (key, plan workspace, event, rows) of a plan computed ahead on a side stream
+        self._mini_plan = None           # _MiniPlan of the last pg_mini_plan: reused while the key matches
+        self._mini_next = None           # _MiniNext: a plan computed ahead on a side stream
         self._mini_spare = None          # the plan workspace that is neither in use nor being filled
         self._mini_rec_ws = None
         self._mini_sized_for = None      # (n_words, geometry) the record / slot workspaces were sized for (with slack)
-        self._mini_optimistic = None     # the arguments of a count that ran on them without reading its plan's counts
+        self._mini_optimistic = None     # _Optimistic: the arguments of a count that ran on them without reading its plan's counts
         self._mini_pieces = 1            # word ranges the last count of a mini table was done in (``_count_mini_pieces``)
-        self._half = None                # (fill, n_words, rows, window, vsize) between count_half and lookup_half (N > 1 ranks)
+        self._half = None                # _Half, between count_half and lookup_half (N > 1 ranks)
         self._half_ws = None
-        self._half_pieces = None         # ([(plan ws, slot buffer, meta words, words) per piece], held tensors) of a count half in pieces
+        self._half_pieces = None         # ([_Piece], held tensors) of a count half in pieces
         self._half_world = 1             # ranks the count half's exchange goes to (its buffers count in the pieces decision)
         self._merge_ws = None            # the provisional words of the merged lookups (fixed slots per record)
 
@@ -217,12 +261,21 @@ class KmerTable:
         self._emitted = None
         return self
 
+    def _grown(self, name: str, need: int, dtype=torch.uint8, exact: bool = False, shrink: bool = False) -> torch.Tensor:
+        """the workspace held in attribute ``name``, with room for ``need`` elements.  One that is too small is dropped BEFORE its
+        successor is allocated (at 100 GB both would not fit) -- which is why this takes the attribute, not the tensor: a
+        caller's reference would keep the old one alive.  ``exact``: any other size is replaced (a size that depends on the
+        geometry alone); ``shrink``: so is one more than twice too large."""
+        buf = getattr(self, name)
+        n = -1 if buf is None else buf.numel()
+        del buf
+        if n < need or (exact and n != need) or (shrink and n > 2 * need):
+            setattr(self, name, None)
+            setattr(self, name, torch.empty(need, dtype=dtype, device=self.device))
+        return getattr(self, name)
+
     def _workspace_for(self, n_words: int) -> torch.Tensor:
-        need = _lib.check(_lib.load().pg_kmer_count_workspace_bytes(n_words, self.desc()))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._workspace
+        return self._grown("_workspace", _lib.check(_lib.load().pg_kmer_count_workspace_bytes(n_words, self.desc())))
 
     def can_defer(self, n_words: int) -> bool:
         """may ``count(..., deferred_group=g)`` be used for a fresh count of ``n_words`` words?"""
@@ -230,11 +283,7 @@ class KmerTable:
         return self._bucketed() and self._empty and self.log2_slots - self.log2_bucket > 8 and n_words <= step
 
     def _shuffle_workspace_for(self, n_words: int, n_rows: int, vsize: int) -> torch.Tensor:
-        need = _lib.check(_lib.load().pg_abundance_workspace_bytes(n_words, n_rows, vsize, self.desc()))
-        if self._shuffle_ws is None or self._shuffle_ws.numel() < need:
-            self._shuffle_ws = None
-            self._shuffle_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._shuffle_ws
+        return self._grown("_shuffle_ws", _lib.check(_lib.load().pg_abundance_workspace_bytes(n_words, n_rows, vsize, self.desc())))
 
     def count(self, stream: ReadStream, word_begin: int = 0, word_end: int | None = None, check: bool = True,
               rows: "Plan | None" = None, deferred_group: int | None = None, emit: tuple | None = None,
@@ -273,20 +322,10 @@ class KmerTable:
             # expresses (count_kmer.cpp:87) -- no row-tagged records, no fused lookups
             rows = emit = None
 
-        def rows_arg(plan):
-            # the rows' own validity rule stays the strict one: with a lenient counting plane the strict plane rides along
-            if plan is None:
-                return None
-            if not lenient:
-                return C.byref(plan.rows_desc)
-            desc = _lib.pg_rows(plan.row_start.data_ptr(), plan.row_end.data_ptr(), plan.n_rows, stream.valid.data_ptr())
-            self._rows_desc_keepalive = desc
-            return C.byref(desc)
-
         if self.kind in ("mini", "miniw"):
             if deferred_group is not None:
                 raise ValueError("mini tables have no deferred form")
-            return self._count_mini(stream, word_begin, word_end, table_plane, rows, rows_arg, emit, lenient, check)
+            return self._count_mini(stream, word_begin, word_end, table_plane, rows, emit, lenient, check)
         if deferred_group is not None:
             if not self.can_defer(word_end - word_begin):
                 raise ValueError("deferred counting needs a fresh bucketed table with more than 256 buckets and a single pass")
@@ -296,7 +335,7 @@ class KmerTable:
             fill = torch.empty(self.n_buckets, dtype=torch.int64, device=self.device)
             with torch.cuda.device(self.device):
                 _lib.check(L.pg_kmer_count_deferred(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), g,
-                                                    rows_arg(keep), ws.data_ptr(), ws.numel(),
+                                                    self._rows_ref(keep, stream, lenient), ws.data_ptr(), ws.numel(),
                                                     fill.data_ptr(), self.status.data_ptr(), _stream_ptr(self.device)))
             self._empty = False
             self._deferred = (fill, word_end - word_begin)
@@ -320,7 +359,7 @@ class KmerTable:
                     ws = self._workspace_for(n_words)
                     sws = self._shuffle_workspace_for(n_words, keep.n_rows, vsize)
                     _lib.check(L.pg_kmer_count_bucketed_emit(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(),
-                                                             rows_arg(keep), ws.data_ptr(), ws.numel(), window, vsize,
+                                                             self._rows_ref(keep, stream, lenient), ws.data_ptr(), ws.numel(), window, vsize,
                                                              sws.data_ptr(), sws.numel(), self.status.data_ptr(), _stream_ptr(self.device)))
                     self._empty = False
                     self._records = (keep, n_words)
@@ -332,7 +371,7 @@ class KmerTable:
                     w1 = min(word_end, w0 + step)
                     ws = self._workspace_for(w1 - w0)
                     _lib.check(L.pg_kmer_count_bucketed(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(),
-                                                        0 if self._empty else 1, rows_arg(keep),
+                                                        0 if self._empty else 1, self._rows_ref(keep, stream, lenient),
                                                         ws.data_ptr(), ws.numel(), self.status.data_ptr(), _stream_ptr(self.device)))
                     self._empty = False
                 if keep is not None:
@@ -369,7 +408,7 @@ class KmerTable:
 
         Masked input (``half_masked``: soft-masked reads with ``lowercase_is_base``, bases below the quality threshold): the
         table counts the k-mers of ``stream.table_valid(lowercase_is_base)``, the rows keep the strict plane ``stream.valid``, and
-        the kernels segment their union (include/pangaea_feat.h: pg_mini_count_half_masked).  A k-mer only a row sees takes a
+        the kernels segment their union (include/pangaea_feat.h: the masked count half).  A k-mer only a row sees takes a
         local slot with count 0 -- its entry asks the owners for the bin of whatever the other ranks counted (the owners must
         run ``pg_mini_merge_bins_masked``).  Needs the merged lookups and at most 2^19 - 2 rows."""
         if self.kind != "mini":
@@ -377,26 +416,17 @@ class KmerTable:
         _require_gpu(stream.codes, "the read stream")
         self._half_world = int(world)
         if not self.half_masked(stream, lowercase_is_base):
-            plane = stream.table_valid(False)
-            return self._count_mini(stream, 0, stream.n_words, plane, rows, lambda plan: C.byref(plan.rows_desc), emit, False, check, half=True)
-        if rows is None or rows.n_rows > _lib.MINI_MASKED_MAX_ROWS or os.environ.get("PG_MINI_MERGE", "1") in ("", "0"):
+            return self._count_mini(stream, 0, stream.n_words, stream.table_valid(False), rows, emit, False, check, half=True)
+        if rows is None or rows.n_rows > _lib.MINI_MASKED_MAX_ROWS or not _merged_lookups():
             raise ValueError(f"count_half() of masked input needs the merged lookups and at most {_lib.MINI_MASKED_MAX_ROWS} rows")
-        tab = stream.table_valid(lowercase_is_base)
+        # (the rows' own rule: the strict plane rides along, as in ``count``)
+        return self._count_mini(stream, 0, stream.n_words, stream.union_valid(lowercase_is_base), rows, emit, True, check,
+                                half=True, tab_plane=stream.table_valid(lowercase_is_base))
 
-        def strict_rows(plan):
-            # (the rows' own rule: the strict plane rides along, as in ``count``)
-            desc = _lib.pg_rows(plan.row_start.data_ptr(), plan.row_end.data_ptr(), plan.n_rows, stream.valid.data_ptr())
-            self._rows_desc_keepalive = desc
-            return C.byref(desc)
-
-        return self._count_mini(stream, 0, stream.n_words, stream.union_valid(lowercase_is_base), rows, strict_rows, emit, True, check,
-                                half=True, tab_plane=tab)
-
-    def _count_mini(self, stream, word_begin, word_end, table_plane, rows, rows_arg, emit, lenient, check, half=False, tab_plane=None):
+    def _count_mini(self, stream, word_begin, word_end, table_plane, rows, emit, lenient, check, half=False, tab_plane=None):
         """the super-k-mer pipeline (pg_mini_plan + pg_mini_count): a fresh table, one piece.  The partition plan depends on
         the stream, the rows and the geometry only and is kept: counting the same range again skips pg_mini_plan.
         ``tab_plane`` (a masked count half): the table plane, ``table_plane`` then being the union plane the kernels segment."""
-        valid_ptr = table_plane.data_ptr()
         if not self._empty:
             raise ValueError("mini tables are built by ONE count of a fresh (or reset) table")
         L = _lib.load()
@@ -406,146 +436,155 @@ class KmerTable:
             raise ValueError("mini tables need sorted, disjoint, non-empty rows (at most 2^20 - 2 of them)")
         fuse = (emit is not None and keep is not None and n_words > 0 and 1 <= emit[1] <= _lib.SHUFFLE_MAX_VSIZE and emit[0] >= 1
                 and (self.kind == "miniw" or emit[0] * emit[1] <= _lib.HASH_COUNT_SAT))
+        if half and not fuse:
+            raise ValueError("count_half() needs rows and abundance parameters")
+        window, vsize = (int(emit[0]), int(emit[1])) if fuse else (0, 0)
+        rows_ref = self._rows_ref(keep, stream, lenient)
         # a stream whose scratch would not fit in one piece (about 3.4 KB per 150 bp read pair; PANGAEA_MINI_PIECE_WORDS forces a
         # piece size) is counted word range by word range into the same table, its lookups done when the table is final
         piece_words = self._piece_words(n_words, fuse and not half)
         if piece_words is not None:
-            return self._count_mini_pieces(stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check)
+            return self._count_mini_pieces(stream, word_begin, word_end, table_plane, keep, rows_ref, window, vsize, piece_words, check)
         self._half_pieces = None
-        piece_words = self._half_piece_words(n_words, keep, int(emit[1])) if half and fuse else None
+        piece_words = self._half_piece_words(n_words, keep, vsize) if half else None
         if piece_words is not None:
-            return self._count_half_pieces(stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check, tab_plane)
+            return self._count_half_pieces(stream, word_begin, word_end, table_plane, keep, rows_ref, window, vsize, piece_words, check, tab_plane)
         key = self._plan_key(stream.codes, table_plane, word_begin, word_end, keep, lenient, self.log2_slots, self.log2_bucket)
         held = (stream.codes, table_plane)               # (kept with the plan: see _plan_key)
         if tab_plane is not None:
             key += (tab_plane.data_ptr(), tab_plane._version, stream.valid.data_ptr(), stream.valid._version)
             held += (tab_plane, stream.valid)
+        sp = _stream_ptr(self.device)
         with torch.cuda.device(self.device):
-            if (self._mini_plan is None or self._mini_plan[0] != key) and self._mini_next is not None and self._mini_next[0] == key:
-                # a plan computed ahead (``prefetch_plan``): the count waits for it ON THE DEVICE.  Its record counts size the
-                # record and slot workspaces -- but where workspaces of a batch of the same size exist already (a stream of batches),
-                # they are used as they are and the host does not wait for the plan at all: the kernels themselves refuse a plan that
-                # names more records than the buffers hold (PG_STATUS_PLAN_MISMATCH, nothing is written), and ``check_status`` /
-                # the check below then count again with workspaces of the right size.  The counts stay on the device until
-                # somebody asks (``plan_counts``).
-                _, ws, event, _ = self._mini_next[:4]
-                torch.cuda.current_stream(self.device).wait_event(event)
-                if self._mini_plan is not None:
-                    self._mini_spare = self._mini_plan[1]
-                sized_for = getattr(self, "_mini_sized_for", None)
-                if (sized_for == (n_words, self.log2_slots, self.log2_bucket) and self._mini_rec_ws is not None
-                        and os.environ.get("PG_PLAN_HOST_SYNC", "0") in ("", "0")):
-                    self._mini_plan = (key, ws, None, keep, held, None)
-                else:
-                    event.synchronize()
-                    head = ws[:24].view(torch.int64).cpu()                 # (records, -, records of more than four k-mers)
-                    self._mini_plan = (key, ws, int(head[0]), keep, held, int(head[2]))
-                self._mini_next = None
-            if self._mini_plan is None or self._mini_plan[0] != key:
-                need = _lib.check(L.pg_mini_plan_bytes(n_words, self.desc()))
-                ws = self._mini_spare if self._mini_spare is not None and self._mini_spare.numel() == need else None
-                self._mini_spare = None
-                if ws is None:
-                    ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                if tab_plane is not None:
-                    _lib.check(L.pg_mini_plan_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), word_begin, word_end, self.desc(),
-                                                     rows_arg(keep), ws.data_ptr(), ws.numel(), _stream_ptr(self.device)))
-                else:
-                    _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
-                                              ws.data_ptr(), ws.numel(), _stream_ptr(self.device)))
-                head = ws[:24].view(torch.int64).cpu()                     # (host sync; once per plan: records, -, long records)
-                n_records = int(head[0])
-                if self._mini_plan is not None:
-                    self._mini_spare = self._mini_plan[1]
-                self._mini_plan = (key, ws, n_records, keep, held, int(head[2]))
-            _, plan_ws, n_records = self._mini_plan[:3]
+            if (self._mini_plan is None or self._mini_plan.key != key) and not self._take_prefetched_plan(key, n_words, keep, held):
+                self._compute_plan(key, stream, table_plane, tab_plane, word_begin, word_end, keep, rows_ref, held)
+            plan_ws, n_records, n_long = self._mini_plan.ws, self._mini_plan.n_records, self._mini_plan.n_long
             optimistic = n_records is None          # (workspaces of the previous batch of this size, the plan's counts unread)
-            # (3 % of slack on the counts: the next batch of the same size then finds room without asking)
-            slack = (lambda n: n + n // 32 + 4096)
             if not optimistic:
-                need = _lib.check(L.pg_mini_records_bytes(slack(n_records), self.desc()))
-                if self._mini_rec_ws is None or self._mini_rec_ws.numel() < need or self._mini_rec_ws.numel() > 2 * need:
-                    self._mini_rec_ws = None
-                    self._mini_rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+                # (``shrink``: a batch much smaller than the last gives the difference back)
+                self._grown("_mini_rec_ws", _lib.check(L.pg_mini_records_bytes(_slack(n_records), self.desc())), shrink=True)
                 self._mini_sized_for = (n_words, self.log2_slots, self.log2_bucket)
-            window, vsize, sws_ptr, sws_n = 0, 0, None, 0
+            sws_ptr, sws_n = None, 0
             if fuse:
-                window, vsize = int(emit[0]), int(emit[1])
                 # (with the merged lookups the provisional data live in their own buffer below: the row shuffle's layout is smaller)
-                merging = os.environ.get("PG_MINI_MERGE", "1") not in ("", "0")
-                need = _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, keep.n_rows, vsize, self.desc()) if merging
-                                  else L.pg_mini_shuffle_bytes(n_words, keep.n_rows, vsize))
-                if self._shuffle_ws is None or self._shuffle_ws.numel() < need:
-                    self._shuffle_ws = None
-                    self._shuffle_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                sws_ptr, sws_n = self._shuffle_ws.data_ptr(), self._shuffle_ws.numel()
+                sws = self._grown("_shuffle_ws", _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, keep.n_rows, vsize, self.desc()) if _merged_lookups()
+                                                            else L.pg_mini_shuffle_bytes(n_words, keep.n_rows, vsize)))
+                sws_ptr, sws_n = sws.data_ptr(), sws.numel()
             mws_ptr, mws_n = None, 0
-            if fuse and os.environ.get("PG_MINI_MERGE", "1") not in ("", "0"):
-                # the merged form of the lookups (PG_MINI_MERGE=0: word-wise): its provisional words lie in fixed slots per record,
-                # sized from the plan's record counts (records, and records of more than four k-mers: 1st and 3rd word of the plan
-                # workspace); the library falls back to the word-wise form where the merged one does not apply
-                if not optimistic or getattr(self, "_merge_ws", None) is None:
+            if fuse and _merged_lookups():
+                # the merged form of the lookups: its provisional words lie in fixed slots per record, sized from the plan's record
+                # counts; the library falls back to the word-wise form where the merged one does not apply
+                if not optimistic or self._merge_ws is None:
                     if optimistic:                                         # (no slot buffer yet: the counts are needed after all)
                         n_records, n_long = self.plan_counts()
                         optimistic = False
-                    else:
-                        n_long = self._mini_plan[5]
-                    need = _lib.check(L.pg_mini_merge_words(n_words, slack(n_records), min(slack(n_long), slack(n_records)), self.desc()))
-                    if getattr(self, "_merge_ws", None) is None or self._merge_ws.numel() < need:
-                        self._merge_ws = None
-                        self._merge_ws = torch.empty(need, dtype=torch.int32, device=self.device)
+                    self._grown("_merge_ws", _lib.check(L.pg_mini_merge_words(n_words, _slack(n_records), min(_slack(n_long), _slack(n_records)), self.desc())),
+                                dtype=torch.int32)
                 mws_ptr, mws_n = self._merge_ws.data_ptr(), self._merge_ws.numel()
+            rec_ws = self._mini_rec_ws
+            args = (word_begin, word_end, self.desc(), rows_ref, plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(),
+                    window, vsize, sws_ptr, sws_n, mws_ptr, mws_n)
             if half:
-                if not fuse:
-                    raise ValueError("count_half() needs rows and abundance parameters")
-                need = _lib.check(L.pg_mini_half_bytes(self.desc()))
-                if getattr(self, "_half_ws", None) is None or self._half_ws.numel() != need:
-                    self._half_ws = None
-                    self._half_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                # (zeroed: a count half that refuses its plan -- PG_STATUS_PLAN_MISMATCH -- writes nothing, and the exchange sizes its
-                # buffers from these numbers before anybody has looked at the status word)
-                fill = torch.zeros(self.n_buckets, dtype=torch.int64, device=self.device)
-                if tab_plane is not None:
-                    _lib.check(L.pg_mini_count_half_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), word_begin, word_end, self.desc(),
-                                                           rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), self._mini_rec_ws.data_ptr(),
-                                                           self._mini_rec_ws.numel(), window, vsize, sws_ptr, sws_n, mws_ptr, mws_n,
-                                                           self._half_ws.data_ptr(), self._half_ws.numel(), fill.data_ptr(), self.status.data_ptr(),
-                                                           _stream_ptr(self.device)))
-                else:
-                    _lib.check(L.pg_mini_count_half(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
-                                                    plan_ws.data_ptr(), plan_ws.numel(), self._mini_rec_ws.data_ptr(), self._mini_rec_ws.numel(),
-                                                    window, vsize, sws_ptr, sws_n, mws_ptr, mws_n, self._half_ws.data_ptr(), self._half_ws.numel(),
-                                                    fill.data_ptr(), self.status.data_ptr(), _stream_ptr(self.device)))
-                self._half = (fill, n_words, keep, window, vsize)
+                half_ws, fill = self._half_workspaces()
+                _plain_or_masked("pg_mini_count_half", stream, table_plane, tab_plane, *args, half_ws.data_ptr(), half_ws.numel(),
+                                 fill.data_ptr(), self.status.data_ptr(), sp)
+                self._half = _Half(fill, n_words, keep, window, vsize)
             else:
-                _lib.check(L.pg_mini_count(stream.codes.data_ptr(), valid_ptr, word_begin, word_end, self.desc(), rows_arg(keep),
-                                           plan_ws.data_ptr(), plan_ws.numel(), self._mini_rec_ws.data_ptr(), self._mini_rec_ws.numel(),
-                                           window, vsize, sws_ptr, sws_n, mws_ptr, mws_n, self.status.data_ptr(), _stream_ptr(self.device)))
+                _lib.check(L.pg_mini_count(stream.codes.data_ptr(), table_plane.data_ptr(), *args, self.status.data_ptr(), sp))
         self._empty = False
         self._mini_pieces = 1
         self._records = (keep, n_words) if fuse and not half else None
         self._emitted = (window, vsize) if fuse and not half else None
-        self._mini_optimistic = (stream, word_begin, word_end, rows, emit, half) if optimistic else None
+        self._mini_optimistic = _Optimistic(stream, word_begin, word_end, rows, emit, half) if optimistic else None
         if check:
             self.check_status()
         return self
+
+    def _take_prefetched_plan(self, key, n_words: int, keep, held) -> bool:
+        """a plan computed ahead (``prefetch_plan``) for this key becomes the plan in use: the count waits for it ON THE DEVICE.
+        Its record counts size the record and slot workspaces -- but where workspaces of a batch of the same size exist already (a
+        stream of batches), they are used as they are and the host does not wait for the plan at all: the kernels themselves refuse
+        a plan that names more records than the buffers hold (PG_STATUS_PLAN_MISMATCH, nothing is written), and ``check_status``
+        then counts again with workspaces of the right size.  The counts stay on the device until somebody asks (``plan_counts``).
+        False: no such plan."""
+        ahead = self._mini_next
+        if ahead is None or ahead.key != key:
+            return False
+        torch.cuda.current_stream(self.device).wait_event(ahead.event)
+        if self._mini_plan is not None:
+            self._mini_spare = self._mini_plan.ws
+        if (self._mini_sized_for == (n_words, self.log2_slots, self.log2_bucket) and self._mini_rec_ws is not None
+                and os.environ.get("PG_PLAN_HOST_SYNC", "0") in ("", "0")):
+            self._mini_plan = _MiniPlan(key, ahead.ws, None, keep, held, None)
+        else:
+            ahead.event.synchronize()
+            n_records, n_long = _plan_head(ahead.ws)
+            self._mini_plan = _MiniPlan(key, ahead.ws, n_records, keep, held, n_long)
+        self._mini_next = None
+        return True
+
+    def _compute_plan(self, key, stream, table_plane, tab_plane, word_begin, word_end, keep, rows_ref, held) -> None:
+        """pg_mini_plan in front of its count, into the spare plan workspace where that has the size; one host wait for its counts"""
+        need = _lib.check(_lib.load().pg_mini_plan_bytes(word_end - word_begin, self.desc()))
+        ws = self._mini_spare if self._mini_spare is not None and self._mini_spare.numel() == need else None
+        self._mini_spare = None
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        _plain_or_masked("pg_mini_plan", stream, table_plane, tab_plane, word_begin, word_end, self.desc(), rows_ref,
+                         ws.data_ptr(), ws.numel(), _stream_ptr(self.device))
+        n_records, n_long = _plan_head(ws)                             # (host sync; once per plan)
+        if self._mini_plan is not None:
+            self._mini_spare = self._mini_plan.ws
+        self._mini_plan = _MiniPlan(key, ws, n_records, keep, held, n_long)
+
+    def _rows_ref(self, plan, stream: ReadStream, lenient: bool):
+        """the rows argument of a library call (None without rows).  The rows' own validity rule stays the strict one: where the
+        table is counted under a lenient plane, the strict plane rides along."""
+        if plan is None:
+            return None
+        if not lenient:
+            return C.byref(plan.rows_desc)
+        self._rows_desc_keepalive = _lib.pg_rows(plan.row_start.data_ptr(), plan.row_end.data_ptr(), plan.n_rows, stream.valid.data_ptr())
+        return C.byref(self._rows_desc_keepalive)
+
+    def _half_workspaces(self) -> tuple:
+        """(entry slabs and occupancy of a count half, the buckets' fills).  The fills are zeroed: a count half that refuses its plan
+        -- PG_STATUS_PLAN_MISMATCH -- writes nothing, and the exchange sizes its buffers from these numbers before anybody has
+        looked at the status word."""
+        # (``exact``: the size is a function of the geometry alone)
+        half_ws = self._grown("_half_ws", _lib.check(_lib.load().pg_mini_half_bytes(self.desc())), exact=True)
+        return half_ws, torch.zeros(self.n_buckets, dtype=torch.int64, device=self.device)
 
     # bytes of scratch per word of the stream (32 characters): record workspace (two planes of 12-byte records, ~6.7 records per
     # word at k = 21), 2-byte slots of the merged lookups, the row shuffle's word regions (4 bytes per character)
     _PIECE_BYTES_PER_WORD = (24 * 7, 12 * 7, 4 * 32)
 
+    def _pieces_apply(self) -> bool:
+        """the pieces' kernels: packed slots, both scatter passes, the merged lookups"""
+        return self.kind == "mini" and self.n_buckets > 256 and _merged_lookups()
+
+    @staticmethod
+    def _forced_piece_words(n_words: int):
+        """(forced, words per piece or None for one piece) of PANGAEA_MINI_PIECE_WORDS"""
+        forced = os.environ.get("PANGAEA_MINI_PIECE_WORDS")
+        if not forced:
+            return False, None
+        w = max(_lib.WORD_ALIGN, int(forced) // _lib.WORD_ALIGN * _lib.WORD_ALIGN)
+        return True, (w if w < n_words else None)
+
+    def _free_bytes(self) -> int:
+        free, _ = torch.cuda.mem_get_info(self.device)
+        return free + torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # (cached blocks count as free)
+
     def _piece_words(self, n_words: int, applicable: bool):
         """None (one piece, the usual path) or the number of words per piece"""
-        forced = os.environ.get("PANGAEA_MINI_PIECE_WORDS")
-        if not applicable or self.kind != "mini" or self.n_buckets <= 256 or os.environ.get("PG_MINI_MERGE", "1") in ("", "0"):
-            return None                                          # (the pieces' kernels: packed slots, both scatter passes, the merged lookups)
+        if not applicable or not self._pieces_apply():
+            return None
+        forced, w = self._forced_piece_words(n_words)
         if forced:
-            w = max(_lib.WORD_ALIGN, int(forced) // _lib.WORD_ALIGN * _lib.WORD_ALIGN)
-            return w if w < n_words else None
+            return w
         rec, slots, words = self._PIECE_BYTES_PER_WORD
-        free, _ = torch.cuda.mem_get_info(self.device)
-        free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # (cached blocks count as free)
-        budget = 0.85 * free
+        budget = 0.85 * self._free_bytes()
         if (rec + slots + words) * n_words <= budget:
             return None
         room = budget - (slots + words + 4 * 7) * n_words          # what stays per word whatever the piece size (slots, kept meta, words)
@@ -553,93 +592,96 @@ class KmerTable:
             return None                                          # (not even in pieces: the one-piece path reports the allocation that fails)
         return max(_lib.WORD_ALIGN, int(room / rec) // _lib.WORD_ALIGN * _lib.WORD_ALIGN)
 
-    def _count_mini_pieces(self, stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check):
+    def _half_piece_words(self, n_words: int, keep: "Plan", vsize: int):
+        """``_piece_words`` for a count half (N > 1 ranks): None (one piece) or the words per piece.  PANGAEA_MINI_PIECE_WORDS forces
+        a piece size as on one GPU; otherwise ``half_piece_words`` decides from the free device memory, to which the workspaces this
+        table holds from an earlier count are added back (they are reused or replaced)."""
+        if not self._pieces_apply() or _lib.check(_lib.load().pg_mini_merge_form_applies(self.desc(), keep.n_rows, vsize)) != 1:
+            return None
+        forced, w = self._forced_piece_words(n_words)
+        if forced:
+            return w
+        held = [self._mini_rec_ws, self._shuffle_ws, self._merge_ws, self._half_ws] + ([self.data] if self.data.numel() > 1 else [])
+        free = self._free_bytes() + sum(int(t.numel()) * t.element_size() for t in held if t is not None)
+        w = half_piece_words(free, n_words, self.log2_slots, self.log2_bucket, keep.n_rows, self._half_world)
+        return w if w is not None and w < n_words else None
+
+    def _count_pieces(self, stream, word_begin, word_end, piece_words, table_plane, tab_plane, rows_ref, count) -> list:
+        """the piece loop of a count in word ranges of ``piece_words``: every range -> its plan (a host wait for its counts), a
+        record workspace that holds it (one for all pieces, grown where a piece needs more), the 2-byte provisional slots of its
+        merged lookups, then ``count(w0, w1, first, last, plan_ws, rec_ws, merge_ws)`` -- the caller's library call -- and the
+        records' meta words copied out.  Returns what the lookups need, a ``_Piece`` per range; the table is no longer empty.  (``count`` is a callback so that
+        nobody but this loop holds the record workspace: it is dropped before a larger one is allocated, and on return.)"""
+        L = _lib.load()
+        sp = _stream_ptr(self.device)
+        ranges = [(w0, min(word_end, w0 + piece_words)) for w0 in range(word_begin, word_end, piece_words)]
+        kept, rec_ws = [], None
+        for idx, (w0, w1) in enumerate(ranges):
+            plan_ws = torch.empty(_lib.check(L.pg_mini_plan_bytes(w1 - w0, self.desc())), dtype=torch.uint8, device=self.device)
+            _plain_or_masked("pg_mini_plan", stream, table_plane, tab_plane, w0, w1, self.desc(), rows_ref, plan_ws.data_ptr(), plan_ws.numel(), sp)
+            n_records, n_long = _plan_head(plan_ws)                    # (host wait, once per piece)
+            need = _lib.check(L.pg_mini_records_bytes(_slack(n_records), self.desc()))
+            if rec_ws is None or rec_ws.numel() < need:
+                rec_ws = None                                          # (dropped first, as ``_grown`` does)
+                rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            merge_ws = torch.empty(_lib.check(L.pg_mini_merge_words(w1 - w0, n_records, n_long, self.desc())), dtype=torch.int32, device=self.device)
+            count(w0, w1, 1 if idx == 0 else 0, 1 if idx == len(ranges) - 1 else 0, plan_ws, rec_ws, merge_ws)
+            # the bucket-ordered records' meta words (lengths, rows): the second meta plane of [bases A | bases B | meta A | meta B]
+            moff = _lib.check(L.pg_mini_records_meta_offset(rec_ws.numel(), self.desc()))
+            kept.append(_Piece(plan_ws, merge_ws, rec_ws[moff: moff + 4 * n_records].view(torch.int32).clone(), w1 - w0))
+        self._empty = False
+        self._mini_pieces = len(kept)
+        self._mini_optimistic = None
+        return kept
+
+    def _lookup_pieces(self, pieces, keep, held, n_words: int, window: int, vsize: int, rows_ref, lookup) -> None:
+        """the lookups of a count in pieces, once the table is final: the row shuffle's regions of the whole stream prepared once
+        (pg_mini_lookup_begin), then ``lookup(piece, sws)`` -- the caller's library call -- for every piece; ``features`` then reads
+        the rows from the shuffled words as after one count"""
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            sws = self._grown("_shuffle_ws", _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, keep.n_rows, vsize, self.desc())))
+            _lib.check(L.pg_mini_lookup_begin(self.desc(), rows_ref, n_words, vsize, sws.data_ptr(), sws.numel(), _stream_ptr(self.device)))
+            for piece in pieces:
+                lookup(piece, sws)
+            # (``abundance_from_records`` hands a plan workspace of the whole range to pg_mini_abundance_from_emitted, which only checks its
+            # size: a stand-in takes the place of the plan in use)
+            whole = torch.empty(_lib.check(L.pg_mini_plan_bytes(n_words, self.desc())), dtype=torch.uint8, device=self.device)
+        self._mini_plan = _MiniPlan(("pieces", len(pieces)), whole, sum(int(p.meta.numel()) for p in pieces), keep, held, 0)
+        self._records = (keep, n_words)
+        self._emitted = (window, vsize)
+
+    def _count_mini_pieces(self, stream, word_begin, word_end, table_plane, keep, rows_ref, window, vsize, piece_words, check):
         """``_count_mini`` for a stream counted in word ranges of ``piece_words`` (include/pangaea_feat.h: pg_mini_count_piece):
         every piece -> its plan, both scatter passes, the count INTO the table's buckets (slots keep their places), its 2-byte
         provisional slots and its records' meta words kept; then the lookups of every piece in the final table, into the row
         shuffle's regions of the whole stream.  Afterwards the table is what one count would have made it (``features`` reads
         the rows from the shuffled words as usual)."""
         L = _lib.load()
-        valid_ptr = table_plane.data_ptr()
-        window, vsize = int(emit[0]), int(emit[1])
         n_words = word_end - word_begin
-        ranges = [(w0, min(word_end, w0 + piece_words)) for w0 in range(word_begin, word_end, piece_words)]
-        slack = (lambda n: n + n // 32 + 4096)
-        kept = []
         sp = _stream_ptr(self.device)
+
+        def count(w0, w1, first, last, plan_ws, rec_ws, merge_ws):
+            _lib.check(L.pg_mini_count_piece(stream.codes.data_ptr(), table_plane.data_ptr(), w0, w1, self.desc(), rows_ref, plan_ws.data_ptr(), plan_ws.numel(),
+                                             rec_ws.data_ptr(), rec_ws.numel(), window, vsize, merge_ws.data_ptr(), merge_ws.numel(),
+                                             first, self.status.data_ptr(), sp))
+
+        def lookup(piece, sws):
+            _lib.check(L.pg_mini_lookup_piece(self.desc(), rows_ref, piece.plan_ws.data_ptr(), piece.plan_ws.numel(), piece.n_words, piece.meta.data_ptr(),
+                                              n_words, window, vsize, sws.data_ptr(), sws.numel(), piece.merge_ws.data_ptr(), self.status.data_ptr(), sp))
+
         with torch.cuda.device(self.device):
-            rec_ws = None
-            for idx, (w0, w1) in enumerate(ranges):
-                need = _lib.check(L.pg_mini_plan_bytes(w1 - w0, self.desc()))
-                plan_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), sp))
-                head = plan_ws[:24].view(torch.int64).cpu()                 # (host wait, once per piece: records, -, long records)
-                n_records, n_long = int(head[0]), int(head[2])
-                need = _lib.check(L.pg_mini_records_bytes(slack(n_records), self.desc()))
-                if rec_ws is None or rec_ws.numel() < need:
-                    rec_ws = None
-                    rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                need = _lib.check(L.pg_mini_merge_words(w1 - w0, n_records, n_long, self.desc()))
-                merge_ws = torch.empty(need, dtype=torch.int32, device=self.device)
-                _lib.check(L.pg_mini_count_piece(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(),
-                                                 rec_ws.data_ptr(), rec_ws.numel(), window, vsize, merge_ws.data_ptr(), merge_ws.numel(),
-                                                 1 if idx == 0 else 0, self.status.data_ptr(), sp))
-                # the bucket-ordered records' meta words (lengths, rows): the second meta plane of [bases A | bases B | meta A | meta B]
-                moff = _lib.check(L.pg_mini_records_meta_offset(rec_ws.numel(), self.desc()))
-                meta = rec_ws[moff: moff + 4 * n_records].view(torch.int32).clone()
-                kept.append((plan_ws, merge_ws, meta, w1 - w0))
-            rec_ws = None
-            need = _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, keep.n_rows, vsize, self.desc()))
-            if self._shuffle_ws is None or self._shuffle_ws.numel() < need:
-                self._shuffle_ws = None
-                self._shuffle_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            sws = self._shuffle_ws
-            _lib.check(L.pg_mini_lookup_begin(self.desc(), rows_arg(keep), n_words, vsize, sws.data_ptr(), sws.numel(), sp))
-            for plan_ws, merge_ws, meta, nw in kept:
-                _lib.check(L.pg_mini_lookup_piece(self.desc(), rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), nw, meta.data_ptr(), n_words, window, vsize,
-                                                  sws.data_ptr(), sws.numel(), merge_ws.data_ptr(), self.status.data_ptr(), sp))
-            # (``abundance_from_records`` hands a plan workspace of the whole range to pg_mini_abundance_from_emitted, which only checks its size)
-            whole = torch.empty(_lib.check(L.pg_mini_plan_bytes(n_words, self.desc())), dtype=torch.uint8, device=self.device)
-        self._mini_plan = (("pieces", len(ranges)), whole, sum(int(m.numel()) for _, _, m, _ in kept), keep, (stream.codes, table_plane), 0)
-        self._mini_pieces = len(ranges)
-        self._mini_optimistic = None
-        self._empty = False
-        self._records = (keep, n_words)
-        self._emitted = (window, vsize)
+            kept = self._count_pieces(stream, word_begin, word_end, piece_words, table_plane, None, rows_ref, count)
+        self._lookup_pieces(kept, keep, (stream.codes, table_plane), n_words, window, vsize, rows_ref, lookup)
         if check:
             self.check_status()
         return self
 
-    def _half_piece_words(self, n_words: int, keep: "Plan", vsize: int):
-        """``_piece_words`` for a count half (N > 1 ranks): None (one piece) or the words per piece.  PANGAEA_MINI_PIECE_WORDS forces
-        a piece size as on one GPU; otherwise ``half_piece_words`` decides from the free device memory, to which the workspaces this
-        table holds from an earlier count are added back (they are reused or replaced)."""
-        L = _lib.load()
-        if (self.kind != "mini" or self.n_buckets <= 256 or os.environ.get("PG_MINI_MERGE", "1") in ("", "0")
-                or _lib.check(L.pg_mini_merge_form_applies(self.desc(), keep.n_rows, vsize)) != 1):
-            return None                                          # (the pieces' kernels: packed slots, both scatter passes, the merged lookups)
-        forced = os.environ.get("PANGAEA_MINI_PIECE_WORDS")
-        if forced:
-            w = max(_lib.WORD_ALIGN, int(forced) // _lib.WORD_ALIGN * _lib.WORD_ALIGN)
-            return w if w < n_words else None
-        free, _ = torch.cuda.mem_get_info(self.device)
-        free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)      # (cached blocks count as free)
-        held = [self._mini_rec_ws, self._shuffle_ws, self._merge_ws, self._half_ws] + ([self.data] if self.data.numel() > 1 else [])
-        free += sum(int(t.numel()) * t.element_size() for t in held if t is not None)
-        w = half_piece_words(free, n_words, self.log2_slots, self.log2_bucket, keep.n_rows, getattr(self, "_half_world", 1))
-        return w if w is not None and w < n_words else None
-
-    def _count_half_pieces(self, stream, word_begin, word_end, table_plane, keep, rows_arg, emit, piece_words, check, tab_plane=None):
+    def _count_half_pieces(self, stream, word_begin, word_end, table_plane, keep, rows_ref, window, vsize, piece_words, check, tab_plane=None):
         """the count half (``count_half``) of a stream counted in word ranges of ``piece_words`` (include/pangaea_feat.h:
         pg_mini_count_half_piece): every piece -> its plan, both scatter passes, the count INTO this table's own slots (allocated
         here: 8 bytes x 2^log2_slots), its 2-byte provisional slots and its records' meta words kept; the last piece leaves entries,
         occupancy and fill as one count half does.  ``lookup_half`` then looks every piece up with the bins the owners sent back."""
-        L = _lib.load()
-        valid_ptr = table_plane.data_ptr()
-        window, vsize = int(emit[0]), int(emit[1])
-        n_words = word_end - word_begin
-        ranges = [(w0, min(word_end, w0 + piece_words)) for w0 in range(word_begin, word_end, piece_words)]
-        slack = (lambda n: n + n // 32 + 4096)
         sp = _stream_ptr(self.device)
         if self.data.numel() != 1 << self.log2_slots:            # (the slots the pieces count into: every slot is written by the first piece)
             self.data = torch.empty(1 << self.log2_slots, dtype=torch.int64, device=self.device)
@@ -647,53 +689,19 @@ class KmerTable:
         # (the one-piece workspaces are not used on this path: their memory goes back to the allocator)
         self._mini_rec_ws = self._merge_ws = None
         self._mini_plan = None
-        kept = []
         with torch.cuda.device(self.device):
-            need = _lib.check(L.pg_mini_half_bytes(self.desc()))
-            if self._half_ws is None or self._half_ws.numel() != need:
-                self._half_ws = None
-                self._half_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            fill = torch.zeros(self.n_buckets, dtype=torch.int64, device=self.device)
-            rec_ws = None
-            for idx, (w0, w1) in enumerate(ranges):
-                need = _lib.check(L.pg_mini_plan_bytes(w1 - w0, self.desc()))
-                plan_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                if tab_plane is not None:
-                    _lib.check(L.pg_mini_plan_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), w0, w1, self.desc(), rows_arg(keep),
-                                                     plan_ws.data_ptr(), plan_ws.numel(), sp))
-                else:
-                    _lib.check(L.pg_mini_plan(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep), plan_ws.data_ptr(), plan_ws.numel(), sp))
-                head = plan_ws[:24].view(torch.int64).cpu()                 # (host wait, once per piece: records, -, long records)
-                n_records, n_long = int(head[0]), int(head[2])
-                need = _lib.check(L.pg_mini_records_bytes(slack(n_records), self.desc()))
-                if rec_ws is None or rec_ws.numel() < need:
-                    rec_ws = None
-                    rec_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-                need = _lib.check(L.pg_mini_merge_words(w1 - w0, n_records, n_long, self.desc()))
-                merge_ws = torch.empty(need, dtype=torch.int32, device=self.device)
-                if tab_plane is not None:
-                    _lib.check(L.pg_mini_count_half_piece_masked(stream.codes.data_ptr(), valid_ptr, tab_plane.data_ptr(), w0, w1, self.desc(), rows_arg(keep),
-                                                                 plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
-                                                                 merge_ws.data_ptr(), merge_ws.numel(), self._half_ws.data_ptr(), self._half_ws.numel(),
-                                                                 fill.data_ptr(), 1 if idx == 0 else 0, 1 if idx == len(ranges) - 1 else 0,
-                                                                 self.status.data_ptr(), sp))
-                else:
-                    _lib.check(L.pg_mini_count_half_piece(stream.codes.data_ptr(), valid_ptr, w0, w1, self.desc(), rows_arg(keep),
-                                                          plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
-                                                          merge_ws.data_ptr(), merge_ws.numel(), self._half_ws.data_ptr(), self._half_ws.numel(),
-                                                          fill.data_ptr(), 1 if idx == 0 else 0, 1 if idx == len(ranges) - 1 else 0,
-                                                          self.status.data_ptr(), sp))
-                moff = _lib.check(L.pg_mini_records_meta_offset(rec_ws.numel(), self.desc()))
-                meta = rec_ws[moff: moff + 4 * n_records].view(torch.int32).clone()
-                kept.append((plan_ws, merge_ws, meta, w1 - w0))
-            rec_ws = None
-        self._half = (fill, n_words, keep, window, vsize)
+            half_ws, fill = self._half_workspaces()
+
+            def count(w0, w1, first, last, plan_ws, rec_ws, merge_ws):
+                _plain_or_masked("pg_mini_count_half_piece", stream, table_plane, tab_plane, w0, w1, self.desc(), rows_ref,
+                                 plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
+                                 merge_ws.data_ptr(), merge_ws.numel(), half_ws.data_ptr(), half_ws.numel(),
+                                 fill.data_ptr(), first, last, self.status.data_ptr(), sp)
+
+            kept = self._count_pieces(stream, word_begin, word_end, piece_words, table_plane, tab_plane, rows_ref, count)
+        self._half = _Half(fill, word_end - word_begin, keep, window, vsize)
         self._half_pieces = (kept, (stream.codes, table_plane) + (() if tab_plane is None else (tab_plane, stream.valid)))
-        self._mini_pieces = len(ranges)
-        self._mini_optimistic = None
-        self._empty = False
-        self._records = None
-        self._emitted = None
+        self._records = self._emitted = None
         if check:
             self.check_status()
         return self
@@ -701,66 +709,53 @@ class KmerTable:
     def plan_counts(self) -> tuple:
         """(records, records of more than four k-mers) of the partition plan in use -- read from the device on first use (a plan
         picked up without a host wait keeps them there)"""
-        key, ws, n_records, keep, held, n_long = self._mini_plan
-        if n_records is None:
-            head = ws[:24].view(torch.int64).cpu()
-            n_records, n_long = int(head[0]), int(head[2])
-            self._mini_plan = (key, ws, n_records, keep, held, n_long)
-        return n_records, n_long
+        plan = self._mini_plan
+        if plan.n_records is None:
+            n_records, n_long = _plan_head(plan.ws)
+            plan = self._mini_plan = plan._replace(n_records=n_records, n_long=n_long)
+        return plan.n_records, plan.n_long
 
     def lookup_half(self, bins: torch.Tensor, bin_elem: torch.Tensor) -> None:
         """N > 1 ranks: finish a ``count_half`` -- ``bins`` (int16 view of what the bucket owners sent back: bin + 1 of every entry in
         the merged table, in the order the entries were sent), ``bin_elem[b]`` = where bucket b's bins start -- lookups of the
-        provisional words and the row-group scatter; ``features`` then reads the rows from the shuffled words"""
-        fill, n_words, keep, window, vsize = self._half
+        provisional words and the row-group scatter; ``features`` then reads the rows from the shuffled words.
+
+        After a count half in pieces every piece's provisional slots are looked up with the bins, and the pieces stay kept: an
+        exchange done again (``MiniSharded.count`` after PG_STATUS_OVERFLOW_LIST) is looked up again without a recount."""
+        half = self._half
         assert bins.dtype == torch.int16 and bin_elem.dtype == torch.int64 and bin_elem.numel() == self.n_buckets
         L = _lib.load()
-        if getattr(self, "_half_pieces", None) is not None:
-            self._lookup_half_pieces(bins, bin_elem)
-            return
-        plan_ws = self._mini_plan[1]
-        with torch.cuda.device(self.device):
-            _lib.check(L.pg_mini_lookup_half(self.desc(), C.byref(keep.rows_desc), plan_ws.data_ptr(), plan_ws.numel(),
-                                             self._mini_rec_ws.data_ptr(), self._mini_rec_ws.numel(), n_words, vsize,
-                                             self._shuffle_ws.data_ptr(), self._shuffle_ws.numel(),
-                                             self._merge_ws.data_ptr() if getattr(self, "_merge_ws", None) is not None else None,
-                                             self._merge_ws.numel() if getattr(self, "_merge_ws", None) is not None else 0,
-                                             self._half_ws.data_ptr(), self._half_ws.numel(),
-                                             bins.data_ptr(), bin_elem.data_ptr(), self.status.data_ptr(), _stream_ptr(self.device)))
-        self._records = (keep, n_words)
-        self._emitted = (window, vsize)
-        self._half = None
-
-    def _lookup_half_pieces(self, bins: torch.Tensor, bin_elem: torch.Tensor) -> None:
-        """``lookup_half`` after a count half in pieces: the row shuffle's regions of the whole stream prepared once, then every
-        piece's provisional slots looked up with the bins.  The pieces stay kept: an exchange done again (``MiniSharded.count`` after
-        PG_STATUS_OVERFLOW_LIST) is looked up again without a recount."""
-        fill, n_words, keep, window, vsize = self._half
-        kept, held = self._half_pieces
-        L = _lib.load()
         sp = _stream_ptr(self.device)
+        rows_ref = C.byref(half.rows.rows_desc)
+        half_ws = self._half_ws
+        if self._half_pieces is not None:
+            pieces, held = self._half_pieces
+
+            def lookup(piece, sws):
+                _lib.check(L.pg_mini_lookup_half_piece(self.desc(), rows_ref, piece.plan_ws.data_ptr(), piece.plan_ws.numel(), piece.n_words,
+                                                       piece.meta.data_ptr(), half.n_words, half.vsize, sws.data_ptr(), sws.numel(),
+                                                       piece.merge_ws.data_ptr(), half_ws.data_ptr(), half_ws.numel(), bins.data_ptr(),
+                                                       bin_elem.data_ptr(), self.status.data_ptr(), sp))
+
+            self._lookup_pieces(pieces, half.rows, held, half.n_words, half.window, half.vsize, rows_ref, lookup)
+            return
+        plan_ws = self._mini_plan.ws
         with torch.cuda.device(self.device):
-            need = _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, keep.n_rows, vsize, self.desc()))
-            if self._shuffle_ws is None or self._shuffle_ws.numel() < need:
-                self._shuffle_ws = None
-                self._shuffle_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-            sws = self._shuffle_ws
-            _lib.check(L.pg_mini_lookup_begin(self.desc(), C.byref(keep.rows_desc), n_words, vsize, sws.data_ptr(), sws.numel(), sp))
-            for plan_ws, merge_ws, meta, nw in kept:
-                _lib.check(L.pg_mini_lookup_half_piece(self.desc(), C.byref(keep.rows_desc), plan_ws.data_ptr(), plan_ws.numel(), nw, meta.data_ptr(),
-                                                       n_words, vsize, sws.data_ptr(), sws.numel(), merge_ws.data_ptr(),
-                                                       self._half_ws.data_ptr(), self._half_ws.numel(), bins.data_ptr(), bin_elem.data_ptr(),
-                                                       self.status.data_ptr(), sp))
-            # (``abundance_from_records`` hands a plan workspace of the whole range to pg_mini_abundance_from_emitted, which only checks its size)
-            whole = torch.empty(_lib.check(L.pg_mini_plan_bytes(n_words, self.desc())), dtype=torch.uint8, device=self.device)
-        self._mini_plan = (("pieces", len(kept)), whole, sum(int(m.numel()) for _, _, m, _ in kept), keep, held, 0)
-        self._records = (keep, n_words)
-        self._emitted = (window, vsize)
+            _lib.check(L.pg_mini_lookup_half(self.desc(), rows_ref, plan_ws.data_ptr(), plan_ws.numel(),
+                                             self._mini_rec_ws.data_ptr(), self._mini_rec_ws.numel(), half.n_words, half.vsize,
+                                             self._shuffle_ws.data_ptr(), self._shuffle_ws.numel(),
+                                             self._merge_ws.data_ptr() if self._merge_ws is not None else None,
+                                             self._merge_ws.numel() if self._merge_ws is not None else 0,
+                                             half_ws.data_ptr(), half_ws.numel(),
+                                             bins.data_ptr(), bin_elem.data_ptr(), self.status.data_ptr(), sp))
+        self._records = (half.rows, half.n_words)
+        self._emitted = (half.window, half.vsize)
+        self._half = None
 
     def can_reexchange(self) -> bool:
         """does this table still hold what the exchange sends (a count half in pieces keeps its entries, fills and pieces until
         the next count)?"""
-        return self._half is not None and getattr(self, "_half_pieces", None) is not None
+        return self._half is not None and self._half_pieces is not None
 
     def prefetch_plan(self, stream: ReadStream, rows: "Plan | None", side: "torch.cuda.Stream",
                       after: "torch.cuda.Event | None" = None) -> None:
@@ -800,7 +795,7 @@ class KmerTable:
             event = torch.cuda.Event()
             event.record(side)
         ws.record_stream(side)
-        self._mini_next = (key, ws, event, keep, (stream.codes, stream.valid))
+        self._mini_next = _MiniNext(key, ws, event, keep, (stream.codes, stream.valid))
 
     def can_shuffle(self, plan: "Plan", window: int, vsize: int) -> bool:
         """can ``abundance_from_records`` build the rows of this plan (instead of table lookups)?"""
@@ -819,7 +814,7 @@ class KmerTable:
         n_words = self._records[1]
         L = _lib.load()
         if self.kind in ("mini", "miniw"):
-            plan_ws = self._mini_plan[1]
+            plan_ws = self._mini_plan.ws
             with torch.cuda.device(self.device):
                 _lib.check(L.pg_mini_abundance_from_emitted(self.desc(), C.byref(plan.rows_desc), vsize, out.data_ptr(), plan_ws.data_ptr(),
                                                             plan_ws.numel(), n_words, self._shuffle_ws.data_ptr(), self._shuffle_ws.numel(),
@@ -855,19 +850,18 @@ class KmerTable:
         if st & _lib.STATUS_BOUNDS:
             raise RuntimeError("a kernel of the checked build was about to store outside its buffer (PG_STATUS_BOUNDS): the results are incomplete")
         if st & _lib.STATUS_PLAN_MISMATCH:
-            again = getattr(self, "_mini_optimistic", None)
+            again = self._mini_optimistic
             if again is not None and self._mini_plan is not None:
                 # the count ran on the previous batch's workspaces without waiting for its plan's record counts, and this batch has
                 # more records than they hold: nothing was written -- read the counts, size the workspaces, count again
                 self._mini_optimistic = None
-                stream, word_begin, word_end, rows, emit, half = again
                 self.status.zero_()
                 self.plan_counts()
                 self._empty = True
-                if half:
-                    self.count_half(stream, rows, emit, check=False)
+                if again.half:
+                    self.count_half(again.stream, again.rows, again.emit, check=False)
                 else:
-                    self.count(stream, word_begin, word_end, check=False, rows=rows, emit=emit)
+                    self.count(again.stream, again.word_begin, again.word_end, check=False, rows=again.rows, emit=again.emit)
                 return self.check_status()
             self._mini_plan = None
             raise RuntimeError("the partition plan did not describe this stream (PG_STATUS_PLAN_MISMATCH): nothing was counted")

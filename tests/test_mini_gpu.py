@@ -507,6 +507,6 @@ def test_a_plan_of_another_stream_is_not_reused_and_a_forced_one_is_refused(monk
     u = kmer.KmerTable.mini_with_slots(21, DEV, 20, 10).count(small_padded)
     monkeypatch.setattr(kmer.KmerTable, "_plan_key", staticmethod(lambda *a_, **k_: "always the same"))
     u.reset()
-    u._mini_plan = ("always the same",) + tuple(u._mini_plan[1:])
+    u._mini_plan = u._mini_plan._replace(key="always the same")
     with pytest.raises(RuntimeError, match="PLAN_MISMATCH"):
         u.count(a)
