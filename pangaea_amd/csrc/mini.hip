@@ -834,9 +834,6 @@ __device__ __forceinline__ uint32_t mini_lookup_slow(const unsigned long long *t
     return res;
 }
 
-#ifndef PG_SHORT_MAX
-#define PG_SHORT_MAX 4
-#endif
 // where the SLOTS form scatters its (row, bin) words: straight into the row shuffle's group regions (pg_shuffle_ctx)
 struct ShufArgs {
     const unsigned long long *goff;
@@ -2267,6 +2264,8 @@ int mini_cap(int k)
     if (forced >= 1 && forced < cap) cap = forced;
     return cap;
 }
+// the cap the bucket kernels are instantiated for (cap <= W <= 9: see mini_cap)
+constexpr int cap_class(int cap) { return cap <= 4 ? 4 : cap <= 6 ? 6 : cap <= 8 ? 8 : 9; }
 
 int check_mini(const pg_table *t, const char *who)
 {
@@ -2315,15 +2314,50 @@ int plan_mini(const pg_table *t, int64_t n_words, MiniPlan *p)
     return PG_OK;
 }
 
-MiniView mini_view(const pg_table *t)
+// ---- one view per workspace: typed pointers, built by the one function that knows the layout and checks size and alignment (`who`:
+// the entry point, for the message).  The const flavours serve the lookup entries, which read what a count left: they check the size only.
+template <bool CONST, class T> using ws_ptr = std::conditional_t<CONST, const T, T> *;
+bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 255) != 0; }
+
+template <bool CONST> struct PlanViewT : MiniPlan {
+    using Words = ws_ptr<CONST, unsigned long long>;
+    Words header, region_tot, region_off, off, hist, cur2, cur2l, kwords, wbeg, chunk_tab;       // (header first; hist | cur2 | cur2l | kwords in a row)
+    ws_ptr<CONST, int32_t> round_row;
+    // short records per bucket, where the classes are sorted apart (the second scatter pass does that: without it -- at most 256
+    // buckets -- every record counts as long)
+    const unsigned long long *n_short(int k) const { return bits2 && mini_cap(k) > SHORT_MAX ? cur2 : nullptr; }
+};
+using PlanView = PlanViewT<false>; using ConstPlanView = PlanViewT<true>;
+
+// false: plan_ws_bytes are too few for the plan of n_words words (nothing is carved then)
+template <bool CONST> bool plan_carve(const pg_table *t, int64_t n_words, ws_ptr<CONST, void> plan_ws, int64_t plan_ws_bytes, PlanViewT<CONST> *v)
 {
-    MiniView v;
-    v.slots = (uint64_t *)t->data;
-    v.log2_slots = t->log2_slots;
-    v.log2_bucket = t->log2_bucket_slots;
-    v.k = t->k;
-    return v;
+    plan_mini(t, n_words, v);
+    if ((int64_t)v->total > plan_ws_bytes) return false;
+    const auto ws = (ws_ptr<CONST, char>)plan_ws;
+    auto words = [&](size_t at) { return (typename PlanViewT<CONST>::Words)(ws + at); };
+    v->header = words(v->header_off); v->region_tot = words(v->rtot_off); v->region_off = words(v->roff_off); v->off = words(v->off_off);
+    v->hist = words(v->hist_off); v->cur2 = words(v->cur2_off); v->cur2l = words(v->cur2l_off); v->kwords = words(v->kw_off);
+    v->wbeg = words(v->wbeg_off); v->chunk_tab = words(v->chunk_off); v->round_row = (ws_ptr<CONST, int32_t>)(ws + v->round_off);
+    return true;
 }
+
+// the workspace a plan or a count writes.  several: the entry point takes other workspaces too, and its messages say so
+int plan_view(const pg_table *t, int64_t n_words, void *plan_ws, int64_t plan_ws_bytes, const char *who, bool several, PlanView *v)
+{
+    if (!plan_carve(t, n_words, plan_ws, plan_ws_bytes, v))
+        return pg_fail(PG_EINVAL, several ? "%s: plan workspace of %lld bytes, %lld needed" : "%s: workspace of %lld bytes, %lld needed", who, (long long)plan_ws_bytes, (long long)v->total);
+    if (misaligned(plan_ws)) return pg_fail(PG_EINVAL, several ? "%s: workspaces must be 256-byte aligned" : "%s: workspace must be 256-byte aligned", who);
+    return PG_OK;
+}
+
+// the workspace as a count left it.  n_words_name: what the entry point calls the word count the plan was made for
+int plan_view(const pg_table *t, int64_t n_words, const void *plan_ws, int64_t plan_ws_bytes, const char *who, const char *n_words_name, ConstPlanView *v)
+{
+    return plan_carve(t, n_words, plan_ws, plan_ws_bytes, v) ? PG_OK : pg_fail(PG_EINVAL, "%s: plan workspace does not match %s", who, n_words_name);
+}
+
+MiniView mini_view(const pg_table *t) { return MiniView{(uint64_t *)t->data, t->log2_slots, t->log2_bucket_slots, t->k}; }
 
 // the SLOTS form of the lookups needs a row and a slot index in one 32-bit word (PG_MINI_PROBE_TWICE forces the general form)
 // row groups that the count kernel's own scatter reaches in one pass: 2^11 (131 072 rows; 2048 digits in its lookup tiles)
@@ -2348,22 +2382,65 @@ bool mini_merge_form(const pg_table *t, const pg_rows *rows, int vsize)
     return vbits + 6 + gbits <= MERGE_CSHIFT;
 }
 
-// the record workspace: [bases A | bases B | meta A | meta B] of `cap` records each
-struct MiniRecLayout { size_t cap, total; };
-MiniRecLayout mini_rec_layout(size_t cap, size_t)
+// the record workspace: [bases A | bases B | meta A | meta B] of `cap` records each (8-byte bases, 4-byte meta words)
+struct MiniRecLayout { size_t cap, bases_b_off, meta_a_off, meta_b_off, total; };
+MiniRecLayout mini_rec_layout(size_t cap)
 {
-    return MiniRecLayout{cap, 24 * cap};
+    return MiniRecLayout{cap, 8 * cap, 16 * cap, 20 * cap, 24 * cap};
 }
 
 // the largest record capacity (a multiple of 256) whose layout fits a workspace of that many bytes
-size_t mini_rec_cap(int64_t rec_ws_bytes, size_t nb)
+size_t mini_rec_cap(int64_t rec_ws_bytes)
 {
     size_t cap = 0;
     if (rec_ws_bytes > 0) {
         cap = (size_t)rec_ws_bytes / 24 / 256 * 256;
-        while (cap >= 256 && mini_rec_layout(cap, nb).total > (size_t)rec_ws_bytes) cap -= 256;
+        while (cap >= 256 && mini_rec_layout(cap).total > (size_t)rec_ws_bytes) cap -= 256;
     }
     return cap;
+}
+
+template <bool CONST> struct RecViewT { size_t cap; ws_ptr<CONST, uint64_t> bases_a, bases_b; ws_ptr<CONST, uint32_t> meta_a, meta_b; };
+using RecView = RecViewT<false>; using ConstRecView = RecViewT<true>;
+template <bool CONST> int rec_view(ws_ptr<CONST, void> rec_ws, int64_t rec_ws_bytes, const char *who, RecViewT<CONST> *v)
+{
+    if (!CONST && misaligned(rec_ws)) return pg_fail(PG_EINVAL, "%s: workspaces must be 256-byte aligned", who);
+    const MiniRecLayout l = mini_rec_layout(mini_rec_cap(rec_ws_bytes));
+    if (l.cap < 256) return pg_fail(PG_EINVAL, "%s: record workspace of %lld bytes (pg_mini_records_bytes)", who, (long long)rec_ws_bytes);
+    const auto ws = (ws_ptr<CONST, char>)rec_ws;
+    v->cap = l.cap; v->bases_a = (ws_ptr<CONST, uint64_t>)ws; v->bases_b = (ws_ptr<CONST, uint64_t>)(ws + l.bases_b_off);
+    v->meta_a = (ws_ptr<CONST, uint32_t>)(ws + l.meta_a_off); v->meta_b = (ws_ptr<CONST, uint32_t>)(ws + l.meta_b_off);
+    return PG_OK;
+}
+
+// workspace of the count half (N > 1 ranks, see the kernels above): entry slabs | occupancy bitmaps | ring counts
+struct MiniHalfLayout { size_t ent_off, occ_off, ring_off, total; };
+MiniHalfLayout mini_half_layout(const pg_table *t)
+{
+    const size_t nb = (size_t)1 << (t->log2_slots - t->log2_bucket_slots), n_slots = (size_t)1 << t->log2_bucket_slots;
+    const size_t n_occ = n_slots >= 64 ? n_slots / 64 : 1;
+    MiniHalfLayout l;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
+    l.ent_off = take(nb * n_slots * 8);
+    l.occ_off = take(nb * n_occ * 8);
+    l.ring_off = take(nb * 4);
+    l.total = o;
+    return l;
+}
+
+template <bool CONST> struct HalfViewT { ws_ptr<CONST, unsigned long long> ent, occ; ws_ptr<CONST, uint32_t> ring; };
+using HalfView = HalfViewT<false>; using ConstHalfView = HalfViewT<true>;
+template <bool CONST> int half_view(const pg_table *local, ws_ptr<CONST, void> half_ws, int64_t half_ws_bytes, const char *who, HalfViewT<CONST> *v)
+{
+    const MiniHalfLayout l = mini_half_layout(local);
+    if (CONST && (int64_t)l.total > half_ws_bytes) return pg_fail(PG_EINVAL, "%s: workspace does not match the table", who);
+    if (!CONST && ((int64_t)l.total > half_ws_bytes || misaligned(half_ws)))
+        return pg_fail(PG_EINVAL, "%s: workspace of %lld bytes (256-byte aligned), %lld needed", who, (long long)half_ws_bytes, (long long)l.total);
+    const auto ws = (ws_ptr<CONST, char>)half_ws;
+    v->ent = (ws_ptr<CONST, unsigned long long>)(ws + l.ent_off); v->occ = (ws_ptr<CONST, unsigned long long>)(ws + l.occ_off);
+    v->ring = (ws_ptr<CONST, uint32_t>)(ws + l.ring_off);
+    return PG_OK;
 }
 
 int check_mini_rows(const pg_rows *rows, const char *who)
@@ -2371,6 +2448,156 @@ int check_mini_rows(const pg_rows *rows, const char *who)
     if (!rows) return PG_OK;
     if (rows->n_rows < 0 || rows->n_rows > PG_MINI_MAX_ROWS) return pg_fail(PG_EINVAL, "%s: %lld rows (at most %d per launch)", who, (long long)rows->n_rows, PG_MINI_MAX_ROWS);
     if (rows->n_rows > 0 && (!rows->row_start || !rows->row_end)) return pg_fail(PG_EINVAL, "%s: null row arrays", who);
+    return PG_OK;
+}
+
+// ---- typed dispatch: a runtime value becomes a compile-time tag, and the generic lambda `f` is called with the tag of the one
+// case that applies.  Every helper lists exactly the cases that have kernels: f is instantiated for those and no others.
+template <int N> using int_tag = std::integral_constant<int, N>;
+
+// the first-pass kernels are instantiated per window length (registers of the rolling minimum); k > 21 runs the delayed
+// central window of 8 or 9 M-mers (mini_window).  f(WindowTag<W, DELAY, M>, woff)
+template <int W_, bool DELAY_, int M_> struct WindowTag { static constexpr int W = W_, M = M_; static constexpr bool DELAY = DELAY_; };
+template <class F> int with_window(int k, F &&f)
+{
+    int wc, woff;
+    mini_window(k, &wc, &woff);
+    if (k > PG_HASH_MAX_K) return wc == 8 ? f(WindowTag<8, true, MINI_M>{}, woff) : f(WindowTag<9, true, MINI_M>{}, woff);
+    if (mini_m(k) == MINI_M_SMALL)
+        return wc == 3 ? f(WindowTag<3, false, MINI_M_SMALL>{}, woff) : wc == 4 ? f(WindowTag<4, false, MINI_M_SMALL>{}, woff) : f(WindowTag<5, false, MINI_M_SMALL>{}, woff);
+    switch (wc) {
+    case 4: return f(WindowTag<4, false, MINI_M>{}, woff);
+    case 5: return f(WindowTag<5, false, MINI_M>{}, woff);
+    case 6: return f(WindowTag<6, false, MINI_M>{}, woff);
+    case 7: return f(WindowTag<7, false, MINI_M>{}, woff);
+    case 8: return f(WindowTag<8, false, MINI_M>{}, woff);
+    default: return f(WindowTag<9, false, MINI_M>{}, woff);
+    }
+}
+
+// k-mers per record at most (as the first pass cuts them): f(int_tag<4 | 6 | 8 | 9>)
+template <class F> int with_cap(int cap, F &&f)
+{
+    const int c = cap_class(cap);
+    return c == 4 ? f(int_tag<4>{}) : c == 6 ? f(int_tag<6>{}) : c == 8 ? f(int_tag<8>{}) : f(int_tag<9>{});
+}
+
+// the MASKED twin of a kernel or its plain form: f(std::true_type | std::false_type)
+template <class F> int with_flag(bool on, F &&f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+
+// threads and row-group digits of a lookup workgroup (LookupLds / MergeLds): f(GeomTag<BLK, DIG>) for the three that exist
+template <int BLK_, int DIG_> struct GeomTag { static constexpr int BLK = BLK_, DIG = DIG_; };
+template <class F> auto with_lookup_geom(int blk, int dig, F &&f)
+{
+    return dig == 2048 ? f(GeomTag<BIG_BLOCK, 2048>{}) : blk == 512 ? f(GeomTag<512, 1024>{}) : f(GeomTag<BIG_BLOCK, 1024>{});
+}
+
+// raises the kernel's dynamic LDS limit where `lds` needs it, then enqueues it (the arguments convert to the kernel's parameter types)
+template <class... P, class... A>
+int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const char *who, const A &...args)
+{
+    if (int rc = raise_lds_limit((const void *)kernel, lds, who)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(args)...);
+    return PG_OK;
+}
+
+// (the kernel's SLOTS, WIDE, MERGE, HALF, MASKED; threads of a workgroup, row-group digits of its lookup tiles; dynamic LDS)
+struct CountForm { bool slots, wide, merge, half, masked; int blk, dig; size_t lds; };
+// slots / merge: mini_slots_form / mini_merge_form hold and the lookups are wanted; half: any of the count halves (N > 1 ranks, or a
+// piece of a stream); gb1: first-pass digits of the row shuffle the lookups scatter into (0 where the launch does none)
+CountForm count_form(const pg_table *t, const pg_rows *rows, bool slots, bool merge, bool half, bool masked, int gb1)
+{
+    CountForm f{slots, t->kind == PG_TABLE_MINI_WIDE, merge, half, masked, 0, 0, 0};
+    const size_t table_lds = (size_t)(f.wide ? 12 : 8) << t->log2_bucket_slots;          // (wide: 8-byte keys + 4-byte counts per slot)
+    // Buckets of at most 2^13 8-byte slots (64 KiB): 512-thread workgroups, TWO per CU -- one can be in its count loop (VALU, waits)
+    // while the other is in its lookup phase (LDS throughput).  PG_COUNT_BLOCK=1024: the one-workgroup form for such tables too.
+    const char *blk_env = getenv("PG_COUNT_BLOCK");
+    const bool many_groups = slots && rows->n_rows > ((int64_t)1 << (PG_SHUFFLE_ONE_PASS_BITS + 6));     // more than 2^10 row groups: 2048 digits
+    // (the count half does no lookups: the row-group digits do not matter to its geometry)
+    const bool two_per_cu = !f.wide && slots && t->log2_bucket_slots <= 13 && (!many_groups || half) && !(blk_env && atoi(blk_env) == 1024);
+    f.blk = two_per_cu ? 512 : BIG_BLOCK;
+    f.dig = !half && !two_per_cu && gb1 > 10 ? 2048 : 1024;
+    f.lds = table_lds + (size_t)(two_per_cu ? 512 / 64 : COUNT_WAVES) * RING * 12;      // table + the wavefronts' rings
+    // the count kernel scatters its words into the row shuffle's group regions itself: its lookup phase (the table has become 2-byte bins by then) may need more
+    if (slots && !half)
+        f.lds = std::max(f.lds, with_lookup_geom(f.blk, f.dig, [&](auto g) { using G = decltype(g); return merge ? (size_t)MergeLds<G::BLK, G::DIG>::END : (size_t)LookupLds<G::BLK, G::DIG>::END; }));
+    return f;
+}
+
+// calls f(kernel) if `c` is this instantiation
+template <int CAP, bool SLOTS, bool WIDE, int BLK, int DIG, bool MERGE, bool HALF, bool MASKED, class F>
+bool count_form_is(const CountForm &c, F &f, int *rc)
+{
+    if (c.slots != SLOTS || c.wide != WIDE || c.blk != BLK || c.dig != DIG || c.merge != MERGE || c.half != HALF || c.masked != MASKED) return false;
+    *rc = f(mini_count_kernel<CAP, SLOTS, WIDE, BLK, DIG, MERGE, HALF, MASKED>);
+    return true;
+}
+
+// every mini_count_kernel there is (for each of the four caps): f(kernel) for the one that `c` names
+template <int CAP, class F> int with_count_kernel(const CountForm &c, F f)
+{
+    int rc = PG_OK;
+    const bool found =
+        //                 SLOTS  WIDE   BLK   DIG   MERGE  HALF   MASKED
+        // the general form (no lookups, or a row and a slot index do not fit one word): packed and wide tables
+        count_form_is<CAP, false, false, 1024, 1024, false, false, false>(c, f, &rc) ||
+        count_form_is<CAP, false, true,  1024, 1024, false, false, false>(c, f, &rc) ||
+        // one GPU, the slot form: word-wise or merged lookups; one workgroup per CU (1024 or, past 2^16 rows, 2048 digits) ...
+        count_form_is<CAP, true,  false, 1024, 1024, false, false, false>(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 1024, 1024, true,  false, false>(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 1024, 2048, false, false, false>(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 1024, 2048, true,  false, false>(c, f, &rc) ||
+        // ... or two per CU (buckets of at most 2^13 slots)
+        count_form_is<CAP, true,  false, 512,  1024, false, false, false>(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 512,  1024, true,  false, false>(c, f, &rc) ||
+        // the same on wide tables (one workgroup per CU only)
+        count_form_is<CAP, true,  true,  1024, 1024, false, false, false>(c, f, &rc) ||
+        count_form_is<CAP, true,  true,  1024, 1024, true,  false, false>(c, f, &rc) ||
+        count_form_is<CAP, true,  true,  1024, 2048, false, false, false>(c, f, &rc) ||
+        count_form_is<CAP, true,  true,  1024, 2048, true,  false, false>(c, f, &rc) ||
+        // the count half (N > 1 ranks, pieces): packed slots, no lookups of its own
+        count_form_is<CAP, true,  false, 1024, 1024, false, true,  false>(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 1024, 1024, true,  true,  false>(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 512,  1024, false, true,  false>(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 512,  1024, true,  true,  false>(c, f, &rc) ||
+        // the masked count half: merged only
+        count_form_is<CAP, true,  false, 1024, 1024, true,  true,  true >(c, f, &rc) ||
+        count_form_is<CAP, true,  false, 512,  1024, true,  true,  true >(c, f, &rc);
+    // (not reached: count_form and the checks in front of it give one of the forms above)
+    return found ? rc : pg_fail(PG_EINVAL, "pg_mini_count: no kernel of this form");
+}
+
+// threads and digits of the merged lookups that run as kernels of their own (a piece's, a count half's).  More than 2^10 row groups:
+// 2048 digits.  n_rank (the lookup half of N > 1 ranks) on buckets of at most 2^13 slots (what a rank's own reads need at 4+ ranks):
+// 512-thread workgroups, two per CU -- that kernel starts cold (bins, meta words and provisional slots all come from HBM, where
+// the one-GPU kernel's lookup phase finds them in L2), and a second workgroup on the CU hides what one alone waits for:
+// 7.8 -> 5.9 ms, rehearsed 8-rank step 34.3 -> 32.3 ms on one box (PG_LOOKUP_HALF_1024=1: the one-workgroup form)
+struct LookupGeom { int blk, dig; };
+LookupGeom merged_lookup_geom(const pg_table *t, int gb1, bool n_rank)
+{
+    return gb1 > 10 ? LookupGeom{BIG_BLOCK, 2048} : n_rank && t->log2_bucket_slots <= 13 && !getenv("PG_LOOKUP_HALF_1024") ? LookupGeom{512, 1024} : LookupGeom{BIG_BLOCK, 1024};
+}
+
+// ---- what the lookup entries share: the plan workspace as a count left it (n_words_plan words, which the entry point calls
+// n_words_name) and the row shuffle's regions for n_words_shuffle words.  merge: the merged lookups (no input buffer in the
+// shuffle's layout, counted 4-byte words); begun: pg_mini_lookup_begin has prepared offsets and cursors (the piece forms) -- a
+// further launch into them
+enum class Lookups { word_wise, merged };
+enum class Regions { prepare, begun };
+struct LookupPrep { ConstPlanView plan; pg_shuffle_ctx ctx; ShufArgs sh; const unsigned long long *n_short; unsigned nb; };
+int lookup_prepare(const pg_table *t, const pg_rows *rows, const void *plan_ws, int64_t plan_ws_bytes, int64_t n_words_plan, const char *n_words_name,
+                   int64_t n_words_shuffle, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *stream, Lookups form, Regions regions, const char *who, LookupPrep *l)
+{
+    int rc = plan_view(t, n_words_plan, plan_ws, plan_ws_bytes, who, n_words_name, &l->plan);
+    if (rc) return rc;
+    if (!l->plan.bits2) return pg_fail(PG_EINVAL, "%s: needs more than 256 buckets", who);
+    pg_shuffle_ctx &ctx = l->ctx;
+    const bool merge = form == Lookups::merged;
+    if ((rc = pg_internal_shuffle_prepare(n_words_shuffle * 32, rows, vsize, shuffle_ws, shuffle_ws_bytes, stream, &ctx, MINI_ONE_PASS_BITS, merge ? 1 : 0, regions == Regions::begun ? 1 : 0))) return rc;
+    if (ctx.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "%s: %d first-pass digits of the row shuffle", who, ctx.gb1);
+    l->sh = ShufArgs{ctx.goff, ctx.gcur1, ctx.words_out, ctx.gb1, ctx.gb2, ctx.dshift, merge ? 0 : ctx.narrow, ctx.words_cap};
+    l->n_short = l->plan.n_short(t->k);
+    l->nb = 1u << l->plan.bits;
     return PG_OK;
 }
 
@@ -2409,17 +2636,17 @@ extern "C" int64_t pg_mini_records_bytes(int64_t n_records, const pg_table *t)
     int rc = check_mini(t, "pg_mini_records_bytes");
     if (rc) return rc;
     const size_t n = ((size_t)n_records + 255) / 256 * 256 + 256;
-    return (int64_t)mini_rec_layout(n, (size_t)1 << (t->log2_slots - t->log2_bucket_slots)).total;
+    return (int64_t)mini_rec_layout(n).total;
 }
 
-// where the second meta plane of a record workspace of rec_ws_bytes starts: [bases A | bases B | meta A | meta B], cap records each
+// where the second meta plane of a record workspace of rec_ws_bytes starts
 extern "C" int64_t pg_mini_records_meta_offset(int64_t rec_ws_bytes, const pg_table *t)
 {
     int rc = check_mini(t, "pg_mini_records_meta_offset");
     if (rc) return rc;
-    const size_t cap = mini_rec_cap(rec_ws_bytes, (size_t)1 << (t->log2_slots - t->log2_bucket_slots));
+    const size_t cap = mini_rec_cap(rec_ws_bytes);
     if (cap < 256) return pg_fail(PG_EINVAL, "pg_mini_records_meta_offset: record workspace of %lld bytes (pg_mini_records_bytes)", (long long)rec_ws_bytes);
-    return (int64_t)(20 * cap);
+    return (int64_t)mini_rec_layout(cap).meta_b_off;
 }
 
 // the library's own rule for the merged lookups (mini_merge_form): 1 where they apply to n_rows rows of this geometry, else 0
@@ -2458,38 +2685,6 @@ extern "C" int64_t pg_mini_shuffle_bytes_merged(int64_t n_words, int64_t n_rows,
     return (int64_t)sl.total;
 }
 
-// the first-pass kernels are instantiated per window length (registers of the rolling minimum); k > 21 runs the delayed
-// central window of 8 or 9 M-mers (mini_window)
-#define PG_MINI_DISPATCH_W(K_, CALL)                                                                                        \
-    {                                                                                                                       \
-        int wc_, woff;                                                                                                      \
-        mini_window(K_, &wc_, &woff);                                                                                       \
-        if ((K_) > PG_HASH_MAX_K) {                                                                                         \
-            constexpr bool DELAY = true;                                                                                    \
-            constexpr int M = MINI_M;                                                                                       \
-            if (wc_ == 8) { constexpr int W = 8; CALL; } else { constexpr int W = 9; CALL; }                                \
-        } else if (mini_m(K_) == MINI_M_SMALL) {                                                                            \
-            constexpr bool DELAY = false;                                                                                   \
-            constexpr int M = MINI_M_SMALL;                                                                                 \
-            switch (wc_) {                                                                                                  \
-            case 3: { constexpr int W = 3; CALL; } break;                                                                   \
-            case 4: { constexpr int W = 4; CALL; } break;                                                                   \
-            default: { constexpr int W = 5; CALL; } break;                                                                  \
-            }                                                                                                               \
-        } else {                                                                                                            \
-            constexpr bool DELAY = false;                                                                                   \
-            constexpr int M = MINI_M;                                                                                       \
-            switch (wc_) {                                                                                                  \
-            case 4: { constexpr int W = 4; CALL; } break;                                                                   \
-            case 5: { constexpr int W = 5; CALL; } break;                                                                   \
-            case 6: { constexpr int W = 6; CALL; } break;                                                                   \
-            case 7: { constexpr int W = 7; CALL; } break;                                                                   \
-            case 8: { constexpr int W = 8; CALL; } break;                                                                   \
-            default: { constexpr int W = 9; CALL; } break;                                                                  \
-            }                                                                                                               \
-        }                                                                                                                   \
-    }
-
 // tabv: the table plane of the masked form (pg_mini_plan_masked), NULL otherwise
 static int mini_plan_impl(const uint64_t *codes, const uint32_t *valid, const uint32_t *tabv, int64_t word_begin, int64_t word_end, const pg_table *t,
                           const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *stream)
@@ -2499,42 +2694,36 @@ static int mini_plan_impl(const uint64_t *codes, const uint32_t *valid, const ui
     int rc = check_mini(t, "pg_mini_plan");
     if (rc) return rc;
     if ((rc = check_mini_rows(rows, "pg_mini_plan"))) return rc;
-    MiniPlan p;
-    plan_mini(t, word_end - word_begin, &p);
-    if ((int64_t)p.total > plan_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_plan: workspace of %lld bytes, %lld needed", (long long)plan_ws_bytes, (long long)p.total);
-    if ((reinterpret_cast<uintptr_t>(plan_ws) & 255) != 0) return pg_fail(PG_EINVAL, "pg_mini_plan: workspace must be 256-byte aligned");
+    PlanView p;
+    if ((rc = plan_view(t, word_end - word_begin, plan_ws, plan_ws_bytes, "pg_mini_plan", false, &p))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)plan_ws;
-    auto *header = (unsigned long long *)(ws + p.header_off);
-    auto *region_tot = (unsigned long long *)(ws + p.rtot_off);
-    auto *region_off = (unsigned long long *)(ws + p.roff_off);
-    auto *round_row = (int32_t *)(ws + p.round_off);
-    auto *chunk_tab = (unsigned long long *)(ws + p.chunk_off);
     const int n_regions = 1 << p.bits1;
-    if (hipMemsetAsync(ws, 0, p.round_off, s) != hipSuccess) return pg_fail(PG_EHIP, "pg_mini_plan: memset failed");
-    if (hipMemsetAsync(chunk_tab, 0, ((size_t)p.n_chunks << p.bits1) * 8, s) != hipSuccess) return pg_fail(PG_EHIP, "pg_mini_plan: memset failed");
+    // (everything in front of round_row, the header first)
+    if (hipMemsetAsync(p.header, 0, (size_t)((char *)p.round_row - (char *)p.header), s) != hipSuccess) return pg_fail(PG_EHIP, "pg_mini_plan: memset failed");
+    if (hipMemsetAsync(p.chunk_tab, 0, ((size_t)p.n_chunks << p.bits1) * 8, s) != hipSuccess) return pg_fail(PG_EHIP, "pg_mini_plan: memset failed");
     const bool with_rows = rows && rows->n_rows > 0;
     if (word_end > word_begin) {
         if (with_rows)
             hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)((p.n_rounds + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, rows->row_end, rows->n_rows,
-                               word_begin, p.n_rounds, round_row);
+                               word_begin, p.n_rounds, p.round_row);
         const int grid = (int)(p.n_chunks < 4096 ? p.n_chunks : 4096);
-#define PG_MINI_LAUNCH_PLAN(MASKED_)                                                                                        \
-        PG_MINI_DISPATCH_W(t->k,                                                                                            \
-            hipLaunchKernelGGL((mini_plan_kernel<W, DELAY, M, MASKED_>), dim3(grid), dim3(BLOCK), 0, s, codes, valid, word_begin, word_end, t->k, woff, p.bits, p.bits2, mini_cap(t->k), \
-                               with_rows ? rows->row_start : (const int64_t *)nullptr, with_rows ? rows->row_end : (const int64_t *)nullptr, \
-                               with_rows ? rows->n_rows : (int64_t)0, with_rows ? rows->strict_valid : (const uint32_t *)nullptr, \
-                               (const int32_t *)round_row, chunk_tab, p.n_chunks, p.chunk_stride, header + 2, tabv))
-        if (tabv) PG_MINI_LAUNCH_PLAN(true)
-        else PG_MINI_LAUNCH_PLAN(false)
-#undef PG_MINI_LAUNCH_PLAN
+        rc = with_flag(tabv != nullptr, [&](auto masked) {
+            return with_window(t->k, [&](auto w, int woff) {
+                using Win = decltype(w);
+                return launch(mini_plan_kernel<Win::W, Win::DELAY, Win::M, decltype(masked)::value>, dim3(grid), dim3(BLOCK), 0, s, "pg_mini_plan",
+                              codes, valid, word_begin, word_end, t->k, woff, p.bits, p.bits2, mini_cap(t->k),
+                              with_rows ? rows->row_start : nullptr, with_rows ? rows->row_end : nullptr, with_rows ? rows->n_rows : (int64_t)0,
+                              with_rows ? rows->strict_valid : nullptr, p.round_row, p.chunk_tab, p.n_chunks, p.chunk_stride, p.header + 2, tabv);
+            });
+        });
+        if (rc) return rc;
     }
     // records per region -> where the regions start -> exact offset of every (chunk, region) run; total -> header[0]
-    hipLaunchKernelGGL(digit_totals_kernel, dim3((unsigned)n_regions), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)chunk_tab, p.n_chunks, region_tot);
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)region_tot, (int64_t)n_regions, region_off);
-    hipLaunchKernelGGL(digit_scan_kernel, dim3((unsigned)n_regions), dim3(BIG_BLOCK), 0, s, chunk_tab, p.n_chunks, (const unsigned long long *)region_off,
+    hipLaunchKernelGGL(digit_totals_kernel, dim3((unsigned)n_regions), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)p.chunk_tab, p.n_chunks, p.region_tot);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)p.region_tot, (int64_t)n_regions, p.region_off);
+    hipLaunchKernelGGL(digit_scan_kernel, dim3((unsigned)n_regions), dim3(BIG_BLOCK), 0, s, p.chunk_tab, p.n_chunks, (const unsigned long long *)p.region_off,
                        0, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(mini_total_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)region_off, n_regions, header);
+    hipLaunchKernelGGL(mini_total_kernel, dim3(1), dim3(64), 0, s, (const unsigned long long *)p.region_off, n_regions, p.header);
     return check_launch("pg_mini_plan");
 }
 
@@ -2561,204 +2750,137 @@ extern "C" int pg_mini_wait_first_pass(void *stream)
     return PG_OK;
 }
 
+// what the count entry points hand to mini_count_impl.  tabv: the table plane of the masked form, NULL otherwise.
 // `half` (N > 1 ranks): the count half only -- no slice, no lookups; the bucket workgroups leave entries, occupancy and what
 // the lookup half needs (HalfArgs).  `t` is then the rank's LOCAL geometry (the union's buckets, slots for the rank's own
-// k-mers); its slots are never written.
-static int mini_count_impl(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *t,
-                           const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
-                           int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, uint32_t *status, void *stream, const HalfArgs *half,
-                           void *merge_ws = nullptr, int64_t merge_ws_words = 0, const uint32_t *tabv = nullptr)
+// k-mers); its slots are never written.  half->accum != 0: a piece (no lookups in this launch, no row shuffle)
+struct CountArgs {
+    const uint64_t *codes; const uint32_t *valid, *tabv; int64_t word_begin, word_end; const pg_table *t; const pg_rows *rows;
+    void *plan_ws; int64_t plan_ws_bytes; void *rec_ws; int64_t rec_ws_bytes; int window, vsize;
+    void *shuffle_ws; int64_t shuffle_ws_bytes; void *merge_ws; int64_t merge_ws_words; const HalfArgs *half; uint32_t *status; void *stream;
+};
+
+static int mini_count_impl(const CountArgs &a)
 {
-    if (!codes || !valid || !plan_ws || !rec_ws || !status) return pg_fail(PG_EINVAL, "pg_mini_count: null argument");
-    if (word_begin < 0 || word_end < word_begin) return pg_fail(PG_EINVAL, "pg_mini_count: bad word range");
+    const pg_table *t = a.t; const pg_rows *rows = a.rows;
+    const int window = a.window, vsize = a.vsize;
+    const int64_t n_words = a.word_end - a.word_begin;
+    // ---- every refusal comes before anything is enqueued
+    if (!a.codes || !a.valid || !a.plan_ws || !a.rec_ws || !a.status) return pg_fail(PG_EINVAL, "pg_mini_count: null argument");
+    if (a.word_begin < 0 || a.word_end < a.word_begin) return pg_fail(PG_EINVAL, "pg_mini_count: bad word range");
     int rc = check_mini(t, "pg_mini_count");
     if (rc) return rc;
     if ((rc = check_mini_rows(rows, "pg_mini_count"))) return rc;
-    const bool with_rows = rows && rows->n_rows > 0;
+    const bool with_rows = rows && rows->n_rows > 0, some_words = n_words > 0;
     if (window < 0 || vsize < 0 || (window > 0) != (vsize > 0)) return pg_fail(PG_EINVAL, "pg_mini_count: window %d / vector size %d", window, vsize);
-    const bool piece = half && half->accum;                      // (pg_mini_count_piece: no lookups in this launch, no row shuffle)
+    const bool half = a.half != nullptr, piece = half && a.half->accum;
     if (window > 0) {
         if (!with_rows) return pg_fail(PG_EINVAL, "pg_mini_count: the lookup pass needs rows");
-        if (!shuffle_ws && !piece) return pg_fail(PG_EINVAL, "pg_mini_count: null shuffle workspace");
+        if (!a.shuffle_ws && !piece) return pg_fail(PG_EINVAL, "pg_mini_count: null shuffle workspace");
         if (vsize > PG_SHUFFLE_MAX_VSIZE || (t->kind == PG_TABLE_MINI && (int64_t)window * vsize > (int64_t)PG_HASH_COUNT_SAT))
             return pg_fail(PG_EINVAL, "pg_mini_count: window %d x vector size %d outside the exact range of the table", window, vsize);
     }
-    MiniPlan p;
-    plan_mini(t, word_end - word_begin, &p);
-    if ((int64_t)p.total > plan_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_count: plan workspace of %lld bytes, %lld needed", (long long)plan_ws_bytes, (long long)p.total);
-    if ((reinterpret_cast<uintptr_t>(plan_ws) & 255) != 0 || (reinterpret_cast<uintptr_t>(rec_ws) & 255) != 0)
-        return pg_fail(PG_EINVAL, "pg_mini_count: workspaces must be 256-byte aligned");
-    // the largest record capacity (a multiple of 256) whose layout fits the workspace
-    const size_t cap = mini_rec_cap(rec_ws_bytes, (size_t)1 << p.bits);
-    if (cap < 256) return pg_fail(PG_EINVAL, "pg_mini_count: record workspace of %lld bytes (pg_mini_records_bytes)", (long long)rec_ws_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    char *ws = (char *)plan_ws;
-    auto *header = (unsigned long long *)(ws + p.header_off);
-    auto *off = (unsigned long long *)(ws + p.off_off);
-    auto *cur2 = (unsigned long long *)(ws + p.cur2_off);
-    auto *cur2l = (unsigned long long *)(ws + p.cur2l_off);
-    auto *kwords = (unsigned long long *)(ws + p.kw_off);            // (hist | cur2 | cur2l | kwords are cleared together below)
-    auto *hist = (unsigned long long *)(ws + p.hist_off);
-    auto *region_off = (unsigned long long *)(ws + p.roff_off);
-    auto *wbeg = (unsigned long long *)(ws + p.wbeg_off);
-    auto *round_row = (int32_t *)(ws + p.round_off);
-    auto *chunk_tab = (unsigned long long *)(ws + p.chunk_off);
-    const int nb = 1 << p.bits;
-    // record buffers: [bases A | bases B | meta A | meta B], cap records each
-    auto *bases_a = (uint64_t *)rec_ws;
-    auto *bases_b = bases_a + cap;
-    auto *meta_a = (uint32_t *)(bases_b + cap);
-    auto *meta_b = meta_a + cap;
-    if (hipMemsetAsync(hist, 0, p.wbeg_off - p.hist_off, s) != hipSuccess || hipMemsetAsync(header + 1, 0, 8, s) != hipSuccess)
-        return pg_fail(PG_EHIP, "pg_mini_count: memset failed");
+    PlanView p;
+    RecView rec;
+    if ((rc = plan_view(t, n_words, a.plan_ws, a.plan_ws_bytes, "pg_mini_count", true, &p))) return rc;
+    if ((rc = rec_view(a.rec_ws, a.rec_ws_bytes, "pg_mini_count", &rec))) return rc;
+    const bool slots_form = window > 0 && mini_slots_form(t, rows);
+    const bool merge = window > 0 && a.merge_ws && a.merge_ws_words > 0 && mini_merge_form(t, rows, vsize);
     pg_shuffle_layout sl{0, 0, 0, 0, 0};
     if (window > 0 && !piece) {
-        if ((rc = pg_internal_shuffle_layout((word_end - word_begin) * 32, rows->n_rows, vsize, &sl, mini_slots_form(t, rows) ? MINI_ONE_PASS_BITS : PG_SHUFFLE_ONE_PASS_BITS,
-                                             merge_ws && merge_ws_words > 0 && mini_merge_form(t, rows, vsize) ? 1 : 0)))
-            return rc;
-        if ((int64_t)sl.total > shuffle_ws_bytes || (reinterpret_cast<uintptr_t>(shuffle_ws) & 255) != 0)
-            return pg_fail(PG_EINVAL, "pg_mini_count: shuffle workspace of %lld bytes (256-byte aligned), %lld needed", (long long)shuffle_ws_bytes, (long long)sl.total);
+        if ((rc = pg_internal_shuffle_layout(n_words * 32, rows->n_rows, vsize, &sl, slots_form ? MINI_ONE_PASS_BITS : PG_SHUFFLE_ONE_PASS_BITS, merge ? 1 : 0))) return rc;
+        if ((int64_t)sl.total > a.shuffle_ws_bytes || misaligned(a.shuffle_ws))
+            return pg_fail(PG_EINVAL, "pg_mini_count: shuffle workspace of %lld bytes (256-byte aligned), %lld needed", (long long)a.shuffle_ws_bytes, (long long)sl.total);
     }
-    const bool wide = t->kind == PG_TABLE_MINI_WIDE;              // 8-byte keys + 4-byte counts per slot
-    const size_t table_lds = (size_t)(wide ? 12 : 8) << t->log2_bucket_slots;
-    const size_t slice_lds = table_lds + (size_t)COUNT_WAVES * RING * 12;      // table + the wavefronts' rings (1024 threads)
-    if (word_end > word_begin) {
-#define PG_MINI_LAUNCH_SCATTER(N1_, MASKED_)                                                                                 \
-        PG_MINI_DISPATCH_W(t->k,                                                                                            \
-            const size_t lds1 = MASKED_ ? sizeof(Scatter1LdsMasked<N1_>) : sizeof(Scatter1Lds<N1_>);                         \
-            if ((rc = raise_lds_limit((const void *)(mini_scatter_kernel<W, DELAY, M, N1_, MASKED_>), lds1, "pg_mini_count"))) return rc; \
-            hipLaunchKernelGGL((mini_scatter_kernel<W, DELAY, M, N1_, MASKED_>), dim3((unsigned)p.n_chunks), dim3(S1_BLOCK), lds1, s, codes, valid, word_begin, word_end, t->k, woff, p.bits, \
-                               p.bits2, mini_cap(t->k), with_rows ? rows->row_start : (const int64_t *)nullptr, with_rows ? rows->row_end : (const int64_t *)nullptr, \
-                               with_rows ? rows->n_rows : (int64_t)0, with_rows ? rows->strict_valid : (const uint32_t *)nullptr, \
-                               (const int32_t *)round_row, bases_a, meta_a, (const unsigned long long *)chunk_tab, p.n_chunks, p.chunk_stride, \
-                               (const unsigned long long *)header, (const unsigned long long *)region_off, (unsigned long long)cap, status, tabv))
-        if (tabv) PG_MINI_LAUNCH_SCATTER(256, true)
-        else PG_MINI_LAUNCH_SCATTER(256, false)
-#undef PG_MINI_LAUNCH_SCATTER
+    if (a.merge_ws && misaligned(a.merge_ws)) return pg_fail(PG_EINVAL, "pg_mini_count: workspaces must be 256-byte aligned");
+    if (half && (t->kind == PG_TABLE_MINI_WIDE || !slots_form))
+        return pg_fail(PG_EINVAL, "pg_mini_count_half: needs packed slots (k <= %d), rows and fewer than 2^(32 - log2 bucket slots) of them", PG_HASH_MAX_K);
+    if (half && !p.bits2) return pg_fail(PG_EINVAL, "pg_mini_count_half: needs more than 256 buckets");
+    if (piece && !merge) return pg_fail(PG_EINVAL, "pg_mini_count_piece: needs the merged lookups (fewer than 2^20 rows, their slot buffer given)");
+    if (a.tabv && !(half && merge && rows->n_rows <= PG_MINI_MASKED_MAX_ROWS))
+        return pg_fail(PG_EINVAL, "pg_mini_count_half_masked: needs the merged lookups (their slot buffer given) and at most %d rows", PG_MINI_MASKED_MAX_ROWS);
+    hipStream_t s = (hipStream_t)a.stream;
+    const int nb = 1 << p.bits, cap_k = mini_cap(t->k);
+    // ---- clear: hist | cur2 | cur2l | kwords (they lie in a row), and the word cursor
+    if (hipMemsetAsync(p.hist, 0, (size_t)((char *)p.wbeg - (char *)p.hist), s) != hipSuccess || hipMemsetAsync(p.header + 1, 0, 8, s) != hipSuccess)
+        return pg_fail(PG_EHIP, "pg_mini_count: memset failed");
+    // ---- first pass: the stream -> records, sorted by region
+    if (some_words) {
+        rc = with_flag(a.tabv != nullptr, [&](auto masked) {
+            return with_window(t->k, [&](auto w, int woff) {
+                using Win = decltype(w);
+                constexpr bool MASKED = decltype(masked)::value;
+                const size_t lds1 = MASKED ? sizeof(Scatter1LdsMasked<256>) : sizeof(Scatter1Lds<256>);
+                return launch(mini_scatter_kernel<Win::W, Win::DELAY, Win::M, 256, MASKED>, dim3((unsigned)p.n_chunks), dim3(S1_BLOCK), lds1, s, "pg_mini_count",
+                              a.codes, a.valid, a.word_begin, a.word_end, t->k, woff, p.bits, p.bits2, cap_k,
+                              with_rows ? rows->row_start : nullptr, with_rows ? rows->row_end : nullptr, with_rows ? rows->n_rows : (int64_t)0,
+                              with_rows ? rows->strict_valid : nullptr, p.round_row, rec.bases_a, rec.meta_a, p.chunk_tab, p.n_chunks, p.chunk_stride,
+                              p.header, p.region_off, (unsigned long long)rec.cap, a.status, a.tabv);
+            });
+        });
+        if (rc) return rc;
     }
     // (for pg_mini_wait_first_pass: what is enqueued on another stream behind this event runs beside the second pass and the count)
     if (!first_pass_event && hipEventCreateWithFlags(&first_pass_event, hipEventDisableTiming) != hipSuccess)
         return pg_fail(PG_EHIP, "pg_mini_count: event creation failed");
     if (hipEventRecord(first_pass_event, s) != hipSuccess) return pg_fail(PG_EHIP, "pg_mini_count: event record failed");
+    // ---- bucket offsets: records per bucket from the regions' meta plane -> where every bucket starts (an empty range: all zero)
     if (p.bits2) {
-        // records per bucket from the regions' meta plane -> where every bucket starts (an empty range: all zero)
         const int tiles_h = 32;
-        if (word_end > word_begin)
-            hipLaunchKernelGGL(mini_bucket_hist_kernel, dim3((unsigned)(tiles_h << p.bits1)), dim3(BLOCK), 0, s, (const uint32_t *)meta_a,
-                               (const unsigned long long *)region_off, p.bits2, tiles_h, hist, (const unsigned long long *)header, (unsigned long long)cap, (const uint32_t *)status);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)hist, (int64_t)nb, off);
-    } else {
-        off = region_off;                                   // buckets = regions
+        if (some_words)
+            hipLaunchKernelGGL(mini_bucket_hist_kernel, dim3((unsigned)(tiles_h << p.bits1)), dim3(BLOCK), 0, s, (const uint32_t *)rec.meta_a,
+                               (const unsigned long long *)p.region_off, p.bits2, tiles_h, p.hist, (const unsigned long long *)p.header, (unsigned long long)rec.cap, (const uint32_t *)a.status);
+        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)p.hist, (int64_t)nb, p.off);
     }
-    // (the merged lookups size their buffer from record counts: the second pass need not tally the k-mers in rows per bucket)
-    const bool merge_a2 = window > 0 && merge_ws && merge_ws_words > 0 && mini_merge_form(t, rows, vsize);
-    if (word_end > word_begin) {
-        if (p.bits2) {
-            // 256 digits: about one workgroup per tile of a region (from the record capacity: the count itself is on the device); with
-            // the regions' workgroups on one XCD each, 96 workgroups per region walking a dozen tiles each took 3.32 ms where 576 to 1152
-            // take 3.05.  512 digits: one workgroup per CU fits, so 16 per region walk a dozen tiles each with the next one
-            // prefetched (tiles of 512 x 16 records: 2.99 ms with 16 per region; 8: 3.30, 32 to 64: 2.99-3.01, 128: 3.12, one tile
-            // per workgroup without the prefetch: 3.29.  512 x 20: 2.89-3.00, 512 x 24: 2.82-2.95)
-            const bool dig512 = p.bits2 > 7;
-            const size_t tile = dig512 ? (size_t)S2Geom<512, 512, 24>::TILE : (size_t)S2Geom<256, BLOCK, 16>::TILE;
-            const int tiles_x = (int)std::min<size_t>(dig512 ? 16 : 2048, std::max<size_t>(8, cap / (tile << p.bits1) + 1));
-#define PG_MINI_LAUNCH_S2(DIG_, BLK_, RPL_, PF_)                                                                                   \
-            do {                                                                                                            \
-                const size_t lds2 = sizeof(Scatter2Lds<DIG_, BLK_, RPL_>);                                                  \
-                if ((rc = raise_lds_limit((const void *)(mini_scatter2_kernel<DIG_, BLK_, RPL_, PF_>), lds2, "pg_mini_count"))) return rc; \
-                hipLaunchKernelGGL((mini_scatter2_kernel<DIG_, BLK_, RPL_, PF_>), dim3((unsigned)(tiles_x << p.bits1)), dim3(BLK_), lds2, s,   \
-                                   (const uint64_t *)bases_a, (const uint32_t *)meta_a, (const unsigned long long *)off, p.bits2, tiles_x, \
-                                   mini_cap(t->k) > SHORT_MAX ? SHORT_MAX : 0, bases_b, meta_b, cur2, cur2l,                \
-                                   merge_a2 ? (unsigned long long *)nullptr : kwords, (const unsigned long long *)header, (unsigned long long)cap, status); \
-            } while (0)
-            if (dig512) PG_MINI_LAUNCH_S2(512, 512, 24, true);
-            else PG_MINI_LAUNCH_S2(256, BLOCK, 16, false);
-#undef PG_MINI_LAUNCH_S2
-        }
+    const unsigned long long *off = p.bits2 ? p.off : p.region_off;             // (at most 256 buckets: buckets = regions)
+    // ---- second pass: every region -> its buckets, short records first
+    if (some_words && p.bits2) {
+        // 256 digits: about one workgroup per tile of a region (from the record capacity: the count itself is on the device); with
+        // the regions' workgroups on one XCD each, 96 workgroups per region walking a dozen tiles each took 3.32 ms where 576 to 1152
+        // take 3.05.  512 digits: one workgroup per CU fits, so 16 per region walk a dozen tiles each with the next one
+        // prefetched (tiles of 512 x 16 records: 2.99 ms with 16 per region; 8: 3.30, 32 to 64: 2.99-3.01, 128: 3.12, one tile
+        // per workgroup without the prefetch: 3.29.  512 x 20: 2.89-3.00, 512 x 24: 2.82-2.95)
+        const bool dig512 = p.bits2 > 7;
+        const size_t tile = dig512 ? (size_t)S2Geom<512, 512, 24>::TILE : (size_t)S2Geom<256, BLOCK, 16>::TILE;
+        const int tiles_x = (int)std::min<size_t>(dig512 ? 16 : 2048, std::max<size_t>(8, rec.cap / (tile << p.bits1) + 1));
+        auto second_pass = [&](auto dig, auto blk, auto rpl, auto prefetch) {
+            constexpr int DIG = decltype(dig)::value, BLK = decltype(blk)::value, RPL = decltype(rpl)::value;
+            // (the merged lookups size their buffer from record counts: the second pass need not tally the k-mers in rows per bucket)
+            return launch(mini_scatter2_kernel<DIG, BLK, RPL, decltype(prefetch)::value>, dim3((unsigned)(tiles_x << p.bits1)), dim3(BLK),
+                          sizeof(Scatter2Lds<DIG, BLK, RPL>), s, "pg_mini_count", rec.bases_a, rec.meta_a, off, p.bits2, tiles_x,
+                          cap_k > SHORT_MAX ? SHORT_MAX : 0, rec.bases_b, rec.meta_b, p.cur2, p.cur2l, merge ? nullptr : p.kwords, p.header,
+                          (unsigned long long)rec.cap, a.status);
+        };
+        rc = dig512 ? second_pass(int_tag<512>{}, int_tag<512>{}, int_tag<24>{}, std::true_type{}) : second_pass(int_tag<256>{}, int_tag<BLOCK>{}, int_tag<16>{}, std::false_type{});
+        if (rc) return rc;
     }
-    const bool slots_form = window > 0 && mini_slots_form(t, rows);
-    // (the classes are sorted apart by the second scatter pass: without it -- at most 256 buckets -- every record counts as long)
-    const unsigned long long *n_short = p.bits2 && mini_cap(t->k) > SHORT_MAX ? (const unsigned long long *)cur2 : (const unsigned long long *)nullptr;
-    uint32_t *words_e = window && !piece ? (uint32_t *)((char *)shuffle_ws + sl.words_e_off) : (uint32_t *)nullptr;
-    uint32_t *words_a = window && !piece ? (uint32_t *)((char *)shuffle_ws + sl.words_a_off) : (uint32_t *)nullptr;
+    // ---- count (and, but for the halves, the lookups): one workgroup per bucket
+    const bool shuffles = window && !piece;
+    char *shuffle_ws = (char *)a.shuffle_ws;
+    uint32_t *words_e = shuffles ? (uint32_t *)(shuffle_ws + sl.words_e_off) : nullptr;
+    uint32_t *words_a = shuffles ? (uint32_t *)(shuffle_ws + sl.words_a_off) : nullptr;
+    unsigned long long *emit_end = shuffles ? (unsigned long long *)(shuffle_ws + sl.emit_off) : nullptr;
     ShufArgs sh{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0ull};
-    const MergeArgs mg{(uint32_t *)merge_ws, (unsigned long long)(merge_ws ? merge_ws_words : 0)};
-    const bool merge = window > 0 && merge_ws && merge_ws_words > 0 && mini_merge_form(t, rows, vsize);
-    if (merge_ws && (reinterpret_cast<uintptr_t>(merge_ws) & 255) != 0) return pg_fail(PG_EINVAL, "pg_mini_count: workspaces must be 256-byte aligned");
-    if (half && (wide || !(window > 0 && mini_slots_form(t, rows))))
-        return pg_fail(PG_EINVAL, "pg_mini_count_half: needs packed slots (k <= %d), rows and fewer than 2^(32 - log2 bucket slots) of them", PG_HASH_MAX_K);
-    if (half && !p.bits2) return pg_fail(PG_EINVAL, "pg_mini_count_half: needs more than 256 buckets");
-    if (piece && !merge) return pg_fail(PG_EINVAL, "pg_mini_count_piece: needs the merged lookups (fewer than 2^20 rows, their slot buffer given)");
-    if (tabv && !(half && merge && rows->n_rows <= PG_MINI_MASKED_MAX_ROWS))
-        return pg_fail(PG_EINVAL, "pg_mini_count_half_masked: needs the merged lookups (their slot buffer given) and at most %d rows", PG_MINI_MASKED_MAX_ROWS);
-    HalfArgs hv = half ? *half : HalfArgs{nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-    hv.meta_w = tabv ? (p.bits2 ? meta_b : meta_a) : nullptr;    // (the plane the count kernel reads: the lookup half reads it again)
-    size_t count_lds = slice_lds;
-    // Buckets of at most 2^13 8-byte slots (64 KiB): 512-thread workgroups, TWO per CU -- one can be in its count loop (VALU, waits)
-    // while the other is in its lookup phase (LDS throughput).  PG_COUNT_BLOCK=1024: the one-workgroup form for such tables too.
-    const char *blk_env = getenv("PG_COUNT_BLOCK");
-    const bool many_groups = window > 0 && rows && rows->n_rows > ((int64_t)1 << (PG_SHUFFLE_ONE_PASS_BITS + 6));     // more than 2^10 row groups: 2048 digits
-    // (the count half does no lookups: the row-group digits do not matter to its geometry)
-    const bool half_block = !wide && window > 0 && mini_slots_form(t, rows) && t->log2_bucket_slots <= 13 && (!many_groups || half) && !(blk_env && atoi(blk_env) == 1024);
-    if (half_block) count_lds = table_lds + (size_t)(512 / 64) * RING * 12;
     if (slots_form && !piece) {
         // the count kernel scatters its words into the row shuffle's group regions itself: offsets and cursors must be ready
         pg_shuffle_ctx ctx;
-        if ((rc = pg_internal_shuffle_prepare((word_end - word_begin) * 32, rows, vsize, shuffle_ws, shuffle_ws_bytes, stream, &ctx, MINI_ONE_PASS_BITS, merge ? 1 : 0))) return rc;
+        if ((rc = pg_internal_shuffle_prepare(n_words * 32, rows, vsize, a.shuffle_ws, a.shuffle_ws_bytes, a.stream, &ctx, MINI_ONE_PASS_BITS, merge ? 1 : 0))) return rc;
         sh = ShufArgs{ctx.goff, ctx.gcur1, ctx.words_out, ctx.gb1, ctx.gb2, ctx.dshift, merge ? 0 : ctx.narrow, ctx.words_cap};
         words_a = ctx.words_in;                          // the provisional words wait in the shuffle's input buffer
-        const size_t lookup_lds = merge ? (half_block ? MergeLds<512, 1024>::END : sh.gb1 > 10 ? MergeLds<BIG_BLOCK, 2048>::END : MergeLds<BIG_BLOCK, 1024>::END)
-                                        : half_block ? LookupLds<512, 1024>::END : sh.gb1 > 10 ? LookupLds<BIG_BLOCK, 2048>::END : LookupLds<BIG_BLOCK, 1024>::END;
         if (sh.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "pg_mini_count: %d first-pass digits of the row shuffle", sh.gb1);
-        if (count_lds < lookup_lds && !half) count_lds = lookup_lds;
     }
-    unsigned long long *emit_end = window && !piece ? (unsigned long long *)((char *)shuffle_ws + sl.emit_off) : (unsigned long long *)nullptr;
-#define PG_MINI_LAUNCH_COUNT__(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, LDS_) PG_MINI_LAUNCH_COUNT_M(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, false, LDS_)
-#define PG_MINI_LAUNCH_COUNT_M(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, MASKED_, LDS_)                               \
-    do {                                                                                                                    \
-        if ((rc = raise_lds_limit((const void *)(mini_count_kernel<CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, MASKED_>), LDS_, "pg_mini_count"))) return rc; \
-        hipLaunchKernelGGL((mini_count_kernel<CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, HALF_, MASKED_>), dim3(nb), dim3(BLK_), LDS_, s, \
-                           (const uint64_t *)(p.bits2 ? bases_b : bases_a), (const uint32_t *)(p.bits2 ? meta_b : meta_a),  \
-                           (const unsigned long long *)off, n_short, p.bits2 ? (const unsigned long long *)kwords : (const unsigned long long *)nullptr, \
-                           mini_view(t), (uint32_t)window, (uint32_t)vsize,                                                 \
-                           sl.vbits, words_e, words_a, header + 1, wbeg, emit_end, sh, mg, (unsigned long long)cap, status, hv); \
-    } while (0)
-#define PG_MINI_LAUNCH_COUNT_(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, LDS_) PG_MINI_LAUNCH_COUNT__(CAP_, SLOTS_, WIDE_, BLK_, DIG_, MERGE_, false, LDS_)
-#define PG_MINI_LAUNCH_SLOTS_(CAP_, WIDE_, BLK_, DIG_)                                                                      \
-    do {                                                                                                                    \
-        if (merge) PG_MINI_LAUNCH_COUNT_(CAP_, true, WIDE_, BLK_, DIG_, true, count_lds);                                    \
-        else PG_MINI_LAUNCH_COUNT_(CAP_, true, WIDE_, BLK_, DIG_, false, count_lds);                                         \
-    } while (0)
-#define PG_MINI_LAUNCH_SLOTS(CAP_, WIDE_)                                                                                   \
-    do {                                                                                                                    \
-        if (sh.gb1 > 10) PG_MINI_LAUNCH_SLOTS_(CAP_, WIDE_, BIG_BLOCK, 2048);                                                \
-        else PG_MINI_LAUNCH_SLOTS_(CAP_, WIDE_, BIG_BLOCK, 1024);                                                            \
-    } while (0)
-#define PG_MINI_LAUNCH_COUNT(CAP_)                                                                                          \
-    do {                                                                                                                    \
-        if (tabv) { if (half_block) PG_MINI_LAUNCH_COUNT_M(CAP_, true, false, 512, 1024, true, true, true, count_lds);       \
-                    else PG_MINI_LAUNCH_COUNT_M(CAP_, true, false, BIG_BLOCK, 1024, true, true, true, count_lds); }         \
-        else if (half) { if (half_block) { if (merge) PG_MINI_LAUNCH_COUNT__(CAP_, true, false, 512, 1024, true, true, count_lds);  \
-                                      else PG_MINI_LAUNCH_COUNT__(CAP_, true, false, 512, 1024, false, true, count_lds); }   \
-                    else { if (merge) PG_MINI_LAUNCH_COUNT__(CAP_, true, false, BIG_BLOCK, 1024, true, true, count_lds);     \
-                           else PG_MINI_LAUNCH_COUNT__(CAP_, true, false, BIG_BLOCK, 1024, false, true, count_lds); } }      \
-        else if (wide) { if (slots_form) PG_MINI_LAUNCH_SLOTS(CAP_, true); else PG_MINI_LAUNCH_COUNT_(CAP_, false, true, BIG_BLOCK, 1024, false, slice_lds); } \
-        else if (half_block) PG_MINI_LAUNCH_SLOTS_(CAP_, false, 512, 1024);                                                  \
-        else { if (slots_form) PG_MINI_LAUNCH_SLOTS(CAP_, false); else PG_MINI_LAUNCH_COUNT_(CAP_, false, false, BIG_BLOCK, 1024, false, slice_lds); } \
-    } while (0)
-    switch (mini_cap(t->k)) {                                          // k-mers per record at most (as the first pass cuts them)
-    case 1: case 2: case 3: case 4: PG_MINI_LAUNCH_COUNT(4); break;
-    case 5: case 6: PG_MINI_LAUNCH_COUNT(6); break;
-    case 7: case 8: PG_MINI_LAUNCH_COUNT(8); break;
-    default: PG_MINI_LAUNCH_COUNT(9); break;        // (cap <= W <= 9: see mini_cap)
-    }
-#undef PG_MINI_LAUNCH_COUNT
-#undef PG_MINI_LAUNCH_SLOTS
-#undef PG_MINI_LAUNCH_SLOTS_
-#undef PG_MINI_LAUNCH_COUNT_
-#undef PG_MINI_LAUNCH_COUNT__
-#undef PG_MINI_LAUNCH_COUNT_M
-    return check_launch("pg_mini_count");
+    const CountForm form = count_form(t, rows, slots_form, merge, half, a.tabv != nullptr, sh.gb1);
+    const MergeArgs mg{(uint32_t *)a.merge_ws, (unsigned long long)(a.merge_ws ? a.merge_ws_words : 0)};
+    HalfArgs hv = half ? *a.half : HalfArgs{nullptr, nullptr, nullptr, nullptr, 0, nullptr};
+    hv.meta_w = a.tabv ? (p.bits2 ? rec.meta_b : rec.meta_a) : nullptr;    // (the plane the count kernel reads: the lookup half reads it again)
+    rc = with_cap(cap_k, [&](auto cap_c) {
+        return with_count_kernel<decltype(cap_c)::value>(form, [&](auto kernel) {
+            return launch(kernel, dim3(nb), dim3(form.blk), form.lds, s, "pg_mini_count", p.bits2 ? rec.bases_b : rec.bases_a, p.bits2 ? rec.meta_b : rec.meta_a,
+                          off, p.n_short(t->k), p.bits2 ? p.kwords : nullptr, mini_view(t), window, vsize, sl.vbits, words_e, words_a, p.header + 1, p.wbeg,
+                          emit_end, sh, mg, (unsigned long long)rec.cap, a.status, hv);
+        });
+    });
+    return rc ? rc : check_launch("pg_mini_count");
 }
 
 extern "C" int pg_mini_count(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *t,
@@ -2766,8 +2888,8 @@ extern "C" int pg_mini_count(const uint64_t *codes, const uint32_t *valid, int64
                              int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
                              uint32_t *status, void *stream)
 {
-    return mini_count_impl(codes, valid, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize, shuffle_ws,
-                           shuffle_ws_bytes, status, stream, nullptr, merge_ws, merge_ws_words);
+    return mini_count_impl(CountArgs{codes, valid, nullptr, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                     shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, nullptr, status, stream});
 }
 
 // ---- a stream counted in pieces (one GPU; see HalfArgs / mini_lookup_slice_merge_kernel)
@@ -2780,8 +2902,8 @@ extern "C" int pg_mini_count_piece(const uint64_t *codes, const uint32_t *valid,
     if (t->kind != PG_TABLE_MINI) return pg_fail(PG_EINVAL, "pg_mini_count_piece: packed mini tables (13 <= k <= %d)", PG_HASH_MAX_K);
     if (window < 1 || vsize < 1 || !merge_ws) return pg_fail(PG_EINVAL, "pg_mini_count_piece: needs the abundance parameters and the slot buffer");
     const HalfArgs hv{nullptr, nullptr, nullptr, nullptr, first ? 1 : 2};
-    return mini_count_impl(codes, valid, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize, nullptr, 0,
-                           status, stream, &hv, merge_ws, merge_ws_words);
+    return mini_count_impl(CountArgs{codes, valid, nullptr, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                     nullptr, 0, merge_ws, merge_ws_words, &hv, status, stream});
 }
 
 // offsets and cursors of the row shuffle for the words of ALL pieces (n_words_total: the words of the whole stream); once, before the
@@ -2804,45 +2926,25 @@ extern "C" int pg_mini_lookup_piece(const pg_table *t, const pg_rows *rows, cons
                                     const uint32_t *meta, int64_t n_words_total, int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes,
                                     const void *merge_ws, uint32_t *status, void *stream)
 {
-    int rc = check_mini(t, "pg_mini_lookup_piece");
+    const char *who = "pg_mini_lookup_piece";
+    int rc = check_mini(t, who);
     if (rc) return rc;
     if (t->kind != PG_TABLE_MINI || !rows || !plan_ws || !meta || !shuffle_ws || !merge_ws || !status || window < 1 || vsize < 1)
         return pg_fail(PG_EINVAL, "pg_mini_lookup_piece: bad argument");
-    if ((rc = check_mini_rows(rows, "pg_mini_lookup_piece"))) return rc;
+    if ((rc = check_mini_rows(rows, who))) return rc;
     if (!mini_merge_form(t, rows, vsize)) return pg_fail(PG_EINVAL, "pg_mini_lookup_piece: the merged lookups do not apply to these rows");
-    MiniPlan p;
-    plan_mini(t, n_words_piece, &p);
-    if ((int64_t)p.total > plan_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_lookup_piece: plan workspace does not match n_words_piece");
-    if (!p.bits2) return pg_fail(PG_EINVAL, "pg_mini_lookup_piece: needs more than 256 buckets");
-    pg_shuffle_ctx ctx;
-    if ((rc = pg_internal_shuffle_prepare(n_words_total * 32, rows, vsize, shuffle_ws, shuffle_ws_bytes, stream, &ctx, MINI_ONE_PASS_BITS, 1, 1))) return rc;
-    if (ctx.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "pg_mini_lookup_piece: %d first-pass digits of the row shuffle", ctx.gb1);
-    const ShufArgs sh{ctx.goff, ctx.gcur1, ctx.words_out, ctx.gb1, ctx.gb2, ctx.dshift, 0, ctx.words_cap};
-    const char *ws = (const char *)plan_ws;
-    const auto *off = (const unsigned long long *)(ws + p.off_off);
-    const auto *cur2 = (const unsigned long long *)(ws + p.cur2_off);
-    const auto *wbeg = (const unsigned long long *)(ws + p.wbeg_off);
-    const int cap_k = mini_cap(t->k);
-    const unsigned long long *n_short = cap_k > SHORT_MAX ? cur2 : (const unsigned long long *)nullptr;
-    const unsigned nb = 1u << p.bits;
-    hipStream_t s = (hipStream_t)stream;
-#define PG_LOOKUP_SLICE_M(CAP_, DIG_)                                                                                       \
-    do {                                                                                                                    \
-        const size_t lds_ = MergeLds<BIG_BLOCK, DIG_>::END;                                                                 \
-        if ((rc = raise_lds_limit((const void *)(mini_lookup_slice_merge_kernel<CAP_, BIG_BLOCK, DIG_>), lds_, "pg_mini_lookup_piece"))) return rc; \
-        hipLaunchKernelGGL((mini_lookup_slice_merge_kernel<CAP_, BIG_BLOCK, DIG_>), dim3(nb), dim3(BIG_BLOCK), lds_, s, off, n_short, wbeg, mini_view(t), \
-                           (uint32_t)window, (uint32_t)vsize, ctx.vbits, (const uint32_t *)merge_ws, meta, sh, status);     \
-    } while (0)
-#define PG_LOOKUP_SLICE_MC(CAP_) do { if (ctx.gb1 > 10) PG_LOOKUP_SLICE_M(CAP_, 2048); else PG_LOOKUP_SLICE_M(CAP_, 1024); } while (0)
-    switch (cap_k) {
-    case 1: case 2: case 3: case 4: PG_LOOKUP_SLICE_MC(4); break;
-    case 5: case 6: PG_LOOKUP_SLICE_MC(6); break;
-    case 7: case 8: PG_LOOKUP_SLICE_MC(8); break;
-    default: PG_LOOKUP_SLICE_MC(9); break;
-    }
-#undef PG_LOOKUP_SLICE_MC
-#undef PG_LOOKUP_SLICE_M
-    return check_launch("pg_mini_lookup_piece");
+    LookupPrep l;
+    if ((rc = lookup_prepare(t, rows, plan_ws, plan_ws_bytes, n_words_piece, "n_words_piece", n_words_total, vsize, shuffle_ws, shuffle_ws_bytes, stream, Lookups::merged, Regions::begun, who, &l))) return rc;
+    const LookupGeom g = merged_lookup_geom(t, l.ctx.gb1, false);
+    rc = with_cap(mini_cap(t->k), [&](auto cap_c) {
+        auto go = [&](auto dig) {
+            constexpr int CAP = decltype(cap_c)::value, DIG = decltype(dig)::value;
+            return launch(mini_lookup_slice_merge_kernel<CAP, BIG_BLOCK, DIG>, dim3(l.nb), dim3(BIG_BLOCK), MergeLds<BIG_BLOCK, DIG>::END, (hipStream_t)stream, who,
+                          l.plan.off, l.n_short, l.plan.wbeg, mini_view(t), window, vsize, l.ctx.vbits, (const uint32_t *)merge_ws, meta, l.sh, status);
+        };
+        return g.dig == 2048 ? go(int_tag<2048>{}) : go(int_tag<1024>{});      // (one workgroup per CU: the slots are warm in L2 here)
+    });
+    return rc ? rc : check_launch(who);
 }
 
 // dwords of the merged form's provisional buffer (pg_mini_count's merge_ws): a halfword per k-mer slot of every batch of 64
@@ -2853,8 +2955,7 @@ extern "C" int64_t pg_mini_merge_words(int64_t n_words, int64_t n_records, int64
     if (rc) return rc;
     if (n_words < 0 || n_records < 0 || n_long_records < 0 || n_long_records > n_records) return pg_fail(PG_EINVAL, "pg_mini_merge_words: bad counts");
     const int64_t nb = (int64_t)1 << (t->log2_slots - t->log2_bucket_slots);
-    const int cap = mini_cap(t->k);
-    const int cap_t = cap <= 4 ? 4 : cap <= 6 ? 6 : cap <= 8 ? 8 : 9;           // (the kernels' instantiations)
+    const int cap_t = cap_class(mini_cap(t->k));                     // (the kernels' instantiations)
     MiniPlan p;
     plan_mini(t, n_words, &p);
     const bool two = cap_t > SHORT_MAX && p.bits2 > 0;               // (without a second scatter pass the classes are not sorted apart: all "long")
@@ -2865,24 +2966,7 @@ extern "C" int64_t pg_mini_merge_words(int64_t n_words, int64_t n_records, int64
     return (fixed + 32 * 16 + 255) / 256 * 256;
 }
 
-// ---- N > 1 ranks (see the kernels above): workspace of the count half: entry slabs | occupancy bitmaps | ring counts
-namespace {
-struct MiniHalfLayout { size_t ent_off, occ_off, ring_off, total; };
-MiniHalfLayout mini_half_layout(const pg_table *t)
-{
-    const size_t nb = (size_t)1 << (t->log2_slots - t->log2_bucket_slots), n_slots = (size_t)1 << t->log2_bucket_slots;
-    const size_t n_occ = n_slots >= 64 ? n_slots / 64 : 1;
-    MiniHalfLayout l;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) / 256 * 256; return at; };
-    l.ent_off = take(nb * n_slots * 8);
-    l.occ_off = take(nb * n_occ * 8);
-    l.ring_off = take(nb * 4);
-    l.total = o;
-    return l;
-}
-}  // namespace
-
+// ---- N > 1 ranks (see the kernels above)
 extern "C" int64_t pg_mini_half_bytes(const pg_table *local)
 {
     int rc = check_mini(local, "pg_mini_half_bytes");
@@ -2890,21 +2974,17 @@ extern "C" int64_t pg_mini_half_bytes(const pg_table *local)
     return (int64_t)mini_half_layout(local).total;
 }
 
-static int mini_count_half_impl(const uint64_t *codes, const uint32_t *valid, const uint32_t *tabv, int64_t word_begin, int64_t word_end, const pg_table *local,
-                                const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
-                                int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
-                                void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream)
+// accum: see HalfArgs (0: one launch; else a piece, for `who` = pg_mini_count_half_piece)
+static int mini_count_half_impl(CountArgs a, void *half_ws, int64_t half_ws_bytes, int64_t *fill, int accum, const char *who)
 {
-    int rc = check_mini(local, "pg_mini_count_half");
+    int rc = check_mini(a.t, who);
     if (rc) return rc;
-    if (!half_ws || !fill) return pg_fail(PG_EINVAL, "pg_mini_count_half: null argument");
-    const MiniHalfLayout hl = mini_half_layout(local);
-    if ((int64_t)hl.total > half_ws_bytes || (reinterpret_cast<uintptr_t>(half_ws) & 255) != 0)
-        return pg_fail(PG_EINVAL, "pg_mini_count_half: workspace of %lld bytes (256-byte aligned), %lld needed", (long long)half_ws_bytes, (long long)hl.total);
-    char *hw = (char *)half_ws;
-    const HalfArgs hv{(unsigned long long *)(hw + hl.ent_off), (unsigned long long *)(hw + hl.occ_off), (long long *)fill, (uint32_t *)(hw + hl.ring_off), 0, nullptr};
-    return mini_count_impl(codes, valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize, shuffle_ws,
-                           shuffle_ws_bytes, status, stream, &hv, merge_ws, merge_ws_words, tabv);
+    if (!half_ws || !fill) return pg_fail(PG_EINVAL, "%s: null argument", who);
+    HalfView h;
+    if ((rc = half_view(a.t, half_ws, half_ws_bytes, who, &h))) return rc;
+    const HalfArgs hv{h.ent, h.occ, (long long *)fill, h.ring, accum, nullptr};
+    a.half = &hv;
+    return mini_count_impl(a);
 }
 
 extern "C" int pg_mini_count_half(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
@@ -2912,8 +2992,8 @@ extern "C" int pg_mini_count_half(const uint64_t *codes, const uint32_t *valid, 
                                   int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
                                   void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream)
 {
-    return mini_count_half_impl(codes, valid, nullptr, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
-                                shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, status, stream);
+    return mini_count_half_impl(CountArgs{codes, valid, nullptr, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                          shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, nullptr, status, stream}, half_ws, half_ws_bytes, fill, 0, "pg_mini_count_half");
 }
 
 extern "C" int pg_mini_count_half_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
@@ -2921,8 +3001,8 @@ extern "C" int pg_mini_count_half_masked(const uint64_t *codes, const uint32_t *
                                          int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
                                          void *half_ws, int64_t half_ws_bytes, int64_t *fill, uint32_t *status, void *stream)
 {
-    return mini_count_half_impl(codes, valid, table_valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
-                                shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, status, stream);
+    return mini_count_half_impl(CountArgs{codes, valid, table_valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                          shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, nullptr, status, stream}, half_ws, half_ws_bytes, fill, 0, "pg_mini_count_half");
 }
 
 extern "C" int pg_mini_gather_entries(const pg_table *local, const void *half_ws, int64_t half_ws_bytes, const int64_t *fill,
@@ -2931,11 +3011,10 @@ extern "C" int pg_mini_gather_entries(const pg_table *local, const void *half_ws
     int rc = check_mini(local, "pg_mini_gather_entries");
     if (rc) return rc;
     if (!half_ws || !fill || !dst_elem || !out || !status || out_elems < 0) return pg_fail(PG_EINVAL, "pg_mini_gather_entries: null argument");
-    const MiniHalfLayout hl = mini_half_layout(local);
-    if ((int64_t)hl.total > half_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_gather_entries: workspace does not match the table");
+    ConstHalfView h;
+    if ((rc = half_view(local, half_ws, half_ws_bytes, "pg_mini_gather_entries", &h))) return rc;
     const unsigned nb = 1u << (local->log2_slots - local->log2_bucket_slots);
-    hipLaunchKernelGGL(mini_gather_entries_kernel, dim3(nb), dim3(BLOCK), 0, (hipStream_t)stream,
-                       (const unsigned long long *)((const char *)half_ws + hl.ent_off), local->log2_bucket_slots, (const long long *)fill,
+    hipLaunchKernelGGL(mini_gather_entries_kernel, dim3(nb), dim3(BLOCK), 0, (hipStream_t)stream, h.ent, local->log2_bucket_slots, (const long long *)fill,
                        (const long long *)dst_elem, (unsigned long long *)out, (unsigned long long)out_elems, status);
     return check_launch("pg_mini_gather_entries");
 }
@@ -2950,18 +3029,12 @@ static int mini_merge_bins_impl(bool masked, const uint64_t *recv, int64_t part_
     if (!recv || !seg || !bins_out || !status || n_parts < 1 || bucket_begin < 0 || bucket_end < bucket_begin || bucket_end > nb || window < 1 || vsize < 1)
         return pg_fail(PG_EINVAL, "pg_mini_merge_bins: bad arguments");
     if (bucket_end == bucket_begin) return PG_OK;
-    const size_t lds = (size_t)8 << t->log2_bucket_slots;
-#define PG_MINI_LAUNCH_MERGE(MASKED_)                                                                                       \
-    do {                                                                                                                    \
-        if ((rc = raise_lds_limit((const void *)mini_merge_bins_kernel<MASKED_>, lds, "pg_mini_merge_bins"))) return rc;    \
-        hipLaunchKernelGGL(mini_merge_bins_kernel<MASKED_>, dim3((unsigned)(bucket_end - bucket_begin)), dim3(BIG_BLOCK), lds, (hipStream_t)stream, \
-                           (const unsigned long long *)recv, (long long)part_stride, (const long long *)seg, n_parts, (int)(bucket_end - bucket_begin), \
-                           mini_view(t), (long long)bucket_begin, (uint32_t)window, (uint32_t)vsize, bins_out, status);    \
-    } while (0)
-    if (masked) PG_MINI_LAUNCH_MERGE(true);
-    else PG_MINI_LAUNCH_MERGE(false);
-#undef PG_MINI_LAUNCH_MERGE
-    return check_launch("pg_mini_merge_bins");
+    rc = with_flag(masked, [&](auto m) {
+        return launch(mini_merge_bins_kernel<decltype(m)::value>, dim3((unsigned)(bucket_end - bucket_begin)), dim3(BIG_BLOCK), (size_t)8 << t->log2_bucket_slots,
+                      (hipStream_t)stream, "pg_mini_merge_bins", (const unsigned long long *)recv, part_stride, (const long long *)seg, n_parts,
+                      (int)(bucket_end - bucket_begin), mini_view(t), bucket_begin, window, vsize, bins_out, status);
+    });
+    return rc ? rc : check_launch("pg_mini_merge_bins");
 }
 
 extern "C" int pg_mini_merge_bins(const uint64_t *recv, int64_t part_stride, const int64_t *seg, int n_parts, const pg_table *t,
@@ -2982,109 +3055,57 @@ extern "C" int pg_mini_lookup_half(const pg_table *local, const pg_rows *rows, c
                                    const void *half_ws, int64_t half_ws_bytes,
                                    const uint16_t *bins_in, const int64_t *bin_elem, uint32_t *status, void *stream)
 {
-    int rc = check_mini(local, "pg_mini_lookup_half");
+    const char *who = "pg_mini_lookup_half";
+    int rc = check_mini(local, who);
     if (rc) return rc;
     if (!rows || !plan_ws || !shuffle_ws || !half_ws || !bins_in || !bin_elem || !status) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: null argument");
-    if ((rc = check_mini_rows(rows, "pg_mini_lookup_half"))) return rc;
+    if ((rc = check_mini_rows(rows, who))) return rc;
     if (local->kind != PG_TABLE_MINI || !mini_slots_form(local, rows)) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: not the slot form");
-    MiniPlan p;
-    plan_mini(local, n_words_counted, &p);
-    if ((int64_t)p.total > plan_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: plan workspace does not match n_words_counted");
-    const MiniHalfLayout hl = mini_half_layout(local);
-    if ((int64_t)hl.total > half_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: workspace does not match the table");
-    const char *ws = (const char *)plan_ws;
-    const auto *kwords = (const unsigned long long *)(ws + p.kw_off);
-    const auto *wbeg = (const unsigned long long *)(ws + p.wbeg_off);
-    if (!p.bits2) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: needs more than 256 buckets");
-    // the row shuffle's regions: offsets and cursors as the count half's launch prepared them (same layout call)
-    pg_shuffle_ctx ctx;
+    ConstHalfView h;
+    if ((rc = half_view(local, half_ws, half_ws_bytes, who, &h))) return rc;
     const bool merge = merge_ws && merge_ws_words > 0 && mini_merge_form(local, rows, vsize);         // (as the count half decided)
-    if ((rc = pg_internal_shuffle_prepare(n_words_counted * 32, rows, vsize, shuffle_ws, shuffle_ws_bytes, stream, &ctx, MINI_ONE_PASS_BITS, merge ? 1 : 0))) return rc;
-    if (ctx.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: %d first-pass digits of the row shuffle", ctx.gb1);
-    const ShufArgs sh{ctx.goff, ctx.gcur1, ctx.words_out, ctx.gb1, ctx.gb2, ctx.dshift, merge ? 0 : ctx.narrow, ctx.words_cap};
-    const unsigned nb = 1u << p.bits;
-    const auto *occ = (const unsigned long long *)((const char *)half_ws + hl.occ_off);
+    ConstRecView rec{};
     if (merge) {
         // (the merged form reads the records' meta words again: lengths and rows say which provisional slots mean anything)
         if (!rec_ws) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: the merged form needs the count half's record workspace");
-        const size_t rcap = mini_rec_cap(rec_ws_bytes, (size_t)1 << p.bits);
-        if (rcap < 256) return pg_fail(PG_EINVAL, "pg_mini_lookup_half: record workspace of %lld bytes (pg_mini_records_bytes)", (long long)rec_ws_bytes);
-        const uint32_t *meta_b = (const uint32_t *)((const uint64_t *)rec_ws + 2 * rcap) + rcap;     // [bases A | bases B | meta A | meta B]
-        const auto *off = (const unsigned long long *)(ws + p.off_off);
-        const auto *cur2 = (const unsigned long long *)(ws + p.cur2_off);
-        const auto *ring = (const uint32_t *)((const char *)half_ws + hl.ring_off);
-        const int cap_k = mini_cap(local->k);
-        const unsigned long long *n_short = cap_k > SHORT_MAX ? cur2 : (const unsigned long long *)nullptr;
-        hipStream_t s2 = (hipStream_t)stream;
-#define PG_LOOKUP_HALF_M(CAP_, DIG_)                                                                                        \
-        do {                                                                                                                \
-            const size_t lds_ = MergeLds<BIG_BLOCK, DIG_>::END;                                                             \
-            if ((rc = raise_lds_limit((const void *)(mini_lookup_half_merge_kernel<CAP_, BIG_BLOCK, DIG_>), lds_, "pg_mini_lookup_half"))) return rc; \
-            hipLaunchKernelGGL((mini_lookup_half_merge_kernel<CAP_, BIG_BLOCK, DIG_>), dim3(nb), dim3(BIG_BLOCK), lds_, s2, off, n_short, wbeg, ring, occ, \
-                               bins_in, (const long long *)bin_elem, local->log2_bucket_slots, ctx.vbits, (const uint32_t *)merge_ws, meta_b, sh, status); \
-        } while (0)
-        // buckets of at most 2^13 slots (what a rank's own reads need at 4+ ranks): 512-thread workgroups, two per CU -- this kernel
-        // starts cold (bins, meta words and provisional slots all come from HBM, where the one-GPU kernel's lookup phase finds
-        // them in L2), and a second workgroup on the CU hides what one alone waits for: 7.8 -> 5.9 ms, rehearsed 8-rank step
-        // 34.3 -> 32.3 ms on one box (PG_LOOKUP_HALF_1024=1: the one-workgroup form)
-#define PG_LOOKUP_HALF_M5(CAP_)                                                                                             \
-        do {                                                                                                                \
-            const size_t lds_ = MergeLds<512, 1024>::END;                                                                   \
-            if ((rc = raise_lds_limit((const void *)(mini_lookup_half_merge_kernel<CAP_, 512, 1024>), lds_, "pg_mini_lookup_half"))) return rc; \
-            hipLaunchKernelGGL((mini_lookup_half_merge_kernel<CAP_, 512, 1024>), dim3(nb), dim3(512), lds_, s2, off, n_short, wbeg, ring, occ, \
-                               bins_in, (const long long *)bin_elem, local->log2_bucket_slots, ctx.vbits, (const uint32_t *)merge_ws, meta_b, sh, status); \
-        } while (0)
-#define PG_LOOKUP_HALF_MC(CAP_) do { if (ctx.gb1 > 10) PG_LOOKUP_HALF_M(CAP_, 2048); else if (local->log2_bucket_slots <= 13 && !getenv("PG_LOOKUP_HALF_1024")) PG_LOOKUP_HALF_M5(CAP_); else PG_LOOKUP_HALF_M(CAP_, 1024); } while (0)
-        switch (cap_k) {
-        case 1: case 2: case 3: case 4: PG_LOOKUP_HALF_MC(4); break;
-        case 5: case 6: PG_LOOKUP_HALF_MC(6); break;
-        case 7: case 8: PG_LOOKUP_HALF_MC(8); break;
-        default: PG_LOOKUP_HALF_MC(9); break;
-        }
-#undef PG_LOOKUP_HALF_MC
-#undef PG_LOOKUP_HALF_M5
-#undef PG_LOOKUP_HALF_M
-        return check_launch("pg_mini_lookup_half");
+        if ((rc = rec_view(rec_ws, rec_ws_bytes, who, &rec))) return rc;
     }
-    // 1024-thread workgroups whatever the bucket size: tiles of 16 Ki words keep the runs per row group at 32 bytes -- with
-    // 512 threads (8 Ki-word tiles, two workgroups per CU) this kernel took 14.1 ms where the one-GPU kernel's lookup phase
-    // takes 8.5 (PG_LOOKUP_HALF_512=1: that form, for comparison)
-    const bool half_block = local->log2_bucket_slots <= 13 && ctx.gb1 <= 10 && getenv("PG_LOOKUP_HALF_512");
-    hipStream_t s = (hipStream_t)stream;
-#define PG_LOOKUP_HALF(BLK_, DIG_)                                                                                          \
-    do {                                                                                                                    \
-        const size_t lds_ = LookupLds<BLK_, DIG_>::END;                                                                     \
-        if ((rc = raise_lds_limit((const void *)(mini_lookup_half_kernel<BLK_, DIG_>), lds_, "pg_mini_lookup_half"))) return rc; \
-        hipLaunchKernelGGL((mini_lookup_half_kernel<BLK_, DIG_>), dim3(nb), dim3(BLK_), lds_, s, kwords, wbeg, occ, bins_in, (const long long *)bin_elem, \
-                           local->log2_bucket_slots, ctx.vbits, (const uint32_t *)ctx.words_in, sh, status);                \
-    } while (0)
-    if (half_block) PG_LOOKUP_HALF(512, 1024);
-    else if (ctx.gb1 > 10) PG_LOOKUP_HALF(BIG_BLOCK, 2048);
-    else PG_LOOKUP_HALF(BIG_BLOCK, 1024);
-#undef PG_LOOKUP_HALF
-    return check_launch("pg_mini_lookup_half");
+    // the row shuffle's regions: offsets and cursors as the count half's launch prepared them (same layout call)
+    LookupPrep l;
+    if ((rc = lookup_prepare(local, rows, plan_ws, plan_ws_bytes, n_words_counted, "n_words_counted", n_words_counted, vsize, shuffle_ws, shuffle_ws_bytes, stream, merge ? Lookups::merged : Lookups::word_wise, Regions::prepare, who, &l))) return rc;
+    if (merge) {
+        const LookupGeom g = merged_lookup_geom(local, l.ctx.gb1, true);
+        rc = with_cap(mini_cap(local->k), [&](auto cap_c) {
+            return with_lookup_geom(g.blk, g.dig, [&](auto geom) {
+                using G = decltype(geom);
+                return launch(mini_lookup_half_merge_kernel<decltype(cap_c)::value, G::BLK, G::DIG>, dim3(l.nb), dim3(G::BLK), MergeLds<G::BLK, G::DIG>::END, (hipStream_t)stream, who,
+                              l.plan.off, l.n_short, l.plan.wbeg, h.ring, h.occ, bins_in, (const long long *)bin_elem, local->log2_bucket_slots, l.ctx.vbits,
+                              (const uint32_t *)merge_ws, rec.meta_b, l.sh, status);
+            });
+        });
+    } else {
+        // 1024-thread workgroups whatever the bucket size: tiles of 16 Ki words keep the runs per row group at 32 bytes -- with
+        // 512 threads (8 Ki-word tiles, two workgroups per CU) this kernel took 14.1 ms where the one-GPU kernel's lookup phase
+        // takes 8.5 (PG_LOOKUP_HALF_512=1: that form, for comparison)
+        const bool half_block = local->log2_bucket_slots <= 13 && l.ctx.gb1 <= 10 && getenv("PG_LOOKUP_HALF_512");
+        rc = with_lookup_geom(half_block ? 512 : BIG_BLOCK, l.ctx.gb1 > 10 ? 2048 : 1024, [&](auto geom) {
+            using G = decltype(geom);
+            return launch(mini_lookup_half_kernel<G::BLK, G::DIG>, dim3(l.nb), dim3(G::BLK), LookupLds<G::BLK, G::DIG>::END, (hipStream_t)stream, who, l.plan.kwords, l.plan.wbeg, h.occ,
+                          bins_in, (const long long *)bin_elem, local->log2_bucket_slots, l.ctx.vbits, l.ctx.words_in, l.sh, status);
+        });
+    }
+    return rc ? rc : check_launch(who);
 }
 
 // ---- the count half in pieces (N > 1 ranks; see HalfArgs): `local` has real slots here (2^log2_slots words), which the pieces
 // count into; the last piece leaves entries, occupancy and fill in half_ws as one pg_mini_count_half would
-static int mini_count_half_piece_impl(const uint64_t *codes, const uint32_t *valid, const uint32_t *tabv, int64_t word_begin, int64_t word_end,
-                                      const pg_table *local, const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
-                                      int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
-                                      int64_t *fill, int first, int last, uint32_t *status, void *stream)
+static int mini_count_half_piece_impl(CountArgs a, void *half_ws, int64_t half_ws_bytes, int64_t *fill, int first, int last)
 {
-    int rc = check_mini(local, "pg_mini_count_half_piece");
+    int rc = check_mini(a.t, "pg_mini_count_half_piece");
     if (rc) return rc;
-    if (local->kind != PG_TABLE_MINI) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: packed mini tables (13 <= k <= %d)", PG_HASH_MAX_K);
-    if (window < 1 || vsize < 1 || !merge_ws || merge_ws_words <= 0) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: needs the abundance parameters and the slot buffer");
-    if (!half_ws || !fill) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: null argument");
-    const MiniHalfLayout hl = mini_half_layout(local);
-    if ((int64_t)hl.total > half_ws_bytes || (reinterpret_cast<uintptr_t>(half_ws) & 255) != 0)
-        return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: workspace of %lld bytes (256-byte aligned), %lld needed", (long long)half_ws_bytes, (long long)hl.total);
-    char *hw = (char *)half_ws;
-    const int accum = first ? (last ? 4 : 1) : (last ? 3 : 2);
-    const HalfArgs hv{(unsigned long long *)(hw + hl.ent_off), (unsigned long long *)(hw + hl.occ_off), (long long *)fill, (uint32_t *)(hw + hl.ring_off), accum, nullptr};
-    return mini_count_impl(codes, valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize, nullptr, 0,
-                           status, stream, &hv, merge_ws, merge_ws_words, tabv);
+    if (a.t->kind != PG_TABLE_MINI) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: packed mini tables (13 <= k <= %d)", PG_HASH_MAX_K);
+    if (a.window < 1 || a.vsize < 1 || !a.merge_ws || a.merge_ws_words <= 0) return pg_fail(PG_EINVAL, "pg_mini_count_half_piece: needs the abundance parameters and the slot buffer");
+    return mini_count_half_impl(a, half_ws, half_ws_bytes, fill, first ? (last ? 4 : 1) : (last ? 3 : 2), "pg_mini_count_half_piece");
 }
 
 extern "C" int pg_mini_count_half_piece(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *local,
@@ -3092,8 +3113,8 @@ extern "C" int pg_mini_count_half_piece(const uint64_t *codes, const uint32_t *v
                                         int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
                                         int64_t *fill, int first, int last, uint32_t *status, void *stream)
 {
-    return mini_count_half_piece_impl(codes, valid, nullptr, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
-                                      merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, first, last, status, stream);
+    return mini_count_half_piece_impl(CountArgs{codes, valid, nullptr, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                                nullptr, 0, merge_ws, merge_ws_words, nullptr, status, stream}, half_ws, half_ws_bytes, fill, first, last);
 }
 
 extern "C" int pg_mini_count_half_piece_masked(const uint64_t *codes, const uint32_t *valid, const uint32_t *table_valid, int64_t word_begin, int64_t word_end,
@@ -3101,8 +3122,8 @@ extern "C" int pg_mini_count_half_piece_masked(const uint64_t *codes, const uint
                                                int window, int vsize, void *merge_ws, int64_t merge_ws_words, void *half_ws, int64_t half_ws_bytes,
                                                int64_t *fill, int first, int last, uint32_t *status, void *stream)
 {
-    return mini_count_half_piece_impl(codes, valid, table_valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
-                                      merge_ws, merge_ws_words, half_ws, half_ws_bytes, fill, first, last, status, stream);
+    return mini_count_half_piece_impl(CountArgs{codes, valid, table_valid, word_begin, word_end, local, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                                                nullptr, 0, merge_ws, merge_ws_words, nullptr, status, stream}, half_ws, half_ws_bytes, fill, first, last);
 }
 
 // the lookups of one piece of a count half in pieces, once the bins are back: plan_ws / meta / merge_ws of that piece (as for
@@ -3113,50 +3134,27 @@ extern "C" int pg_mini_lookup_half_piece(const pg_table *local, const pg_rows *r
                                          const void *merge_ws, const void *half_ws, int64_t half_ws_bytes,
                                          const uint16_t *bins_in, const int64_t *bin_elem, uint32_t *status, void *stream)
 {
-    int rc = check_mini(local, "pg_mini_lookup_half_piece");
+    const char *who = "pg_mini_lookup_half_piece";
+    int rc = check_mini(local, who);
     if (rc) return rc;
     if (local->kind != PG_TABLE_MINI || !rows || !plan_ws || !meta || !shuffle_ws || !merge_ws || !half_ws || !bins_in || !bin_elem || !status || vsize < 1)
         return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: bad argument");
-    if ((rc = check_mini_rows(rows, "pg_mini_lookup_half_piece"))) return rc;
+    if ((rc = check_mini_rows(rows, who))) return rc;
     if (!mini_merge_form(local, rows, vsize)) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: the merged lookups do not apply to these rows");
-    MiniPlan p;
-    plan_mini(local, n_words_piece, &p);
-    if ((int64_t)p.total > plan_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: plan workspace does not match n_words_piece");
-    if (!p.bits2) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: needs more than 256 buckets");
-    const MiniHalfLayout hl = mini_half_layout(local);
-    if ((int64_t)hl.total > half_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: workspace does not match the table");
-    pg_shuffle_ctx ctx;
-    if ((rc = pg_internal_shuffle_prepare(n_words_total * 32, rows, vsize, shuffle_ws, shuffle_ws_bytes, stream, &ctx, MINI_ONE_PASS_BITS, 1, 1))) return rc;
-    if (ctx.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "pg_mini_lookup_half_piece: %d first-pass digits of the row shuffle", ctx.gb1);
-    const ShufArgs sh{ctx.goff, ctx.gcur1, ctx.words_out, ctx.gb1, ctx.gb2, ctx.dshift, 0, ctx.words_cap};
-    const char *ws = (const char *)plan_ws;
-    const auto *off = (const unsigned long long *)(ws + p.off_off);
-    const auto *cur2 = (const unsigned long long *)(ws + p.cur2_off);
-    const auto *wbeg = (const unsigned long long *)(ws + p.wbeg_off);
-    const auto *occ = (const unsigned long long *)((const char *)half_ws + hl.occ_off);
-    const auto *ring = (const uint32_t *)((const char *)half_ws + hl.ring_off);
-    const int cap_k = mini_cap(local->k);
-    const unsigned long long *n_short = cap_k > SHORT_MAX ? cur2 : (const unsigned long long *)nullptr;
-    const unsigned nb = 1u << p.bits;
-    hipStream_t s = (hipStream_t)stream;
-    // (the workgroup geometry of pg_mini_lookup_half's merged form)
-#define PG_LOOKUP_HALF_P(CAP_, BLK_, DIG_)                                                                                  \
-    do {                                                                                                                    \
-        const size_t lds_ = MergeLds<BLK_, DIG_>::END;                                                                      \
-        if ((rc = raise_lds_limit((const void *)(mini_lookup_half_merge_kernel<CAP_, BLK_, DIG_, true>), lds_, "pg_mini_lookup_half_piece"))) return rc; \
-        hipLaunchKernelGGL((mini_lookup_half_merge_kernel<CAP_, BLK_, DIG_, true>), dim3(nb), dim3(BLK_), lds_, s, off, n_short, wbeg, ring, occ, \
-                           bins_in, (const long long *)bin_elem, local->log2_bucket_slots, ctx.vbits, (const uint32_t *)merge_ws, meta, sh, status); \
-    } while (0)
-#define PG_LOOKUP_HALF_PC(CAP_) do { if (ctx.gb1 > 10) PG_LOOKUP_HALF_P(CAP_, BIG_BLOCK, 2048); else if (local->log2_bucket_slots <= 13 && !getenv("PG_LOOKUP_HALF_1024")) PG_LOOKUP_HALF_P(CAP_, 512, 1024); else PG_LOOKUP_HALF_P(CAP_, BIG_BLOCK, 1024); } while (0)
-    switch (cap_k) {
-    case 1: case 2: case 3: case 4: PG_LOOKUP_HALF_PC(4); break;
-    case 5: case 6: PG_LOOKUP_HALF_PC(6); break;
-    case 7: case 8: PG_LOOKUP_HALF_PC(8); break;
-    default: PG_LOOKUP_HALF_PC(9); break;
-    }
-#undef PG_LOOKUP_HALF_PC
-#undef PG_LOOKUP_HALF_P
-    return check_launch("pg_mini_lookup_half_piece");
+    ConstHalfView h;
+    if ((rc = half_view(local, half_ws, half_ws_bytes, who, &h))) return rc;
+    LookupPrep l;
+    if ((rc = lookup_prepare(local, rows, plan_ws, plan_ws_bytes, n_words_piece, "n_words_piece", n_words_total, vsize, shuffle_ws, shuffle_ws_bytes, stream, Lookups::merged, Regions::begun, who, &l))) return rc;
+    const LookupGeom g = merged_lookup_geom(local, l.ctx.gb1, true);
+    rc = with_cap(mini_cap(local->k), [&](auto cap_c) {
+        return with_lookup_geom(g.blk, g.dig, [&](auto geom) {
+            using G = decltype(geom);
+            return launch(mini_lookup_half_merge_kernel<decltype(cap_c)::value, G::BLK, G::DIG, true>, dim3(l.nb), dim3(G::BLK), MergeLds<G::BLK, G::DIG>::END,
+                          (hipStream_t)stream, who, l.plan.off, l.n_short, l.plan.wbeg, h.ring, h.occ, bins_in, (const long long *)bin_elem,
+                          local->log2_bucket_slots, l.ctx.vbits, (const uint32_t *)merge_ws, meta, l.sh, status);
+        });
+    });
+    return rc ? rc : check_launch(who);
 }
 
 extern "C" int pg_mini_abundance_from_emitted(const pg_table *t, const pg_rows *rows, int vsize, int32_t *abd_out,
@@ -3167,15 +3165,13 @@ extern "C" int pg_mini_abundance_from_emitted(const pg_table *t, const pg_rows *
     if (rc) return rc;
     if (!rows || !abd_out || !plan_ws || !shuffle_ws) return pg_fail(PG_EINVAL, "pg_mini_abundance_from_emitted: null argument");
     if ((rc = check_mini_rows(rows, "pg_mini_abundance_from_emitted"))) return rc;
-    MiniPlan p;
-    plan_mini(t, n_words_counted, &p);
-    if ((int64_t)p.total > plan_ws_bytes) return pg_fail(PG_EINVAL, "pg_mini_abundance_from_emitted: plan workspace does not match n_words_counted");
-    if ((reinterpret_cast<uintptr_t>(shuffle_ws) & 255) != 0) return pg_fail(PG_EINVAL, "pg_mini_abundance_from_emitted: workspace must be 256-byte aligned");
+    ConstPlanView p;
+    if ((rc = plan_view(t, n_words_counted, plan_ws, plan_ws_bytes, "pg_mini_abundance_from_emitted", "n_words_counted", &p))) return rc;
+    if (misaligned(shuffle_ws)) return pg_fail(PG_EINVAL, "pg_mini_abundance_from_emitted: workspace must be 256-byte aligned");
     if (mini_slots_form(t, rows))        // the count kernel has scattered the words by row group already
         return pg_internal_shuffle_finish(n_words_counted * 32, rows, vsize, abd_out, shuffle_ws, shuffle_ws_bytes, stream,
                                           mini_merge_form(t, rows, vsize) ? PG_SHUFFLE_WORDS_COUNTED
                                           : pg_internal_shuffle_is_narrow(n_words_counted * 32, rows->n_rows, vsize, MINI_ONE_PASS_BITS) ? PG_SHUFFLE_WORDS_NARROW
                                           : PG_SHUFFLE_WORDS_PLAIN, MINI_ONE_PASS_BITS, mini_merge_form(t, rows, vsize) ? 1 : 0);
-    const auto *wbeg = (const unsigned long long *)((const char *)plan_ws + p.wbeg_off);
-    return pg_internal_shuffle_rows(wbeg, 1 << p.bits, n_words_counted * 32, rows, vsize, abd_out, shuffle_ws, shuffle_ws_bytes, stream);
+    return pg_internal_shuffle_rows(p.wbeg, 1 << p.bits, n_words_counted * 32, rows, vsize, abd_out, shuffle_ws, shuffle_ws_bytes, stream);
 }

@@ -459,7 +459,9 @@ def test_waits_for_rank0_use_the_control_plane():
 # ------------------------------------------------------------------ the super-k-mer form on N > 1 ranks (dist.MiniSharded)
 
 
-def _mini_cfg():
+def _mini_cfg(many_rows=False):
+    if many_rows:       # one pair per barcode: about 70 k rows of 302 characters (min_len 200)
+        return synth.SynthConfig(n_pairs=72_000, n_barcodes=72_000, n_genomes=3, genome_len=200_000, fragment=10_000, sub_rate=0.01, seed=77)
     return synth.SynthConfig(n_pairs=24_000, n_barcodes=150, n_genomes=3, genome_len=40_000, fragment=10_000, sub_rate=0.01, n_rate=0.05, seed=321)
 
 
@@ -468,7 +470,7 @@ def _shard_by_runs(s, rank, world):
     return pdist.shard_stream(ReadStream(s.codes.cpu(), s.valid.cpu(), s.n_chars, s.run_off, s.run_names), rank, world).to("cuda:0")
 
 
-def _mini_sharded_worker(rank, world, port, outdir, backend, saturate):
+def _mini_sharded_worker(rank, world, port, outdir, backend, saturate, many_rows=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(0)
@@ -486,9 +488,9 @@ def _mini_sharded_worker(rank, world, port, outdir, backend, saturate):
                                       ("c", rnd + b"N")], device="cuda:0")
             part = s
         else:
-            s = synth.generate(_mini_cfg(), device="cuda:0")
+            s = synth.generate(_mini_cfg(many_rows), device="cuda:0")
             part = _shard_by_runs(s, rank, world)
-        rows = part.rows(2000 if not saturate else 0)
+        rows = part.rows(0 if saturate else 200 if many_rows else 2000)
         plan = kmer.Plan(rows, "cuda:0")
         tnf, abd, ms = pdist.features_sharded_mini(part, plan, 21, 4, 10, 400)
         assert ms.local.n_buckets == ms.union.n_buckets >= 512 and ms.local.log2_bucket <= ms.union.log2_bucket
@@ -511,8 +513,8 @@ def _mini_sharded_worker(rank, world, port, outdir, backend, saturate):
         dist.destroy_process_group()
 
 
-def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False):
-    _spawn(_mini_sharded_worker, world, str(tmp_path), backend, saturate)
+def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False, many_rows=False):
+    _spawn(_mini_sharded_worker, world, str(tmp_path), backend, saturate, many_rows)
     parts = [np.load(str(tmp_path / f"m{r}.npz")) for r in range(world)]
     if saturate:
         rng = np.random.RandomState(3)
@@ -523,7 +525,7 @@ def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False):
         for _ in range(world):
             otab.count(text)                                 # every rank holds a copy of the same reads
     else:
-        s = synth.generate(_mini_cfg(), device="cuda:0")
+        s = synth.generate(_mini_cfg(many_rows), device="cuda:0")
         text = s.decode()
         otab = oracle.Table(21, threads=4).count(text)
     # the owners' ranges together are the oracle's table (counts saturate at 2^21 exactly as one rank's table would)
@@ -539,7 +541,8 @@ def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False):
                 assert np.array_equal(p["abd"][r], oracle.abd_row(text[rows.start[r]:rows.end[r]], 21, otab, 10, 400))
         return
     # the ranks' rows, in rank order, are the rows of the whole file
-    rows = s.rows(2000)
+    rows = s.rows(200 if many_rows else 2000)
+    assert not many_rows or min(len(p["names"]) for p in parts) > 65_536
     names = [n for p in parts for n in p["names"].tolist()]
     assert names == list(rows.names)
     abd = np.concatenate([p["abd"] for p in parts]); tnf = np.concatenate([p["tnf"] for p in parts])
@@ -559,6 +562,38 @@ def test_super_kmer_form_on_several_ranks(tmp_path, world):
     distinct k-mer), merged bins come back (2 bytes), the lookup half finishes: rows == the one-process rows == the oracle's, the
     owners' table ranges together == the oracle's table (3 ranks: uneven ranges)"""
     _check_mini_sharded(tmp_path, world)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("threads", ["1024", "512"])
+def test_super_kmer_form_with_word_wise_lookups_on_two_ranks(tmp_path, monkeypatch, threads):
+    """PG_MINI_MERGE=0: the count half without the merged words and the word-wise lookup half give the one-process rows and the
+    oracle's table as the merged forms do -- with 1024-thread workgroups in both halves (PG_COUNT_BLOCK=1024 for the count half, the
+    lookup half's own choice), and with 512 (the count half's own choice on these local buckets, PG_LOOKUP_HALF_512=1)"""
+    monkeypatch.setenv("PG_MINI_MERGE", "0")
+    monkeypatch.setenv("PG_COUNT_BLOCK" if threads == "1024" else "PG_LOOKUP_HALF_512", threads if threads == "1024" else "1")
+    _check_mini_sharded(tmp_path, 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form", ["word-wise", "merged", "merged-pieces"])
+def test_super_kmer_form_with_2048_row_group_digits(tmp_path, monkeypatch, form):
+    """more than 2^16 (and at most 2^17) rows on a rank: the lookup half scatters by 2048 row-group digits -- word-wise
+    (PG_MINI_MERGE=0), merged, and merged with the share counted in pieces (a one-rank RCCL group: the smallest input that has so
+    many rows on one rank)"""
+    if form == "word-wise":
+        monkeypatch.setenv("PG_MINI_MERGE", "0")
+    if form == "merged-pieces":
+        monkeypatch.setenv("PANGAEA_MINI_PIECE_WORDS", str(1 << 18))
+    _check_mini_sharded(tmp_path, 1, backend="nccl", many_rows=True)
+
+
+@pytest.mark.gpu
+def test_super_kmer_form_with_one_lookup_workgroup_per_cu(tmp_path, monkeypatch):
+    """PG_LOOKUP_HALF_1024=1: the merged lookup half in 1024-thread workgroups (what local buckets of 2^14 slots run) gives the rows
+    of the 512-thread form that these local buckets take by default"""
+    monkeypatch.setenv("PG_LOOKUP_HALF_1024", "1")
+    _check_mini_sharded(tmp_path, 2)
 
 
 @pytest.mark.gpu

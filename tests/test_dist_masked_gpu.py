@@ -187,6 +187,13 @@ def test_quality_masked_on_several_ranks(tmp_path, world):
 
 
 @pytest.mark.gpu
+def test_quality_masked_with_one_count_workgroup_per_cu(tmp_path, monkeypatch):
+    """PG_COUNT_BLOCK=1024: the masked count half in 1024-thread workgroups (what local buckets of 2^14 slots run)"""
+    monkeypatch.setenv("PG_COUNT_BLOCK", "1024")
+    _check(tmp_path, 2, "qual")
+
+
+@pytest.mark.gpu
 def test_soft_and_quality_masked_on_two_ranks(tmp_path):
     """lower-case bases counted (lowercase_is_base) and low-quality bases left out of the table: k-mers mixing the two kinds are
     neither counted nor looked up"""

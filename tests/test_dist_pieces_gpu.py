@@ -153,6 +153,13 @@ def test_pieces_on_several_ranks(tmp_path, world):
 
 
 @pytest.mark.gpu
+def test_share_counted_piecewise_with_one_lookup_workgroup_per_cu(tmp_path, monkeypatch):
+    """PG_LOOKUP_HALF_1024=1: the lookups of every piece in 1024-thread workgroups (what local buckets of 2^14 slots run)"""
+    monkeypatch.setenv("PG_LOOKUP_HALF_1024", "1")
+    _check(_run(tmp_path, 2), 2)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("piece_words", [0, 65_536])
 def test_more_than_2_17_rows_per_rank(tmp_path, piece_words):
     """about 157 k rows per rank (the row shuffle takes two scatter passes) stay in the super-k-mer form, in one piece and in pieces"""

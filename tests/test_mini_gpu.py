@@ -348,6 +348,39 @@ def test_one_pass_row_shuffle_for_every_row_count_it_reaches(n_rows, monkeypatch
     assert torch.equal(abd_w, want25) and torch.equal(abd_w1, want25)
 
 
+def test_word_wise_lookups_with_2048_row_group_digits(monkeypatch):
+    """more than 2^16 rows (2048 row-group digits in the lookup tiles): the word-wise lookups (PG_MINI_MERGE=0) of a packed and of a
+    wide table, and the merged lookups of a stream counted in pieces (pg_mini_lookup_piece), give the rows of the lookup kernel; so do
+    the wide table's word-wise lookups on a few of these rows (1024 digits)"""
+    n_rows = 70_000
+    rng = np.random.RandomState(n_rows)
+    text = bytes(rng.choice(list(b"ACGT"), size=4 * n_rows + 200).astype(np.uint8))
+    s = ReadStream.from_runs([("x", text)], device=DEV)
+    start = 50 + 4 * np.arange(n_rows, dtype=np.int64)
+    rows = Rows(np.zeros(n_rows, dtype=np.int64), [""] * n_rows, start, start + 4)
+    plan = kmer.Plan(rows, DEV)
+    want = {}
+    for k, kind in ((21, "hash"), (25, "wide")):
+        h = kmer.count_kmers(s, k, kind=kind)
+        want[k] = kmer.features(s, rows, k_tnf=None, table=h, window=1, vsize=8, seg_chars=32)[1]
+    assert int(want[21].sum()) == n_rows * 4
+
+    def rows_of(k, lb, log2_slots=20, in_pieces=False):
+        t = kmer.KmerTable.mini_with_slots(k, DEV, log2_slots, lb).count(s, rows=plan, emit=(1, 8))
+        assert (t._mini_pieces > 1) == in_pieces
+        return kmer.features(s, plan, k_tnf=None, table=t, window=1, vsize=8)[1]
+    assert torch.equal(rows_of(21, 14), want[21])                      # (merged, one count: the reference of the forms below)
+    monkeypatch.setenv("PANGAEA_MINI_PIECE_WORDS", "4096")              # three pieces (a table of more than 256 buckets: pieces apply)
+    assert torch.equal(rows_of(21, 14, 24, in_pieces=True), want[21])
+    monkeypatch.delenv("PANGAEA_MINI_PIECE_WORDS")
+    monkeypatch.setenv("PG_MINI_MERGE", "0")
+    assert torch.equal(rows_of(21, 14), want[21]) and torch.equal(rows_of(25, 13), want[25])
+    # the wide table's word-wise lookups with 1024 digits: the first 5000 of these rows
+    few = 5000
+    plan = kmer.Plan(Rows(np.zeros(few, dtype=np.int64), [""] * few, start[:few], start[:few] + 4), DEV)
+    assert torch.equal(rows_of(25, 13), want[25][:few])
+
+
 @pytest.mark.parametrize("force", ["5,7", "40,3", "1000,2"])
 def test_row_histograms_shared_among_workgroups_give_the_same_rows(force, monkeypatch):
     """the row groups of a last, mostly empty round of workgroups are histogrammed by several workgroups each, which add their
