@@ -470,7 +470,7 @@ def _shard_by_runs(s, rank, world):
     return pdist.shard_stream(ReadStream(s.codes.cpu(), s.valid.cpu(), s.n_chars, s.run_off, s.run_names), rank, world).to("cuda:0")
 
 
-def _mini_sharded_worker(rank, world, port, outdir, backend, saturate, many_rows=False):
+def _mini_sharded_worker(rank, world, port, outdir, backend, saturate, many_rows=False, k=21, window=10, vsize=400, form=False):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     torch.cuda.set_device(0)
@@ -492,14 +492,18 @@ def _mini_sharded_worker(rank, world, port, outdir, backend, saturate, many_rows
             part = _shard_by_runs(s, rank, world)
         rows = part.rows(0 if saturate else 200 if many_rows else 2000)
         plan = kmer.Plan(rows, "cuda:0")
-        tnf, abd, ms = pdist.features_sharded_mini(part, plan, 21, 4, 10, 400)
+        if form:                                              # (a collective: every rank asks)
+            from pangaea_amd import feature
+            assert feature._sharded_mini_applies(part, plan, k, window, vsize, False)
+        tnf, abd, ms = pdist.features_sharded_mini(part, plan, k, 4, window, vsize)
+        assert not form or (isinstance(ms, pdist.MiniSharded) and ms.local.k == ms.union.k == k and not ms.masked)
         assert ms.local.n_buckets == ms.union.n_buckets >= 512 and ms.local.log2_bucket <= ms.union.log2_bucket
         c, n = ms.owned_items()
         np.savez(os.path.join(outdir, f"m{rank}.npz"), c=c, n=n, tnf=tnf.cpu().numpy(), abd=abd.cpu().numpy(),
                  names=np.array(rows.names), sent=ms.bytes_sent)
         # counting again with the same object (what every bench step does) gives the same rows
         ms.count(part, plan)
-        _, abd2 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=10, vsize=400)
+        _, abd2 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=window, vsize=vsize)
         assert torch.equal(abd2, abd)
         # the exchange keeps the part size of the first batch and does not ask the device again: a batch that does not fit it is
         # not exchanged, the status word says so on every rank, and count() sizes and counts again
@@ -507,27 +511,27 @@ def _mini_sharded_worker(rank, world, port, outdir, backend, saturate, many_rows
         ms._cap1 = 8
         ms.count(part, plan)
         assert ms._cap1 == kept
-        _, abd3 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=10, vsize=400)
+        _, abd3 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=window, vsize=vsize)
         assert torch.equal(abd3, abd)
     finally:
         dist.destroy_process_group()
 
 
-def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False, many_rows=False):
-    _spawn(_mini_sharded_worker, world, str(tmp_path), backend, saturate, many_rows)
+def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False, many_rows=False, k=21, window=10, vsize=400, every_row=False):
+    _spawn(_mini_sharded_worker, world, str(tmp_path), backend, saturate, many_rows, k, window, vsize, every_row)
     parts = [np.load(str(tmp_path / f"m{r}.npz")) for r in range(world)]
     if saturate:
         rng = np.random.RandomState(3)
         rnd = bytes(rng.choice(list(b"ACGT"), size=60_000).astype(np.uint8))
         s = ReadStream.from_runs([("a", b"A" * 1_600_000 + b"N" + b"T" * 1_500_040 + b"N"), ("b", b"ACG" * 30_000 + b"N"), ("c", rnd + b"N")], device="cuda:0")
         text = s.decode()
-        otab = oracle.Table(21, threads=4)
+        otab = oracle.Table(k, threads=4)
         for _ in range(world):
             otab.count(text)                                 # every rank holds a copy of the same reads
     else:
         s = synth.generate(_mini_cfg(many_rows), device="cuda:0")
         text = s.decode()
-        otab = oracle.Table(21, threads=4).count(text)
+        otab = oracle.Table(k, threads=4).count(text)
     # the owners' ranges together are the oracle's table (counts saturate at 2^21 exactly as one rank's table would)
     codes = np.concatenate([p["c"] for p in parts]); counts = np.concatenate([p["n"] for p in parts])
     order = np.argsort(codes)
@@ -538,7 +542,7 @@ def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False, many_ro
         rows = s.rows(0)
         for p in parts:                                       # every rank has the rows of the whole text, looked up in the summed table
             for r in range(len(rows)):
-                assert np.array_equal(p["abd"][r], oracle.abd_row(text[rows.start[r]:rows.end[r]], 21, otab, 10, 400))
+                assert np.array_equal(p["abd"][r], oracle.abd_row(text[rows.start[r]:rows.end[r]], k, otab, window, vsize))
         return
     # the ranks' rows, in rank order, are the rows of the whole file
     rows = s.rows(200 if many_rows else 2000)
@@ -547,11 +551,12 @@ def _check_mini_sharded(tmp_path, world, backend="gloo", saturate=False, many_ro
     assert names == list(rows.names)
     abd = np.concatenate([p["abd"] for p in parts]); tnf = np.concatenate([p["tnf"] for p in parts])
     plan = kmer.Plan(rows, "cuda:0")
-    one = kmer.count_kmers(s, 21, rows=plan, emit=(10, 400))
-    want_tnf, want_abd = kmer.features(s, plan, k_tnf=4, table=one, window=10, vsize=400)
+    one = kmer.count_kmers(s, k, rows=plan, emit=(window, vsize))
+    want_tnf, want_abd = kmer.features(s, plan, k_tnf=4, table=one, window=window, vsize=vsize)
     assert np.array_equal(abd, want_abd.cpu().numpy()) and np.array_equal(tnf, want_tnf.cpu().numpy())
-    for r in range(0, len(rows), max(1, len(rows) // 8)):
-        assert np.array_equal(abd[r], oracle.abd_row(text[rows.start[r]:rows.end[r]], 21, otab, 10, 400))
+    for r in range(0, len(rows), 1 if every_row else max(1, len(rows) // 8)):
+        assert np.array_equal(abd[r], oracle.abd_row(text[rows.start[r]:rows.end[r]], k, otab, window, vsize))
+        assert not every_row or np.array_equal(tnf[r], oracle.tnf_row(text[rows.start[r]:rows.end[r]], 4))
     assert world == 1 or all(int(p["sent"]) > 0 for p in parts)
 
 
@@ -607,6 +612,29 @@ def test_super_kmer_form_over_a_one_rank_rccl_group(tmp_path):
     _check_mini_sharded(tmp_path, 1, backend="nccl")
 
 
+# (window, vsize) of the cases at k < 21: k = 15 with the default flags, every pair at least once, window * vsize <= 2^21, vsize <= 512
+_KWV = {13: (1, 6), 14: (3, 64), 15: (10, 400), 16: (25, 512), 17: (2, 50), 18: (10, 400), 19: (1, 6), 20: (3, 64)}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,world,backend", [(k, 2, "gloo") for k in sorted(_KWV)] + [(15, 3, "gloo"), (16, 3, "gloo"), (15, 1, "nccl")])
+def test_super_kmer_form_at_every_k(tmp_path, k, world, backend):
+    """13 <= k <= 20: the count half, the owner merge, the entry gather and the merged lookup half in the instantiations for 4, 6 and
+    8 k-mers per record, the first pass for every window length and both minimizer lengths (11: k <= 15, 13: above) -- the owners'
+    ranges == the oracle's table, rows == the one-process rows, and EVERY row == the oracle's (three ranks: uneven owner ranges on
+    both sides of the minimizer switch; k = 15 also over the one-rank RCCL group)"""
+    _check_mini_sharded(tmp_path, world, backend=backend, k=k, window=_KWV[k][0], vsize=_KWV[k][1], every_row=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [14, 17, 19])
+def test_super_kmer_form_with_word_wise_lookups_at_every_cap(tmp_path, monkeypatch, k):
+    """PG_MINI_MERGE=0 at one k of each class of k-mers per record below 9 (4, 6, 8): the count half without the merged words and
+    the word-wise lookup half"""
+    monkeypatch.setenv("PG_MINI_MERGE", "0")
+    _check_mini_sharded(tmp_path, 2, k=k, window=_KWV[k][0], vsize=_KWV[k][1], every_row=True)
+
+
 @pytest.mark.gpu
 def test_super_kmer_form_through_the_checked_build():
     """the N-rank kernels (count half's entries and occupancy, entry gather, owner merge and bins, lookup half) with every global
@@ -617,7 +645,8 @@ def test_super_kmer_form_through_the_checked_build():
     from .conftest import ROOT
     env = dict(os.environ, PANGAEA_LIB="checked")
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.join(ROOT, "tests", "test_dist_gloo.py"),
-                        "-k", "(super_kmer_form_on_several_ranks and 2) or one_rank_rccl or saturating_counts"],
+                        "-k", "(super_kmer_form_on_several_ranks and 2) or one_rank_rccl or saturating_counts"
+                              " or (at_every_k and (14-2 or 15-2 or 17-2 or 19-2 or 15-1)) or at_every_cap"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout and "no tests ran" not in r.stdout

@@ -49,7 +49,7 @@ def _stream(case):
     return synth.generate(_small_cfg(), device="cuda:0"), 2000
 
 
-def _worker(rank, world, port, outdir, case, backend, piece_words, shrink):
+def _worker(rank, world, port, outdir, case, backend, piece_words, shrink, k=21, window=10, vsize=400):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     if piece_words:
@@ -67,7 +67,7 @@ def _worker(rank, world, port, outdir, case, backend, piece_words, shrink):
                                                                 rank, world).to("cuda:0")
         rows = part.rows(min_len)
         plan = kmer.Plan(rows, "cuda:0")
-        applies = feature._sharded_mini_applies(part, plan, 21, 10, 400, True)
+        applies = feature._sharded_mini_applies(part, plan, k, window, vsize, True)
         first_lb = None
         if shrink:
             # a local bucket two steps too small: the first count runs full, features_sharded_mini grows the geometry and counts again
@@ -79,8 +79,8 @@ def _worker(rank, world, port, outdir, case, backend, piece_words, shrink):
                 first_lb = max(4, lb_l - 2)
                 return log2_u, lb_u, first_lb
             pdist.MiniSharded.geometry = staticmethod(small)
-        tnf, abd, ms = pdist.features_sharded_mini(part, plan, 21, 4, 10, 400)
-        assert isinstance(ms, pdist.MiniSharded), "the key-partitioned fallback was taken"
+        tnf, abd, ms = pdist.features_sharded_mini(part, plan, k, 4, window, vsize)
+        assert isinstance(ms, pdist.MiniSharded) and ms.local.k == k, "the key-partitioned fallback was taken"
         if shrink:
             assert ms.local.log2_bucket > first_lb, "no regrow happened"
         pieces = ms.pieces
@@ -89,12 +89,12 @@ def _worker(rank, world, port, outdir, case, backend, piece_words, shrink):
         if case != "saturate":
             # counting again with the same object gives the same rows
             ms.count(part, plan)
-            _, abd2 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=10, vsize=400)
+            _, abd2 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=window, vsize=vsize)
             same = bool(torch.equal(abd2, abd))
             # a part size too small for this batch: nothing is exchanged, count() exchanges again (no recount with pieces)
             ms._cap1 = 8
             ms.count(part, plan)
-            _, abd3 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=10, vsize=400)
+            _, abd3 = kmer.features(part, plan, k_tnf=None, table=ms.local, window=window, vsize=vsize)
             again = bool(torch.equal(abd3, abd))
         np.savez(os.path.join(outdir, f"p{rank}.npz"), c=c, n=n, tnf=tnf.cpu().numpy(), abd=abd.cpu().numpy(), names=np.array(rows.names),
                  pieces=pieces, applies=applies, n_rows=len(rows), same=same, again=again)
@@ -102,23 +102,23 @@ def _worker(rank, world, port, outdir, case, backend, piece_words, shrink):
         dist.destroy_process_group()
 
 
-def _run(tmp_path, world, case="small", backend="gloo", piece_words=PIECE_WORDS, shrink=False):
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), case, backend, piece_words, shrink), nprocs=world, join=True)
+def _run(tmp_path, world, case="small", backend="gloo", piece_words=PIECE_WORDS, shrink=False, k=21, window=10, vsize=400):
+    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), case, backend, piece_words, shrink, k, window, vsize), nprocs=world, join=True)
     return [np.load(str(tmp_path / f"p{r}.npz")) for r in range(world)]
 
 
-def _check(parts, world, case="small", min_pieces=3, table=True):
+def _check(parts, world, case="small", min_pieces=3, table=True, k=21, window=10, vsize=400, every_row=False):
     s, min_len = _stream(case)
     text = s.decode()
     for p in parts:
         assert int(p["pieces"]) >= min_pieces, int(p["pieces"])
         assert bool(p["same"]) and bool(p["again"])
     if case == "saturate":
-        otab = oracle.Table(21, threads=4)
+        otab = oracle.Table(k, threads=4)
         for _ in range(world):
             otab.count(text)                                 # every rank holds a copy of the same reads
     else:
-        otab = oracle.Table(21, threads=4).count(text)
+        otab = oracle.Table(k, threads=4).count(text)
     if table:
         codes = np.concatenate([p["c"] for p in parts]); counts = np.concatenate([p["n"] for p in parts])
         order = np.argsort(codes)
@@ -130,17 +130,17 @@ def _check(parts, world, case="small", min_pieces=3, table=True):
         assert counts.max() == 1 << 21 and (codes >> np.uint64(42)).max() == 0          # the sum stayed at 2^21, nothing carried into the code
         for p in parts:
             for r in range(len(rows)):
-                assert np.array_equal(p["abd"][r], oracle.abd_row(text[rows.start[r]:rows.end[r]], 21, otab, 10, 400))
+                assert np.array_equal(p["abd"][r], oracle.abd_row(text[rows.start[r]:rows.end[r]], k, otab, window, vsize))
         return
     names = [x for p in parts for x in p["names"].tolist()]
     assert names == list(rows.names)
     abd = np.concatenate([p["abd"] for p in parts]); tnf = np.concatenate([p["tnf"] for p in parts])
     plan = kmer.Plan(rows, "cuda:0")
-    one = kmer.count_kmers(s, 21, rows=plan, emit=(10, 400))
-    want_tnf, want_abd = kmer.features(s, plan, k_tnf=4, table=one, window=10, vsize=400)
+    one = kmer.count_kmers(s, k, rows=plan, emit=(window, vsize))
+    want_tnf, want_abd = kmer.features(s, plan, k_tnf=4, table=one, window=window, vsize=vsize)
     assert np.array_equal(abd, want_abd.cpu().numpy()) and np.array_equal(tnf, want_tnf.cpu().numpy())
-    for r in range(0, len(rows), max(1, len(rows) // 16)):
-        assert np.array_equal(abd[r], oracle.abd_row(text[rows.start[r]:rows.end[r]], 21, otab, 10, 400))
+    for r in range(0, len(rows), 1 if every_row else max(1, len(rows) // 16)):
+        assert np.array_equal(abd[r], oracle.abd_row(text[rows.start[r]:rows.end[r]], k, otab, window, vsize))
 
 
 @pytest.mark.gpu
@@ -150,6 +150,14 @@ def test_pieces_on_several_ranks(tmp_path, world):
     rows == the one-process rows == the oracle's, the owners' slices together == the oracle's table, counting again and an
     exchange redone after PG_STATUS_OVERFLOW_LIST give the same rows"""
     _check(_run(tmp_path, world), world)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k,window,vsize", [(14, 3, 64), (15, 10, 400), (16, 25, 512), (17, 2, 50), (19, 1, 6)])
+def test_pieces_at_other_k(tmp_path, k, window, vsize):
+    """the small case on two ranks away from k = 21: the pieces' count halves and the <PIECE> lookup half in the instantiations for
+    4, 6 and 8 k-mers per record, with minimizers of 11 (k <= 15) and of 13; every row against the oracle"""
+    _check(_run(tmp_path, 2, k=k, window=window, vsize=vsize), 2, k=k, window=window, vsize=vsize, every_row=True)
 
 
 @pytest.mark.gpu
@@ -193,7 +201,7 @@ def test_pieces_through_the_checked_build():
     from .conftest import ROOT
     env = dict(os.environ, PANGAEA_LIB="checked")
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu", os.path.join(ROOT, "tests", "test_dist_pieces_gpu.py"),
-                        "-k", "(pieces_on_several_ranks and 2) or more_than_2_17_rows or one_rank_rccl"],
+                        "-k", "(pieces_on_several_ranks and 2) or more_than_2_17_rows or one_rank_rccl or at_other_k"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert " passed" in r.stdout and "no tests ran" not in r.stdout
