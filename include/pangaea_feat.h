@@ -369,6 +369,25 @@ int pg_kmer_rebuild_bucketed_range(const uint64_t *pairs, const int64_t *seg, in
                                    int64_t bucket_begin, int64_t bucket_end, uint32_t *status, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Reading a finished table (device; one GPU, any of the five kinds; the table is only read).  The reference leaves jellyfish's
+ * abundance.k{k}.count and its text dump on disk (src/feature.py:87,103) -- kept for exactly this: `jellyfish query` gives the
+ * multiplicity of a k-mer, `jellyfish histo` the count spectrum from which -s and -v are chosen (how many distinct k-mers lie
+ * beyond window * vector_size and so in no bin, count_kmer.cpp:86-96).  Both entries are additive to ABI 9.
+ *   pg_table_query     stands in for `jellyfish query` on feature.py:87's table: counts[i] = multiplicity of codes[i], i < n
+ *                      (device arrays).  A code is a k-mer in the stream's encoding (A0 C1 T2 G3, newest character in the low
+ *                      bits), either strand: it is made canonical as the counting kernels do.  0: not in the table;
+ *                      PG_QUERY_INVALID: the code has a bit at or above 2k (no table memory is read for it).  A wide count of
+ *                      2^32 - 1 cannot be told from that.  n == 0: PG_OK, nothing launched.
+ *   pg_table_spectrum  stands in for `jellyfish histo` on the same table (feature.py:87,103): hist[c] = distinct canonical
+ *                      k-mers of multiplicity c for 1 <= c <= high, hist[high + 1] = those above, hist[0] = 0.  hist (device,
+ *                      high + 2 words) is cleared on `stream` first and written whole.  t->data must be 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_QUERY_INVALID 0xFFFFFFFFu
+#define PG_SPECTRUM_MAX_HIGH 16382 /* high + 2 32-bit bins in 64 KiB of LDS */
+int pg_table_query(const pg_table *t, const uint64_t *codes, int64_t n, uint32_t *counts, void *stream);
+int pg_table_spectrum(const pg_table *t, int high, uint64_t *hist /* device, [high + 2], written whole */, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Per-run feature rows (device).  One launch fills both matrices.
  *   tnf_out [n_rows, ncols(k_tnf)] int32: canonical k_tnf-mer counts        (count_tnf.cpp:78-113)
  *   abd_out [n_rows, vsize]        int32: hist[count(kmer)/window]++ where the bin is < vsize

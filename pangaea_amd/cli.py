@@ -3,6 +3,10 @@
     count_tnf  {-i F | -1 F -2 F} -o OUT.gz [-k 4] [-l 1000] [-t 16]              (count_tnf.cpp:117-125)
     count_kmer {-i F | -1 F -2 F} -g DUMP -o OUT.gz [-k 15] [-l 1000] [-t 16] [-v 400] [-w 10]
                                                                                   (count_kmer.cpp:112-123)
+    kmer_table histo {-i F | -1 F -2 F | -g DUMP} -k K [--high 10000] [--full] -o OUT
+    kmer_table query {-i F | -1 F -2 F | -g DUMP} -k K [-q FILE] [KMER ...]
+                                                         (what `jellyfish histo` / `jellyfish query` give from the table the
+                                                          reference keeps on disk, feature.py:87,103; see ``main_kmer_table``)
 ``-t`` is accepted and ignored (the GPU replaces the thread pool).  ``count_kmer -g DUMP``: an existing
 jellyfish ``dump -c -t`` file is loaded with the reference's loader semantics (count_kmer.cpp:139-170); when the
 file does not exist the multiplicities are counted on the GPU from the reads themselves, which is what jellyfish
@@ -103,5 +107,71 @@ def main_count_kmer(argv=None) -> int:
         feature.write_csv_gz(a.output, names, abd)
     except Exception as e:
         sys.stderr.write(f"count_kmer: {e}\n")
+        return 1
+    return 0
+
+
+def _table_for(a):
+    """the multiplicity table a ``kmer_table`` call asks: loaded from a jellyfish text dump (``-g``), else counted from the reads
+    with the table's rule as ``Feature`` applies it (lower-case bases count unless PANGAEA_LOWERCASE_IS_BASE=0; bases of paired
+    files below the quality threshold never do)"""
+    import torch
+    from .kmer import KmerTable, count_kmers
+    from .reads import ReadStream
+    device = torch.device("cuda", torch.cuda.current_device())
+    if a.global_:
+        codes, counts = load_dump(a.global_, a.kmer)
+        return KmerTable.from_items(a.kmer, codes, counts, device)
+    stream = ReadStream.from_fastq(a.interleaved or a.reads1, None if a.interleaved else a.reads2, device=device).to(device)
+    return count_kmers(stream, a.kmer, lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+
+
+def main_kmer_table(argv=None) -> int:
+    """``kmer_table histo``: the count spectrum, one line ``"<count> <distinct k-mers>"`` for count = 1 .. high + 1 (the last
+    line gathers every count above ``--high``); lines of 0 are left out unless ``--full``.  ``kmer_table query``: one line
+    ``"<k-mer as given> <count>"`` on stdout per k-mer of the arguments and then of ``-q FILE`` (one per line), in that order;
+    either strand may be given, 0 = not in the table.  The two formats follow jellyfish's documented ``histo`` and ``query``
+    output; jellyfish is not at hand to compare with, so they are unpinned (like the two rules of DESIGN section 2) -- what the
+    tests pin is the content, against the oracle.  Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
+    p = _Parser(prog="kmer_table")
+    sub = p.add_subparsers(dest="cmd", required=True)
+    for name in ("histo", "query"):
+        q = sub.add_parser(name)
+        q.add_argument("-1", "--reads1", default="")
+        q.add_argument("-2", "--reads2", default="")
+        q.add_argument("-i", "--interleaved", default="")
+        q.add_argument("-g", "--global", dest="global_", default="")
+        q.add_argument("-k", "--kmer", type=int, required=True)
+        if name == "histo":
+            q.add_argument("--high", type=int, default=10000)
+            q.add_argument("--full", action="store_true")
+            q.add_argument("-o", "--output", required=True)
+        else:
+            q.add_argument("-q", "--queries", default="")
+            q.add_argument("kmers", nargs="*")
+    a = p.parse_args(argv)
+    from . import _lib
+    try:
+        if not (a.global_ or a.interleaved or (a.reads1 and a.reads2)):
+            raise ValueError("no input: -i F, -1 F -2 F or -g DUMP is needed")
+        if not 1 <= a.kmer <= _lib.WIDE_MAX_K:
+            raise ValueError(f"k-mer size {a.kmer} unsupported (1..{_lib.WIDE_MAX_K})")
+        if a.cmd == "histo":
+            if not 1 <= a.high <= _lib.SPECTRUM_MAX_HIGH:
+                raise ValueError(f"--high must lie in [1, {_lib.SPECTRUM_MAX_HIGH}]")
+            hist = _table_for(a).spectrum(a.high)
+            with open(a.output, "w") as f:
+                f.writelines(f"{c} {int(hist[c])}\n" for c in range(1, a.high + 2) if a.full or hist[c])
+        else:
+            from .kmer import encode_kmers
+            asked = list(a.kmers)
+            if a.queries:
+                with open(a.queries) as f:
+                    asked += [line.strip() for line in f if line.strip()]
+            codes = encode_kmers(asked, a.kmer)              # a bad k-mer is refused before anything is counted
+            counts = _table_for(a).query(codes).cpu().numpy() if asked else []
+            sys.stdout.writelines(f"{s} {int(c)}\n" for s, c in zip(asked, counts))
+    except Exception as e:
+        sys.stderr.write(f"kmer_table: {e}\n")
         return 1
     return 0

@@ -252,6 +252,128 @@ __global__ __launch_bounds__(BLOCK) void kmer_merge_kernel(const uint64_t *__res
     }
 }
 
+// -------------------------------------------------------------------------------- reading a finished table
+//
+// What `jellyfish query` and `jellyfish histo` answer from the dump that the reference keeps (feature.py:87,103).  Both kernels
+// only read the table: plain loads, no atomics on it.
+
+// out[i] = multiplicity of the k-mer codes[i] (either strand; the stream's encoding, newest character in the low bits), 0 when
+// the table does not hold it, PG_QUERY_INVALID when the code has a bit at or above 2k -- such a code reads no table memory.
+// One query per lane and turn, QRY_BATCH turns at a time: the first probes of the batch are issued before any is resolved
+// (every probe is a random 8-byte read, i.e. one 64-byte line, as the lookups of features_kernel).
+constexpr int QRY_BATCH = 8;
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void table_query_kernel(const uint64_t *__restrict__ codes, int64_t n, int k,
+                                                            const uint32_t *__restrict__ dense, HashView t, uint32_t *__restrict__ out)
+{
+    const uint64_t kmask = low_mask<uint64_t>(k);
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t i0 = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i0 < n; i0 += stride * QRY_BATCH) {
+        uint64_t key[QRY_BATCH], hh[QRY_BATCH], cur[QRY_BATCH];
+        bool ask[QRY_BATCH];
+#pragma unroll
+        for (int u = 0; u < QRY_BATCH; ++u) {
+            const int64_t i = i0 + u * stride;
+            const uint64_t fw = i < n ? codes[i] : ~0ull;
+            ask[u] = (fw & ~kmask) == 0;                   // (a lane past the end asks nothing and writes nothing)
+            key[u] = hh[u] = cur[u] = 0;
+            if (!ask[u]) continue;
+            // the reverse complement as Roller builds it: complement = ^ 2 per character, order reversed
+            const uint64_t rc = rev2_64(fw ^ 0xAAAAAAAAAAAAAAAAull) >> (64 - 2 * k);
+            const uint64_t canon = fw < rc ? fw : rc;
+            if (TK == TK_DENSE) {
+                cur[u] = dense[(uint32_t)canon];
+            } else {
+                key[u] = TK == TK_HASH ? key42(canon) : canon;
+                hh[u] = TK == TK_WIDE ? t.home_wide(canon) : (TK == TK_MINI || TK == TK_MINIW) ? t.home_mini(canon, k) : t.home_key(key[u]);
+                cur[u] = t.slots[hh[u]];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < QRY_BATCH; ++u) {
+            const int64_t i = i0 + u * stride;
+            if (i >= n) continue;
+            uint32_t cnt = PG_QUERY_INVALID;
+            if (ask[u]) {
+                bool found;
+                if (TK == TK_DENSE) cnt = (uint32_t)cur[u];
+                else if (TK == TK_WIDE || TK == TK_MINIW) cnt = wide_probe(t, hh[u], cur[u], key[u], &found);
+                else cnt = hash_probe(t, hh[u], cur[u], key[u], &found);
+            }
+            out[i] = cnt;
+        }
+    }
+}
+
+// hist[c] += distinct k-mers of multiplicity c (1 <= c <= high), hist[high + 1] += those above; hist zeroed by the launcher.
+// One streaming pass, 16 bytes per lane and load (SPEC_FORM: four dense counters, two packed slots, or four keys of the key
+// plane with their four counts), SPEC_UNROLL loads in flight per lane.  Bins are 32-bit LDS counters (dynamic LDS, high + 2 of
+// them: at most 64 KiB); a workgroup sees fewer than 2^32 slots (the launcher's grid), so none overflows.  Real spectra are
+// mostly c == 1 (sequencing errors): all 64 lanes would add to one LDS counter, so those lanes are counted with a ballot and
+// kept in a register of the wavefront until the end (BALLOT >= 1; BALLOT == 2: c == 2 as well); every other count is an LDS add
+// whose result nobody reads.  Non-zero bins leave with one 64-bit global add each: integer sums, the same whatever the order.
+enum { SPEC_DENSE = 0, SPEC_PACKED = 1, SPEC_PLANES = 2 };
+constexpr int SPEC_UNROLL = 4;
+template <int BALLOT> __device__ __forceinline__ void spectrum_bin(uint32_t *bins, uint32_t c, uint32_t cap, uint32_t &ones, uint32_t &twos)
+{
+    c = c < cap ? c : cap;
+    if (BALLOT >= 1) ones += (uint32_t)__popcll(__ballot(c == 1));
+    if (BALLOT >= 2) twos += (uint32_t)__popcll(__ballot(c == 2));
+    if (c > (uint32_t)BALLOT) atomicAdd(&bins[c], 1u);
+}
+template <int FORM, int BALLOT>
+__global__ __launch_bounds__(BIG_BLOCK) void table_spectrum_kernel(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t n_units,
+                                                                   int high, unsigned long long *__restrict__ hist)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t bins[];
+    const int n_bins = high + 2;
+    const uint32_t cap = (uint32_t)high + 1u;
+    for (int i = threadIdx.x; i < n_bins; i += BIG_BLOCK) bins[i] = 0;
+    lds_sync();
+    uint32_t ones = 0, twos = 0;                                     // (the same in every lane of a wavefront)
+    constexpr int64_t TILE = (int64_t)BIG_BLOCK * SPEC_UNROLL;
+    // (the trip count is the same for the whole workgroup: the ballots run with every lane)
+    for (int64_t t0 = (int64_t)blockIdx.x * TILE; t0 < n_units; t0 += (int64_t)gridDim.x * TILE) {
+        uint4 v[SPEC_UNROLL], w[SPEC_UNROLL], c[SPEC_UNROLL];
+#pragma unroll
+        for (int q = 0; q < SPEC_UNROLL; ++q) {
+            const int64_t i = t0 + (int64_t)q * BIG_BLOCK + threadIdx.x;
+            v[q] = w[q] = c[q] = make_uint4(0, 0, 0, 0);
+            if (i < n_units) {
+                if (FORM == SPEC_PLANES) { v[q] = slots[2 * i]; w[q] = slots[2 * i + 1]; c[q] = counts[i]; }
+                else v[q] = slots[i];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < SPEC_UNROLL; ++q) {
+            if (FORM == SPEC_DENSE) {
+                spectrum_bin<BALLOT>(bins, v[q].x, cap, ones, twos);
+                spectrum_bin<BALLOT>(bins, v[q].y, cap, ones, twos);
+                spectrum_bin<BALLOT>(bins, v[q].z, cap, ones, twos);
+                spectrum_bin<BALLOT>(bins, v[q].w, cap, ones, twos);
+            } else if (FORM == SPEC_PACKED) {
+                // slot = (key << 22) | count: the count is the low 22 bits of the low dword, an empty slot is all zero
+                spectrum_bin<BALLOT>(bins, (v[q].x | v[q].y) ? v[q].x & (uint32_t)HASH_CMASK : 0u, cap, ones, twos);
+                spectrum_bin<BALLOT>(bins, (v[q].z | v[q].w) ? v[q].z & (uint32_t)HASH_CMASK : 0u, cap, ones, twos);
+            } else {
+                spectrum_bin<BALLOT>(bins, (v[q].x | v[q].y) ? c[q].x : 0u, cap, ones, twos);
+                spectrum_bin<BALLOT>(bins, (v[q].z | v[q].w) ? c[q].y : 0u, cap, ones, twos);
+                spectrum_bin<BALLOT>(bins, (w[q].x | w[q].y) ? c[q].z : 0u, cap, ones, twos);
+                spectrum_bin<BALLOT>(bins, (w[q].z | w[q].w) ? c[q].w : 0u, cap, ones, twos);
+            }
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (BALLOT >= 1 && ones) atomicAdd(&bins[1], ones);
+        if (BALLOT >= 2 && twos) atomicAdd(&bins[2], twos);          // (high >= 1: bin 2 exists, as the bin above `high` if need be)
+    }
+    lds_sync();
+    for (int i = threadIdx.x; i < n_bins; i += BIG_BLOCK) {
+        const uint32_t s = bins[i];
+        if (s) atomicAdd(&hist[i], (unsigned long long)s);
+    }
+}
+
 // HyperLogLog sketch of the canonical k-mers of a word range: registers[j] = max over k-mers with hash prefix j of
 // (1 + leading zeros of the remaining hash bits).  4096 registers: ~1.6 % standard error -- enough to size a table.
 constexpr int HLL_BITS = 12;
@@ -2237,6 +2359,80 @@ extern "C" int pg_table_compact(const pg_table *t, const int64_t *seg, uint64_t 
     hipLaunchKernelGGL(table_compact_kernel, dim3(1u << (t->log2_slots - t->log2_bucket_slots)), dim3(BLOCK), 0, (hipStream_t)stream,
                        (const uint64_t *)t->data, t->log2_bucket_slots, (const long long *)seg, out);
     return check_launch("pg_table_compact");
+}
+
+extern "C" int pg_table_query(const pg_table *t, const uint64_t *codes, int64_t n, uint32_t *counts, void *stream)
+{
+    if (!t) return pg_fail(PG_EINVAL, "pg_table_query: t is null");
+    if (!codes) return pg_fail(PG_EINVAL, "pg_table_query: codes is null");
+    if (!counts) return pg_fail(PG_EINVAL, "pg_table_query: counts is null");
+    if (n < 0) return pg_fail(PG_EINVAL, "pg_table_query: n is negative (%lld)", (long long)n);
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (n == 0) return PG_OK;
+    const int grid = grid_for((n + QRY_BATCH - 1) / QRY_BATCH);
+    const HashView v = t->kind == PG_TABLE_DENSE ? HashView{nullptr, 0, 0} : view_of(t);
+    const uint32_t *dense = t->kind == PG_TABLE_DENSE ? (const uint32_t *)t->data : nullptr;
+#define PG_LAUNCH(TK) hipLaunchKernelGGL((table_query_kernel<TK>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, codes, n, t->k, dense, v, counts)
+    switch (t->kind) {
+    case PG_TABLE_DENSE: PG_LAUNCH(TK_DENSE); break;
+    case PG_TABLE_HASH: PG_LAUNCH(TK_HASH); break;
+    case PG_TABLE_WIDE: PG_LAUNCH(TK_WIDE); break;
+    case PG_TABLE_MINI: PG_LAUNCH(TK_MINI); break;
+    default: PG_LAUNCH(TK_MINIW); break;
+    }
+#undef PG_LAUNCH
+    return check_launch("pg_table_query");
+}
+
+extern "C" int pg_table_spectrum(const pg_table *t, int high, uint64_t *hist, void *stream)
+{
+    if (!t) return pg_fail(PG_EINVAL, "pg_table_spectrum: t is null");
+    if (!hist) return pg_fail(PG_EINVAL, "pg_table_spectrum: hist is null");
+    if (high < 1 || high > PG_SPECTRUM_MAX_HIGH) return pg_fail(PG_EINVAL, "pg_table_spectrum: high %d outside [1, %d]", high, PG_SPECTRUM_MAX_HIGH);
+    int rc = check_table(t);
+    if (rc) return rc;
+    if ((uintptr_t)t->data & 15) return pg_fail(PG_EINVAL, "pg_table_spectrum: t->data is not 16-byte aligned");
+    // units of 16 bytes of the slots (planes form: 32 bytes of keys + 16 of counts); every form's table is a whole number of them
+    int form;
+    int64_t n_units;
+    const uint4 *counts = nullptr;
+    if (t->kind == PG_TABLE_DENSE) {
+        form = SPEC_DENSE;
+        n_units = (int64_t)1 << (2 * t->k - 2);
+    } else if (t->kind == PG_TABLE_HASH || t->kind == PG_TABLE_MINI) {
+        form = SPEC_PACKED;
+        n_units = (int64_t)1 << (t->log2_slots - 1);
+    } else {
+        form = SPEC_PLANES;
+        n_units = (int64_t)1 << (t->log2_slots - 2);
+        counts = (const uint4 *)((const uint64_t *)t->data + ((int64_t)1 << t->log2_slots));
+    }
+    // two workgroups of 1024 per CU: tables of up to 2^40 slots leave a workgroup at most 2^31 of them, so its 32-bit bins hold
+    constexpr int64_t tile = (int64_t)BIG_BLOCK * SPEC_UNROLL;
+    int64_t grid = (n_units + tile - 1) / tile;
+    if (grid > 512) grid = 512;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t lds = (size_t)(high + 2) * sizeof(uint32_t);
+    if (hipMemsetAsync(hist, 0, (size_t)(high + 2) * sizeof(uint64_t), s) != hipSuccess) return pg_fail(PG_EHIP, "pg_table_spectrum: cannot clear hist");
+    // PG_SPECTRUM_BALLOT (timing experiments): 0 = every count through an LDS add, 1 = c == 1 by ballot (the default), 2 = c == 2 as well
+    const char *env = getenv("PG_SPECTRUM_BALLOT");
+    const int ballot = env && *env ? atoi(env) : 1;
+#define PG_LAUNCH(FORM, BALLOT)                                                                                             \
+    hipLaunchKernelGGL((table_spectrum_kernel<FORM, BALLOT>), dim3((unsigned)grid), dim3(BIG_BLOCK), lds, s, (const uint4 *)t->data, counts, n_units, \
+                       high, (unsigned long long *)hist)
+#define PG_LAUNCH_FORM(FORM)                                                                                                \
+    do {                                                                                                                    \
+        if (ballot <= 0) PG_LAUNCH(FORM, 0);                                                                                \
+        else if (ballot == 1) PG_LAUNCH(FORM, 1);                                                                           \
+        else PG_LAUNCH(FORM, 2);                                                                                            \
+    } while (0)
+    if (form == SPEC_DENSE) PG_LAUNCH_FORM(SPEC_DENSE);
+    else if (form == SPEC_PACKED) PG_LAUNCH_FORM(SPEC_PACKED);
+    else PG_LAUNCH_FORM(SPEC_PLANES);
+#undef PG_LAUNCH_FORM
+#undef PG_LAUNCH
+    return check_launch("pg_table_spectrum");
 }
 
 extern "C" int64_t pg_abundance_workspace_bytes(int64_t n_words_counted, int64_t n_rows, int vsize, const pg_table *t)

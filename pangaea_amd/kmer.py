@@ -1095,6 +1095,85 @@ class KmerTable:
         order = np.argsort(codes)
         return codes[order], counts[order]
 
+    # ------------------------------------------------------------------ asking a finished table (jellyfish query / histo)
+
+    def _require_readable(self) -> None:
+        self._require_counts()
+        _require_gpu(self.data, "the table")
+        if self._empty and self.log2_bucket and self.kind in ("hash", "mini", "miniw"):
+            self.data.zero_()            # a reset() bucketed table is only logically empty
+
+    def query(self, codes) -> torch.Tensor:
+        """multiplicity of each given k-mer (``jellyfish query`` on the table of src/feature.py:87): int64 on the table's device,
+        0 for a k-mer the table does not hold, -1 for a code with bits at or above 2k.
+
+        ``codes``: an int64 / uint64 tensor ON THE DEVICE (used as it is, no host round trip), a numpy integer array, or a list
+        of k-mer strings (``encode_kmers``).  A code is a k-mer in the stream's encoding -- A0 C1 T2 G3, newest character in the
+        low bits -- of either strand."""
+        self._require_readable()
+        if isinstance(codes, torch.Tensor):
+            _require_gpu(codes, "the codes")
+            if codes.dtype not in (torch.int64, torch.uint64):
+                raise TypeError(f"codes must be int64 or uint64 (got {codes.dtype})")
+            if codes.device != self.device:
+                raise ValueError("codes and table are on different devices")
+            c = codes.reshape(-1).contiguous()
+        else:
+            a = np.asarray(codes)
+            if a.dtype.kind in "US" or (a.dtype == object and a.size and isinstance(a.flat[0], (str, bytes))):
+                a = encode_kmers([s.decode() if isinstance(s, bytes) else s for s in a.reshape(-1).tolist()], self.k)
+            elif a.size == 0:
+                a = np.zeros(0, np.uint64)
+            elif a.dtype.kind not in "iu":
+                raise TypeError(f"codes must be integers or k-mer strings (got {a.dtype})")
+            c = torch.from_numpy(np.ascontiguousarray(a.reshape(-1)).astype(np.uint64).view(np.int64)).to(self.device)
+        if c.numel() == 0:               # (an empty tensor has no address to give the library)
+            return torch.zeros(0, dtype=torch.int64, device=self.device)
+        out = torch.empty(c.numel(), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pg_table_query(self.desc(), c.data_ptr(), c.numel(), out.data_ptr(), _stream_ptr(self.device)))
+        return torch.where(out == -1, -1, out.to(torch.int64) & 0xFFFFFFFF)      # (-1 as int32: PG_QUERY_INVALID)
+
+    def spectrum(self, high: int = 10000) -> np.ndarray:
+        """the count spectrum (``jellyfish histo`` on the table of src/feature.py:87,103): int64 [high + 2]; entry c = distinct
+        canonical k-mers of multiplicity c for 1 <= c <= high, entry high + 1 = those above, entry 0 = 0.  What one reads to
+        choose -s and -v: the k-mers beyond window * vector_size fall into no bin of an abundance row (count_kmer.cpp:86-96)."""
+        high = int(high)
+        if not 1 <= high <= _lib.SPECTRUM_MAX_HIGH:
+            raise ValueError(f"high must lie in [1, {_lib.SPECTRUM_MAX_HIGH}] (got {high})")
+        self._require_readable()
+        hist = torch.empty(high + 2, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pg_table_spectrum(self.desc(), high, hist.data_ptr(), _stream_ptr(self.device)))
+        return hist.cpu().numpy()
+
+
+def encode_kmers(strings, k: int) -> np.ndarray:
+    """uint64 codes of k-mer strings in the stream's encoding: ``(c >> 1) & 3`` over ``ACGT`` (A0 C1 T2 G3, count_tnf.cpp:99), the
+    first character highest, the newest (last) in the low two bits.  ValueError for a string of another length than ``k`` or with
+    any other character (N, lower case, IUPAC)."""
+    strings = list(strings)
+    k = int(k)
+    if not 1 <= k <= _lib.WIDE_MAX_K:
+        raise ValueError(f"k-mer size {k} unsupported (1..{_lib.WIDE_MAX_K})")
+    for s in strings:
+        if not isinstance(s, str) or len(s) != k:
+            raise ValueError(f"{s!r} is not a k-mer of length {k}")
+    if not strings:
+        return np.zeros(0, np.uint64)
+    try:
+        chars = np.frombuffer("".join(strings).encode("ascii"), dtype=np.uint8).reshape(-1, k)
+    except UnicodeEncodeError:
+        chars = np.zeros((len(strings), k), np.uint8)
+    bad = ~np.isin(chars, np.frombuffer(b"ACGT", dtype=np.uint8)).all(axis=1)
+    if bad.any():
+        raise ValueError(f"{strings[int(np.nonzero(bad)[0][0])]!r} holds a character other than A, C, G, T")
+    d = ((chars >> 1) & 3).astype(np.uint64)
+    codes = np.zeros(len(strings), dtype=np.uint64)
+    for j in range(k):
+        codes = (codes << np.uint64(2)) | d[:, j]
+    return codes
+
 
 def half_piece_words(free_bytes: int, n_words: int, local_log2_slots: int, local_log2_bucket: int, n_rows: int, world: int):
     """words per piece of an N-rank count half (``KmerTable.count_half``): ``n_words`` (one piece) when everything the rank holds
