@@ -388,6 +388,53 @@ int pg_table_query(const pg_table *t, const uint64_t *codes, int64_t n, uint32_t
 int pg_table_spectrum(const pg_table *t, int high, uint64_t *hist /* device, [high + 2], written whole */, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
+ * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
+ * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for
+ * 0 1 2 3; the count is the stored value (packed kinds stop at PG_HASH_COUNT_SAT).  Lines stand in slot order, so the text of a
+ * table is one fixed byte string and can be written range by range.  All entries are additive to ABI 9; every argument is
+ * checked before the first HIP call; the table is only read (plain loads) and t->data must be 16-byte aligned.
+ *   pg_table_dump_units  the table's units: PG_DUMP_UNIT_SLOTS consecutive entries each (the last may be short: 4^k < a unit)
+ *   pg_table_dump_sizes  stands in for the sizing of `jellyfish dump -c -t -L lower` (feature.py:87,103): unit_bytes[u] = text
+ *                        bytes of unit u, k + 2 + digits(count) per entry with count >= lower (lower >= 1; 1 = every entry);
+ *                        unit_lines[u] (may be NULL) = its lines.  Device arrays of pg_table_dump_units(t) words.
+ *   pg_table_dump_text   stands in for `jellyfish dump -c -t -L lower` itself (feature.py:87,103): the lines of units
+ *                        [unit_begin, unit_end) go to text + (unit_offsets[u] - text_base), unit_offsets (device) being the
+ *                        exclusive scan of unit_bytes.  text_base and range_bytes are what the caller knows of that scan on the
+ *                        host: unit_offsets[unit_begin] and unit_offsets[unit_end] - unit_offsets[unit_begin]; a text buffer
+ *                        shorter than range_bytes is refused, and whatever the device offsets say, no byte outside
+ *                        [0, range_bytes) of text is written.  An empty range or range_bytes == 0: PG_OK, nothing launched.
+ *   pg_dump_parse        stands in for the dump reload of count_kmer.cpp:139-170 over n_bytes of text (device, 16-byte aligned)
+ *                        that hold whole lines; a last line without newline is a line.  Per line: the text before the first
+ *                        TAB must have exactly k characters (else PG_DUMP_BAD_LENGTH; a line without TAB: PG_DUMP_NO_TAB); the
+ *                        count is the 1 to PG_DUMP_MAX_DIGITS decimal digits behind the TAB, followed by the end of the line,
+ *                        one '\r' before it tolerated (else PG_DUMP_BAD_COUNT); blank lines are skipped; a k-mer with a character
+ *                        outside ACGT (N, lower case) is dropped silently, as count_kmer.cpp:153 drops it.  Kept lines leave as
+ *                        codes[i] (canonical, (c >> 1) & 3 per character), counts[i], ordinals[i] = first_ordinal + the line's
+ *                        0-based index in the text, i < n_out[0], in no particular order (later lines override earlier ones,
+ *                        count_kmer.cpp:166: the caller's business, by ordinal); n_out[1] = lines of the text, blank ones
+ *                        included.  status (device, one word): PG_DUMP_CLEAN, or (1-based line << 8) | reason of the FIRST bad
+ *                        line (PG_DUMP_CAPACITY: more kept lines than cap) -- the output of such a call must not be used.
+ *                        workspace: pg_dump_parse_workspace_bytes(n_bytes), 8-byte aligned.  n_bytes == 0: PG_OK, nothing
+ *                        launched, nothing written.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_DUMP_UNIT_SLOTS 1024 /* one workgroup of 256 lanes x 4 entries; its text (<= 43 bytes per line) fits 44 KiB of LDS */
+#define PG_DUMP_MAX_DIGITS 18
+#define PG_DUMP_CLEAN 0xFFFFFFFFFFFFFFFFull
+#define PG_DUMP_BAD_LENGTH 1u
+#define PG_DUMP_NO_TAB 2u
+#define PG_DUMP_BAD_COUNT 3u
+#define PG_DUMP_CAPACITY 4u
+int64_t pg_table_dump_units(const pg_table *t);
+int pg_table_dump_sizes(const pg_table *t, int64_t lower, int64_t *unit_bytes, int64_t *unit_lines /* may be NULL */, void *stream);
+int pg_table_dump_text(const pg_table *t, int64_t lower, int64_t unit_begin, int64_t unit_end, const int64_t *unit_offsets,
+                       int64_t text_base, int64_t range_bytes, uint8_t *text, int64_t text_bytes, void *stream);
+int64_t pg_dump_parse_workspace_bytes(int64_t n_bytes);
+int pg_dump_parse(const uint8_t *text, int64_t n_bytes, int k, int64_t first_ordinal, uint64_t *codes, uint64_t *counts,
+                  int64_t *ordinals, int64_t cap, int64_t *n_out /* device [2] */, uint64_t *status /* device [1] */,
+                  void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Per-run feature rows (device).  One launch fills both matrices.
  *   tnf_out [n_rows, ncols(k_tnf)] int32: canonical k_tnf-mer counts        (count_tnf.cpp:78-113)
  *   abd_out [n_rows, vsize]        int32: hist[count(kmer)/window]++ where the bin is < vsize

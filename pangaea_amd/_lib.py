@@ -43,6 +43,10 @@ KEY42_M2 = 0x1fe1a85ec53
 HLL_REGISTERS = 4096
 QUERY_INVALID = 0xFFFFFFFF         # PG_QUERY_INVALID: pg_table_query's answer to a code with bits at or above 2k
 SPECTRUM_MAX_HIGH = 16382          # PG_SPECTRUM_MAX_HIGH
+DUMP_UNIT_SLOTS = 1024             # PG_DUMP_UNIT_SLOTS: entries per unit of pg_table_dump_sizes / pg_table_dump_text
+DUMP_MAX_DIGITS = 18               # PG_DUMP_MAX_DIGITS
+DUMP_CLEAN = (1 << 64) - 1         # PG_DUMP_CLEAN: pg_dump_parse's status word when every line was fine
+DUMP_BAD_LENGTH, DUMP_NO_TAB, DUMP_BAD_COUNT, DUMP_CAPACITY = 1, 2, 3, 4
 MAX_ROWS = (1 << 22) - 2
 
 
@@ -168,6 +172,11 @@ def load() -> C.CDLL:
         "pg_mini_wait_first_pass": (i32, [vp]),
         "pg_table_query": (i32, [tp, vp, i64, vp, vp]),
         "pg_table_spectrum": (i32, [tp, i32, vp, vp]),
+        "pg_table_dump_units": (i64, [tp]),
+        "pg_table_dump_sizes": (i32, [tp, i64, vp, vp, vp]),
+        "pg_table_dump_text": (i32, [tp, i64, i64, i64, vp, i64, i64, vp, i64, vp]),
+        "pg_dump_parse_workspace_bytes": (i64, [i64]),
+        "pg_dump_parse": (i32, [vp, i64, i32, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
         "pg_features": (i32, [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp, tp, i32, i32, vp, vp]),
         "pg_normalize_rows": (i32, [vp, i64, i32, vp, vp, vp]),
         "pg_write_csv_gz": (i32, [cp, cp, vp, i64, i64]),
@@ -199,6 +208,7 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_mini_plan_bytes", "pg_mini_plan", "pg_mini_records_bytes", "pg_mini_shuffle_bytes", "pg_mini_shuffle_bytes_merged", "pg_mini_merge_words", "pg_mini_count_piece", "pg_mini_lookup_begin", "pg_mini_lookup_piece", "pg_mini_count", "pg_mini_half_bytes", "pg_mini_count_half", "pg_mini_gather_entries", "pg_mini_merge_bins", "pg_mini_lookup_half", "pg_mini_count_half_piece", "pg_mini_lookup_half_piece", "pg_mini_merge_form_applies", "pg_mini_records_meta_offset", "pg_mini_wait_first_pass", "pg_mini_abundance_from_emitted",
            "pg_mini_plan_masked", "pg_mini_count_half_masked", "pg_mini_count_half_piece_masked", "pg_mini_merge_bins_masked",
            "pg_table_query", "pg_table_spectrum",
+           "pg_table_dump_units", "pg_table_dump_sizes", "pg_table_dump_text", "pg_dump_parse_workspace_bytes", "pg_dump_parse",
            "pg_features", "pg_normalize_rows", "pg_write_csv_gz", "pg_extract_reads"]
 
 

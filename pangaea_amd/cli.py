@@ -5,10 +5,13 @@
                                                                                   (count_kmer.cpp:112-123)
     kmer_table histo {-i F | -1 F -2 F | -g DUMP} -k K [--high 10000] [--full] -o OUT
     kmer_table query {-i F | -1 F -2 F | -g DUMP} -k K [-q FILE] [KMER ...]
-                                                         (what `jellyfish histo` / `jellyfish query` give from the table the
-                                                          reference keeps on disk, feature.py:87,103; see ``main_kmer_table``)
+    kmer_table dump  {-i F | -1 F -2 F | -g DUMP} -k K [-L LOWER] -o OUT
+                                                         (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
+                                                          from the table the reference keeps on disk, feature.py:87,103; see
+                                                          ``main_kmer_table``)
 ``-t`` is accepted and ignored (the GPU replaces the thread pool).  ``count_kmer -g DUMP``: an existing
-jellyfish ``dump -c -t`` file is loaded with the reference's loader semantics (count_kmer.cpp:139-170); when the
+jellyfish ``dump -c -t`` file is loaded on the GPU (``KmerTable.from_dump``) with the reference's loader semantics
+(count_kmer.cpp:139-170; ``load_dump`` states them on the host and is what the tests compare with); when the
 file does not exist the multiplicities are counted on the GPU from the reads themselves, which is what jellyfish
 would have reported.  Exit status 0, or 1 on bad arguments / failure, as the reference (cmdline.h:592-597).
 """
@@ -101,8 +104,7 @@ def main_count_kmer(argv=None) -> int:
     try:
         table = None
         if os.path.isfile(a.global_):
-            codes, counts = load_dump(a.global_, a.kmer)
-            table = KmerTable.from_items(a.kmer, codes, counts, torch.device("cuda", torch.cuda.current_device()))
+            table = KmerTable.from_dump(a.global_, a.kmer, torch.device("cuda", torch.cuda.current_device()))
         names, _, abd = feature.compute_features(r1, r2, a.kmer, 0, a.window, a.vector, a.len, want_tnf=False, table=table)
         feature.write_csv_gz(a.output, names, abd)
     except Exception as e:
@@ -120,8 +122,7 @@ def _table_for(a):
     from .reads import ReadStream
     device = torch.device("cuda", torch.cuda.current_device())
     if a.global_:
-        codes, counts = load_dump(a.global_, a.kmer)
-        return KmerTable.from_items(a.kmer, codes, counts, device)
+        return KmerTable.from_dump(a.global_, a.kmer, device)
     stream = ReadStream.from_fastq(a.interleaved or a.reads1, None if a.interleaved else a.reads2, device=device).to(device)
     return count_kmers(stream, a.kmer, lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
 
@@ -130,12 +131,14 @@ def main_kmer_table(argv=None) -> int:
     """``kmer_table histo``: the count spectrum, one line ``"<count> <distinct k-mers>"`` for count = 1 .. high + 1 (the last
     line gathers every count above ``--high``); lines of 0 are left out unless ``--full``.  ``kmer_table query``: one line
     ``"<k-mer as given> <count>"`` on stdout per k-mer of the arguments and then of ``-q FILE`` (one per line), in that order;
-    either strand may be given, 0 = not in the table.  The two formats follow jellyfish's documented ``histo`` and ``query``
+    either strand may be given, 0 = not in the table.  ``kmer_table dump``: the table as ``jellyfish dump -c -t [-L LOWER]``
+    writes it, one line ``"<k-mer>\t<count>"`` per canonical k-mer of count >= LOWER (``KmerTable.write_dump``; the file
+    ``count_kmer -g`` and ``kmer_table -g`` read).  The two formats of histo and query follow jellyfish's documented ``histo`` and ``query``
     output; jellyfish is not at hand to compare with, so they are unpinned (like the two rules of DESIGN section 2) -- what the
     tests pin is the content, against the oracle.  Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
     p = _Parser(prog="kmer_table")
     sub = p.add_subparsers(dest="cmd", required=True)
-    for name in ("histo", "query"):
+    for name in ("histo", "query", "dump"):
         q = sub.add_parser(name)
         q.add_argument("-1", "--reads1", default="")
         q.add_argument("-2", "--reads2", default="")
@@ -145,6 +148,9 @@ def main_kmer_table(argv=None) -> int:
         if name == "histo":
             q.add_argument("--high", type=int, default=10000)
             q.add_argument("--full", action="store_true")
+            q.add_argument("-o", "--output", required=True)
+        elif name == "dump":
+            q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
             q.add_argument("-o", "--output", required=True)
         else:
             q.add_argument("-q", "--queries", default="")
@@ -162,6 +168,10 @@ def main_kmer_table(argv=None) -> int:
             hist = _table_for(a).spectrum(a.high)
             with open(a.output, "w") as f:
                 f.writelines(f"{c} {int(hist[c])}\n" for c in range(1, a.high + 2) if a.full or hist[c])
+        elif a.cmd == "dump":
+            if a.lower < 1:
+                raise ValueError(f"-L must be at least 1 (got {a.lower})")
+            _table_for(a).write_dump(a.output, a.lower)
         else:
             from .kmer import encode_kmers
             asked = list(a.kmers)

@@ -31,21 +31,7 @@
 namespace {
 enum { TK_NONE = 0, TK_DENSE = 1, TK_HASH = 2, TK_WIDE = 3, TK_MINI = 4, TK_MINIW = 5 };
 
-// Packed hash tables (k <= 21) do not store the canonical code but key42(code): a BIJECTION of the 42-bit codes onto
-// themselves with the avalanche of a hash (two xorshift-multiply rounds modulo 2^42; every step is invertible, the
-// inverse is in pangaea_amd/kmer.py).  A k-mer is hashed ONCE, where it leaves the read stream; from then on every
-// consumer takes its digit, bucket and slot straight from the bits of the key -- bucket = top bits, slot = the bits
-// below -- and the key alone identifies the k-mer, in partition records, in table slots and between ranks.
-constexpr int KEY_BITS = 42;
-constexpr uint64_t KEY_MASK = (1ull << KEY_BITS) - 1;
-static_assert(2 * PG_HASH_MAX_K == KEY_BITS, "the packed table keys cover exactly the codes of the largest k");
-__device__ __forceinline__ uint64_t key42(uint64_t x)
-{
-    x ^= x >> 21; x = (x * PG_KEY42_M1) & KEY_MASK;
-    x ^= x >> 21; x = (x * PG_KEY42_M2) & KEY_MASK;
-    x ^= x >> 21;
-    return x;
-}
+// (key42, the slot key of the packed hash tables, and its inverse: pg_device.hpp)
 
 // hash table as the kernels see it: 2^log2_slots slots in buckets of 2^log2_bucket slots; a key's home slot is its top
 // log2_slots bits (packed form) / the top bits of mix64(code) (wide form), probing is linear and wraps inside the
@@ -371,6 +357,284 @@ __global__ __launch_bounds__(BIG_BLOCK) void table_spectrum_kernel(const uint4 *
     for (int i = threadIdx.x; i < n_bins; i += BIG_BLOCK) {
         const uint32_t s = bins[i];
         if (s) atomicAdd(&hist[i], (unsigned long long)s);
+    }
+}
+
+// -------------------------------------------------------------------------------- the table as jellyfish's text dump, and back
+//
+// `jellyfish dump -c -t` of the table (feature.py:87,103: the abundance.k{k}.dump the reference leaves on disk) and the reload
+// of such a file (count_kmer.cpp:139-170).  One line per kept entry, "<k-mer>\t<count>\n", the first character of the k-mer from
+// the highest two bits of the canonical code, A C T G for 0 1 2 3; lines in slot order.  The table is only read, by plain loads.
+//
+// A UNIT is PG_DUMP_UNIT_SLOTS consecutive entries: one workgroup of BLOCK lanes, DUMP_PER consecutive entries per lane (16 bytes
+// of dense counters, 32 of packed slots or of keys).  Pass 1 (table_dump_sizes_kernel) leaves the text bytes of every unit, the
+// caller scans them, pass 2 (table_dump_text_kernel) writes each unit's lines where the scan puts them.
+enum { DUMP_DENSE = 0, DUMP_HASH = 1, DUMP_MINI = 2, DUMP_PLANES = 3 };
+constexpr int DUMP_PER = PG_DUMP_UNIT_SLOTS / BLOCK;
+static_assert(DUMP_PER == 4, "a lane's entries are one 16-byte load of dense counters");
+constexpr int DUMP_MAX_LINE = PG_WIDE_MAX_K + 2 + 10;                       // 31 letters, TAB, a 32-bit count, newline
+constexpr int DUMP_LDS_BYTES = PG_DUMP_UNIT_SLOTS * DUMP_MAX_LINE + 16;     // (+ the text's misalignment in global memory)
+
+__device__ __forceinline__ uint32_t dump_digits(uint32_t c)
+{
+    return c < 10u ? 1u : c < 100u ? 2u : c < 1000u ? 3u : c < 10000u ? 4u : c < 100000u ? 5u : c < 1000000u ? 6u
+         : c < 10000000u ? 7u : c < 100000000u ? 8u : c < 1000000000u ? 9u : 10u;
+}
+
+// entries 4 * quad .. 4 * quad + 3 of the table: present (in the table at all), code (FORM's own: the index, the key, the code),
+// count.  quad < n_entries / 4 (the caller's business).
+template <int FORM>
+__device__ __forceinline__ void dump_load(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t quad,
+                                          uint64_t raw[DUMP_PER], uint32_t cnt[DUMP_PER], bool present[DUMP_PER])
+{
+    if (FORM == DUMP_DENSE) {
+        const uint4 v = slots[quad];
+        const uint32_t c[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < DUMP_PER; ++q) { raw[q] = (uint64_t)(4 * quad + q); cnt[q] = c[q]; present[q] = c[q] != 0; }
+    } else {
+        const uint4 a = slots[2 * quad], b = slots[2 * quad + 1];
+        const uint64_t s[4] = {((uint64_t)a.y << 32) | a.x, ((uint64_t)a.w << 32) | a.z, ((uint64_t)b.y << 32) | b.x, ((uint64_t)b.w << 32) | b.z};
+        uint32_t c[4] = {0, 0, 0, 0};
+        if (FORM == DUMP_PLANES) { const uint4 v = counts[quad]; c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w; }
+#pragma unroll
+        for (int q = 0; q < DUMP_PER; ++q) {
+            present[q] = s[q] != 0;
+            if (FORM == DUMP_PLANES) { raw[q] = s[q] - 1; cnt[q] = c[q]; }
+            else { raw[q] = s[q] >> HASH_CBITS; cnt[q] = (uint32_t)(s[q] & HASH_CMASK); }
+        }
+    }
+}
+
+// sum over the workgroup (BLOCK lanes) of v, and the sum over the lanes before this one; `part` = WAVES words of LDS, free again
+// after the call's second barrier
+__device__ __forceinline__ uint32_t dump_block_scan(uint32_t v, uint32_t *part, uint32_t *total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(incl, d);
+        if (lane >= d) incl += o;
+    }
+    if (lane == 63) part[wave] = incl;
+    lds_sync();
+    uint32_t before = incl - v, tot = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const uint32_t t = part[w];
+        if (w < wave) before += t;
+        tot += t;
+    }
+    lds_sync();
+    *total = tot;
+    return before;
+}
+
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void table_dump_sizes_kernel(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t n_entries,
+                                                                 int64_t n_units, int k, uint64_t lower, long long *__restrict__ unit_bytes,
+                                                                 long long *__restrict__ unit_lines)
+{
+    __shared__ uint32_t part[WAVES];
+    for (int64_t u = blockIdx.x; u < n_units; u += gridDim.x) {
+        const int64_t quad = u * (PG_DUMP_UNIT_SLOTS / DUMP_PER) + threadIdx.x;
+        uint32_t bytes = 0, lines = 0;
+        if (quad * DUMP_PER < n_entries) {
+            uint64_t raw[DUMP_PER];
+            uint32_t cnt[DUMP_PER];
+            bool present[DUMP_PER];
+            dump_load<FORM>(slots, counts, quad, raw, cnt, present);
+#pragma unroll
+            for (int q = 0; q < DUMP_PER; ++q)
+                if (present[q] && (uint64_t)cnt[q] >= lower) { bytes += (uint32_t)k + 2u + dump_digits(cnt[q]); ++lines; }
+        }
+        // (both sums in one scan: a unit has at most 2^10 lines of at most 43 bytes)
+        uint32_t total;
+        dump_block_scan((bytes << 11) | lines, part, &total);
+        if (threadIdx.x == 0) {
+            unit_bytes[u] = (long long)(total >> 11);
+            if (unit_lines) unit_lines[u] = (long long)(total & 2047u);
+        }
+    }
+}
+
+// The lines of units [unit_begin, unit_end) into `text`: unit u's at byte unit_offsets[u] - text_base.  A unit is formatted in
+// LDS -- every lane writes its lines behind those of the lanes before it -- and leaves by 16-byte stores: the LDS image starts at
+// the misalignment of its place in global memory, so 16-byte pieces of the one are 16-byte pieces of the other; the fewer than 16
+// bytes in front of the first aligned piece and behind the last go byte-wise.  No byte outside [0, range_bytes) of `text` is
+// written, whatever the offsets say.
+template <int FORM>
+__global__ __launch_bounds__(BLOCK) void table_dump_text_kernel(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t n_entries,
+                                                                int64_t unit_begin, int64_t unit_end, int k, uint64_t lower,
+                                                                const long long *__restrict__ unit_offsets, int64_t text_base, int64_t range_bytes,
+                                                                uint8_t *__restrict__ text)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t img[DUMP_LDS_BYTES];
+    __shared__ uint32_t part[WAVES];
+    for (int64_t u = unit_begin + blockIdx.x; u < unit_end; u += gridDim.x) {
+        const int64_t quad = u * (PG_DUMP_UNIT_SLOTS / DUMP_PER) + threadIdx.x;
+        uint64_t raw[DUMP_PER];
+        uint32_t cnt[DUMP_PER], len[DUMP_PER] = {0, 0, 0, 0};
+        if (quad * DUMP_PER < n_entries) {
+            bool present[DUMP_PER];
+            dump_load<FORM>(slots, counts, quad, raw, cnt, present);
+#pragma unroll
+            for (int q = 0; q < DUMP_PER; ++q)
+                if (present[q] && (uint64_t)cnt[q] >= lower) len[q] = (uint32_t)k + 2u + dump_digits(cnt[q]);
+        }
+        uint32_t total;
+        uint32_t at = dump_block_scan(len[0] + len[1] + len[2] + len[3], part, &total);
+        const int64_t dst = (int64_t)unit_offsets[u] - text_base;            // where the unit's text starts in `text`
+        const uint32_t mis = (uint32_t)(((uintptr_t)text + (uint64_t)dst) & 15u);
+        at += mis;
+#pragma unroll
+        for (int q = 0; q < DUMP_PER; ++q) {
+            if (len[q] == 0) continue;
+            const uint64_t code = FORM == DUMP_HASH ? key42_inverse(raw[q]) : raw[q];
+            for (int j = 0; j < k; ++j) img[at + j] = (uint8_t)(0x47544341u >> (8 * ((uint32_t)(code >> (2 * (k - 1 - j))) & 3u)));   // "ACTG"
+            img[at + k] = '\t';
+            uint32_t c = cnt[q];
+            for (uint32_t p = at + len[q] - 2; p > at + k; --p) { img[p] = (uint8_t)('0' + c % 10u); c /= 10u; }
+            img[at + len[q] - 1] = '\n';
+            at += len[q];
+        }
+        lds_sync();
+        // head: up to the first 16-byte boundary of global memory; body: whole 16-byte pieces; tail: the rest
+        const uint32_t head = total < ((16u - mis) & 15u) ? total : ((16u - mis) & 15u);
+        const uint32_t n16 = (total - head) >> 4;
+        const uint32_t tail = total - head - (n16 << 4);
+        for (uint32_t i = threadIdx.x; i < n16; i += BLOCK) {
+            const int64_t p = dst + head + ((int64_t)i << 4);
+            if (p >= 0 && p + 16 <= range_bytes) *(uint4 *)(text + p) = *(const uint4 *)(img + mis + head + (i << 4));
+        }
+        if (threadIdx.x < head + tail) {
+            const uint32_t o = threadIdx.x < head ? threadIdx.x : total - tail + (threadIdx.x - head);
+            const int64_t p = dst + o;
+            if (p >= 0 && p < range_bytes) text[p] = img[mis + o];
+        }
+        lds_sync();                                                       // (the image is rewritten by the next unit)
+    }
+}
+
+// ---- the reload: text -> (canonical code, count, line ordinal) of every line that holds a k-mer over ACGT
+//
+// Tiles of BLOCK x 16 bytes, a lane owning 16 consecutive bytes.  dump_newlines_kernel counts the newlines of every tile, one
+// scan turns the counts into the ordinal of each tile's first line start, dump_parse_kernel then finds the line starts of its
+// tile (the byte behind a newline, and byte 0), numbers them by a scan over the lanes' newline counts and lets the lane that owns
+// a line's first byte read that line -- at most 64 bytes of it; the longest legal line has 31 + 1 + 18 + 2.  A lane with several
+// line starts (lines may be as short as "A\t1\n", or blank) takes them in turns of the whole wavefront: every turn ends with a
+// ballot and one add to the output counter per wavefront.  Kept entries land in no particular order -- their ordinals say where
+// they stood.  Semantics: cli.load_dump (pangaea_amd/cli.py), which is count_kmer.cpp:144-169 on any file jellyfish has written.
+constexpr int PARSE_TILE = BLOCK * 16;
+
+// bit i = byte i of the lane's 16 is a newline.  p0 < n; `text` is 16-byte aligned, so a full piece is one load
+__device__ __forceinline__ uint32_t dump_newline_mask(const uint8_t *__restrict__ text, int64_t p0, int64_t n)
+{
+    uint32_t m = 0;
+    if (p0 + 16 <= n) {
+        const uint4 v = *(const uint4 *)(text + p0);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint32_t x = w[q] ^ 0x0A0A0A0Au;
+            const uint32_t f = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);      // 0x80 in every byte that is zero
+            m |= (((f >> 7) & 1u) | ((f >> 14) & 2u) | ((f >> 21) & 4u) | ((f >> 28) & 8u)) << (4 * q);
+        }
+    } else {
+        for (int i = 0; p0 + i < n; ++i) m |= (uint32_t)(text[p0 + i] == '\n') << i;
+    }
+    return m;
+}
+
+__global__ __launch_bounds__(BLOCK) void dump_newlines_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t n_tiles, unsigned long long *__restrict__ hist)
+{
+    __shared__ uint32_t part[WAVES];
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * PARSE_TILE + (int64_t)threadIdx.x * 16;
+        uint32_t total;
+        dump_block_scan(p0 < n ? (uint32_t)__popc(dump_newline_mask(text, p0, n)) : 0u, part, &total);
+        if (threadIdx.x == 0) hist[tile] = total;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void dump_parse_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t n_tiles,
+                                                           const unsigned long long *__restrict__ tile_first, int k, int64_t first_ordinal,
+                                                           uint64_t *__restrict__ codes, uint64_t *__restrict__ counts, long long *__restrict__ ordinals,
+                                                           int64_t cap, unsigned long long *__restrict__ n_out, unsigned long long *__restrict__ status)
+{
+    __shared__ uint32_t part[WAVES];
+    const int lane = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x == 0) n_out[1] = tile_first[n_tiles] + (text[n - 1] != '\n');     // lines of the text
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * PARSE_TILE + (int64_t)threadIdx.x * 16;
+        uint32_t nl = 0, starts = 0;
+        if (p0 < n) {
+            nl = dump_newline_mask(text, p0, n);
+            starts = ((nl << 1) | (uint32_t)(p0 == 0 || text[p0 - 1] == '\n')) & 0xffffu;
+            if (p0 + 16 > n) starts &= (1u << (int)(n - p0)) - 1u;
+        }
+        uint32_t total;
+        const uint64_t before = tile_first[tile] + dump_block_scan((uint32_t)__popc(nl), part, &total);
+        for (;;) {
+            const bool have = starts != 0;
+            if (!__any(have)) break;
+            bool keep = false;
+            uint64_t canon = 0, count = 0, line = 0;
+            if (have) {
+                const int b = __ffs(starts) - 1;
+                starts &= starts - 1;
+                line = (uint64_t)first_ordinal + before + (uint64_t)__popc(nl & ((1u << b) - 1u));
+                int64_t i = p0 + b;
+                uint64_t fw = 0;
+                int len = 0;
+                bool acgt = true;
+                uint32_t c = '\n';                               // (the end of the text ends a line)
+                for (; i < n; ++i) {
+                    c = text[i];
+                    if (c == '\n' || c == '\t' || len >= 64) break;
+                    if (len < 32) {
+                        fw = (fw << 2) | ((c >> 1) & 3u);
+                        acgt = acgt && (c == 'A' || c == 'C' || c == 'G' || c == 'T');
+                    }
+                    ++len;
+                }
+                if (i >= n) c = '\n';
+                uint32_t bad = 0;
+                if (c == '\n') {
+                    if (!(len == 0 || (len == 1 && text[i - 1] == '\r'))) bad = PG_DUMP_NO_TAB;      // (else: a blank line)
+                } else if (c != '\t' || len != k) {
+                    bad = PG_DUMP_BAD_LENGTH;
+                } else {
+                    int nd = 0;
+                    for (++i; i < n && nd <= PG_DUMP_MAX_DIGITS; ++i, ++nd) {
+                        const uint32_t d = (uint32_t)text[i] - '0';
+                        if (d > 9u) break;
+                        count = count * 10u + d;
+                    }
+                    if (i < n && text[i] == '\r') ++i;
+                    if (nd < 1 || nd > PG_DUMP_MAX_DIGITS || !(i >= n || text[i] == '\n')) bad = PG_DUMP_BAD_COUNT;
+                    else if (acgt) {
+                        const uint64_t rc = rev2_64(fw ^ 0xAAAAAAAAAAAAAAAAull) >> (64 - 2 * k);
+                        canon = fw < rc ? fw : rc;
+                        keep = true;
+                    }
+                }
+                if (bad) atomicMin(status, ((unsigned long long)(line + 1) << 8) | bad);
+            }
+            const uint64_t m = __ballot(keep);
+            if (m) {
+                const int leader = __ffsll((unsigned long long)m) - 1;
+                unsigned long long base = 0;
+                if (lane == leader) base = atomicAdd(n_out, (unsigned long long)__popcll(m));
+                base = __shfl(base, leader);
+                if (keep) {
+                    const uint64_t at = base + (uint64_t)__popcll(m & ((1ull << lane) - 1ull));
+                    if (at < (uint64_t)cap) { codes[at] = canon; counts[at] = count; ordinals[at] = (long long)line; }
+                    else atomicMin(status, ((unsigned long long)(line + 1) << 8) | PG_DUMP_CAPACITY);
+                }
+            }
+        }
     }
 }
 
@@ -2433,6 +2697,134 @@ extern "C" int pg_table_spectrum(const pg_table *t, int high, uint64_t *hist, vo
 #undef PG_LAUNCH_FORM
 #undef PG_LAUNCH
     return check_launch("pg_table_spectrum");
+}
+
+// the table as the dump kernels see it: form, entries, the counts plane of the planes form
+struct DumpView {
+    int form;
+    int64_t n_entries;
+    const uint4 *counts;
+};
+static int dump_view(const pg_table *t, const char *who, DumpView *v)
+{
+    int rc = check_table(t);
+    if (rc) return rc;
+    if ((uintptr_t)t->data & 15) return pg_fail(PG_EINVAL, "%s: t->data is not 16-byte aligned", who);
+    v->counts = nullptr;
+    if (t->kind == PG_TABLE_DENSE) {
+        v->form = DUMP_DENSE;
+        v->n_entries = (int64_t)1 << (2 * t->k);
+    } else {
+        v->form = t->kind == PG_TABLE_HASH ? DUMP_HASH : t->kind == PG_TABLE_MINI ? DUMP_MINI : DUMP_PLANES;
+        v->n_entries = (int64_t)1 << t->log2_slots;
+        if (v->form == DUMP_PLANES) v->counts = (const uint4 *)((const uint64_t *)t->data + v->n_entries);
+    }
+    return PG_OK;
+}
+
+extern "C" int64_t pg_table_dump_units(const pg_table *t)
+{
+    if (!t) return pg_fail(PG_EINVAL, "pg_table_dump_units: t is null");
+    DumpView v;
+    int rc = dump_view(t, "pg_table_dump_units", &v);
+    if (rc) return rc;
+    return (v.n_entries + PG_DUMP_UNIT_SLOTS - 1) / PG_DUMP_UNIT_SLOTS;
+}
+
+#define PG_DUMP_BY_FORM(form, LAUNCH)                                     \
+    do {                                                                  \
+        if ((form) == DUMP_DENSE) LAUNCH(DUMP_DENSE);                     \
+        else if ((form) == DUMP_HASH) LAUNCH(DUMP_HASH);                  \
+        else if ((form) == DUMP_MINI) LAUNCH(DUMP_MINI);                  \
+        else LAUNCH(DUMP_PLANES);                                         \
+    } while (0)
+
+extern "C" int pg_table_dump_sizes(const pg_table *t, int64_t lower, int64_t *unit_bytes, int64_t *unit_lines, void *stream)
+{
+    if (!t) return pg_fail(PG_EINVAL, "pg_table_dump_sizes: t is null");
+    if (!unit_bytes) return pg_fail(PG_EINVAL, "pg_table_dump_sizes: unit_bytes is null");
+    if (lower < 1) return pg_fail(PG_EINVAL, "pg_table_dump_sizes: lower is below 1 (%lld)", (long long)lower);
+    DumpView v;
+    int rc = dump_view(t, "pg_table_dump_sizes", &v);
+    if (rc) return rc;
+    const int64_t n_units = (v.n_entries + PG_DUMP_UNIT_SLOTS - 1) / PG_DUMP_UNIT_SLOTS;
+    const int grid = grid_for(n_units, 1);
+#define PG_LAUNCH(FORM)                                                                                                            \
+    hipLaunchKernelGGL((table_dump_sizes_kernel<FORM>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, (const uint4 *)t->data, v.counts, \
+                       v.n_entries, n_units, t->k, (uint64_t)lower, (long long *)unit_bytes, (long long *)unit_lines)
+    PG_DUMP_BY_FORM(v.form, PG_LAUNCH);
+#undef PG_LAUNCH
+    return check_launch("pg_table_dump_sizes");
+}
+
+extern "C" int pg_table_dump_text(const pg_table *t, int64_t lower, int64_t unit_begin, int64_t unit_end, const int64_t *unit_offsets,
+                                  int64_t text_base, int64_t range_bytes, uint8_t *text, int64_t text_bytes, void *stream)
+{
+    if (!t) return pg_fail(PG_EINVAL, "pg_table_dump_text: t is null");
+    if (!unit_offsets) return pg_fail(PG_EINVAL, "pg_table_dump_text: unit_offsets is null");
+    if (!text) return pg_fail(PG_EINVAL, "pg_table_dump_text: text is null");
+    if (lower < 1) return pg_fail(PG_EINVAL, "pg_table_dump_text: lower is below 1 (%lld)", (long long)lower);
+    if (text_base < 0) return pg_fail(PG_EINVAL, "pg_table_dump_text: text_base is negative (%lld)", (long long)text_base);
+    if (range_bytes < 0) return pg_fail(PG_EINVAL, "pg_table_dump_text: range_bytes is negative (%lld)", (long long)range_bytes);
+    if (text_bytes < 0) return pg_fail(PG_EINVAL, "pg_table_dump_text: text_bytes is negative (%lld)", (long long)text_bytes);
+    DumpView v;
+    int rc = dump_view(t, "pg_table_dump_text", &v);
+    if (rc) return rc;
+    const int64_t n_units = (v.n_entries + PG_DUMP_UNIT_SLOTS - 1) / PG_DUMP_UNIT_SLOTS;
+    if (unit_begin < 0 || unit_begin > unit_end)
+        return pg_fail(PG_EINVAL, "pg_table_dump_text: units [%lld, %lld) are no range", (long long)unit_begin, (long long)unit_end);
+    if (unit_end > n_units)
+        return pg_fail(PG_EINVAL, "pg_table_dump_text: units [%lld, %lld) reach past the table's %lld", (long long)unit_begin, (long long)unit_end, (long long)n_units);
+    if (text_bytes < range_bytes)
+        return pg_fail(PG_EINVAL, "pg_table_dump_text: text of %lld bytes is shorter than the range's %lld", (long long)text_bytes, (long long)range_bytes);
+    if (unit_end == unit_begin || range_bytes == 0) return PG_OK;
+    const int grid = grid_for(unit_end - unit_begin, 1);
+#define PG_LAUNCH(FORM)                                                                                                           \
+    hipLaunchKernelGGL((table_dump_text_kernel<FORM>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, (const uint4 *)t->data, v.counts, \
+                       v.n_entries, unit_begin, unit_end, t->k, (uint64_t)lower, (const long long *)unit_offsets, text_base, range_bytes, text)
+    PG_DUMP_BY_FORM(v.form, PG_LAUNCH);
+#undef PG_LAUNCH
+    return check_launch("pg_table_dump_text");
+}
+#undef PG_DUMP_BY_FORM
+
+extern "C" int64_t pg_dump_parse_workspace_bytes(int64_t n_bytes)
+{
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "pg_dump_parse_workspace_bytes: n_bytes is negative (%lld)", (long long)n_bytes);
+    const int64_t n_tiles = (n_bytes + PARSE_TILE - 1) / PARSE_TILE;
+    return (2 * n_tiles + 2) * (int64_t)sizeof(uint64_t);                  // newlines per tile; their exclusive scan, n_tiles + 1
+}
+
+extern "C" int pg_dump_parse(const uint8_t *text, int64_t n_bytes, int k, int64_t first_ordinal, uint64_t *codes, uint64_t *counts,
+                             int64_t *ordinals, int64_t cap, int64_t *n_out, uint64_t *status, void *workspace, int64_t workspace_bytes,
+                             void *stream)
+{
+    if (!text) return pg_fail(PG_EINVAL, "pg_dump_parse: text is null");
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "pg_dump_parse: n_bytes is negative (%lld)", (long long)n_bytes);
+    if (k < 1 || k > PG_WIDE_MAX_K) return pg_fail(PG_EINVAL, "pg_dump_parse: k %d outside [1, %d]", k, PG_WIDE_MAX_K);
+    if (first_ordinal < 0) return pg_fail(PG_EINVAL, "pg_dump_parse: first_ordinal is negative (%lld)", (long long)first_ordinal);
+    if (!codes) return pg_fail(PG_EINVAL, "pg_dump_parse: codes is null");
+    if (!counts) return pg_fail(PG_EINVAL, "pg_dump_parse: counts is null");
+    if (!ordinals) return pg_fail(PG_EINVAL, "pg_dump_parse: ordinals is null");
+    if (cap < 0) return pg_fail(PG_EINVAL, "pg_dump_parse: cap is negative (%lld)", (long long)cap);
+    if (!n_out) return pg_fail(PG_EINVAL, "pg_dump_parse: n_out is null");
+    if (!status) return pg_fail(PG_EINVAL, "pg_dump_parse: status is null");
+    if ((uintptr_t)text & 15) return pg_fail(PG_EINVAL, "pg_dump_parse: text is not 16-byte aligned");
+    if (n_bytes == 0) return PG_OK;
+    const int64_t need = pg_dump_parse_workspace_bytes(n_bytes);
+    if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < need)
+        return pg_fail(PG_EINVAL, "pg_dump_parse: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes, (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_tiles = (n_bytes + PARSE_TILE - 1) / PARSE_TILE;
+    unsigned long long *hist = (unsigned long long *)workspace, *first = hist + n_tiles + 1;
+    if (hipMemsetAsync(n_out, 0, 2 * sizeof(int64_t), s) != hipSuccess || hipMemsetAsync(status, 0xff, sizeof(uint64_t), s) != hipSuccess)
+        return pg_fail(PG_EHIP, "pg_dump_parse: cannot clear the counters");
+    const int grid = grid_for(n_tiles, 1);
+    hipLaunchKernelGGL(dump_newlines_kernel, dim3(grid), dim3(BLOCK), 0, s, text, n_bytes, n_tiles, hist);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)hist, n_tiles, first);
+    hipLaunchKernelGGL(dump_parse_kernel, dim3(grid), dim3(BLOCK), 0, s, text, n_bytes, n_tiles, (const unsigned long long *)first, k, first_ordinal,
+                       codes, counts, (long long *)ordinals, cap, (unsigned long long *)n_out, (unsigned long long *)status);
+    return check_launch("pg_dump_parse");
 }
 
 extern "C" int64_t pg_abundance_workspace_bytes(int64_t n_words_counted, int64_t n_rows, int vsize, const pg_table *t)

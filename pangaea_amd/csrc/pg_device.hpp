@@ -28,6 +28,39 @@ __device__ __forceinline__ uint64_t mix64(uint64_t x)
     return x;
 }
 
+// Packed hash tables (k <= 21) do not store the canonical code but key42(code): a BIJECTION of the 42-bit codes onto
+// themselves with the avalanche of a hash (two xorshift-multiply rounds modulo 2^42; every step is invertible).  A k-mer is
+// hashed ONCE, where it leaves the read stream; from then on every
+// consumer takes its digit, bucket and slot straight from the bits of the key -- bucket = top bits, slot = the bits
+// below -- and the key alone identifies the k-mer, in partition records, in table slots and between ranks.
+constexpr int KEY_BITS = 42;
+constexpr uint64_t KEY_MASK = (1ull << KEY_BITS) - 1;
+static_assert(2 * PG_HASH_MAX_K == KEY_BITS, "the packed table keys cover exactly the codes of the largest k");
+__device__ __forceinline__ uint64_t key42(uint64_t x)
+{
+    x ^= x >> 21; x = (x * PG_KEY42_M1) & KEY_MASK;
+    x ^= x >> 21; x = (x * PG_KEY42_M2) & KEY_MASK;
+    x ^= x >> 21;
+    return x;
+}
+// ... and back (pangaea_amd/kmer.py: key42_inverse): the xorshifts by 21 are involutions on 42 bits, the odd multipliers have
+// inverses modulo 2^42 (Newton's iteration doubles the correct low bits: 3, 6, .. 96)
+constexpr uint64_t inverse_odd(uint64_t m)
+{
+    uint64_t x = m;
+    for (int i = 0; i < 5; ++i) x *= 2 - m * x;
+    return x;
+}
+constexpr uint64_t KEY42_M1_INV = inverse_odd(PG_KEY42_M1) & KEY_MASK, KEY42_M2_INV = inverse_odd(PG_KEY42_M2) & KEY_MASK;
+static_assert(((PG_KEY42_M1 * KEY42_M1_INV) & KEY_MASK) == 1 && ((PG_KEY42_M2 * KEY42_M2_INV) & KEY_MASK) == 1, "inverse multipliers");
+__device__ __forceinline__ uint64_t key42_inverse(uint64_t x)
+{
+    x ^= x >> 21; x = (x * KEY42_M2_INV) & KEY_MASK;
+    x ^= x >> 21; x = (x * KEY42_M1_INV) & KEY_MASK;
+    x ^= x >> 21;
+    return x;
+}
+
 // bit p of the result is set iff bits p-k+1..p of m are all set (1 <= k <= 32): which positions of the
 // 64-character window [previous word | this word] end a run of >= k valid characters.
 __device__ __forceinline__ uint64_t runs_of(uint64_t m, int k)

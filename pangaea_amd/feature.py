@@ -8,8 +8,9 @@ under ``<output>/1.features``:
     feature_finished                              (feature.py:37-38)
 The reference obtains the two matrices from three subprocesses (jellyfish, count_kmer, count_tnf) running in two
 threads; here one ingest + one table build + one fused feature launch produce both, and the two ``calcu_*``
-methods only differ in which cache file they write.  ``abundance.k{k}.count/.dump`` (jellyfish's own files) are
-not produced: the multiplicity table lives in HBM.
+methods only differ in which cache file they write.  The multiplicity table lives in HBM; of jellyfish's own files
+``abundance.k{k}.dump`` (feature.py:87,103: what ``count_kmer -g`` and later runs with other -s / -v read) is written from it
+when PANGAEA_WRITE_DUMP=1 asks for it (one rank; ``KmerTable.write_dump``), the binary ``abundance.k{k}.count`` never.
 
 Values are returned exactly as the reference returns them, i.e. as pandas would re-read the CSV cache
 (feature.py:113-123): counts >= 1 000 000 pass through ``%g`` (six significant digits) and turn their column into
@@ -123,7 +124,8 @@ def _sharded_mini_applies(stream, plan, k, window, vsize, lowercase_is_base) -> 
 
 def compute_features(reads1: str, reads2: str | None, k: int, k_tnf: int, window: int, vsize: int, min_len: int,
                      device=None, want_tnf: bool = True, want_abd: bool = True, table: KmerTable | None = None,
-                     stream_cache: str | None = None, lowercase_is_base: bool = True, gather: str = "all"):
+                     stream_cache: str | None = None, lowercase_is_base: bool = True, gather: str = "all",
+                     dump_path: str | None = None):
     """(names, tnf int32 ndarray or None, abd int32 ndarray or None) of a barcode-sorted FASTQ, on the GPU.
 
     Under an initialised ``torch.distributed`` group every rank takes a contiguous range of runs and the table is
@@ -131,7 +133,9 @@ def compute_features(reads1: str, reads2: str | None, k: int, k_tnf: int, window
       "none"   every rank returns its own block of rows (rank order = file order);
       "rank0"  rank 0 additionally receives all blocks (it writes the cache files) and returns
                (names, tnf, abd, local) with ``local`` = its own block; the other ranks return their block;
-      "all"    every rank returns the full matrices (single-call convenience: the CLI tools)."""
+      "all"    every rank returns the full matrices (single-call convenience: the CLI tools).
+    ``dump_path``: the table counted here is also written there as jellyfish's text dump (one rank only: the union table of
+    several ranks is spread over its owners and is not written)."""
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
     world = torch.distributed.get_world_size() if pdist.is_distributed() else 1
@@ -167,6 +171,12 @@ def compute_features(reads1: str, reads2: str | None, k: int, k_tnf: int, window
                                       load=None if sketch is None else 0.4))
         tnf, abd = features(stream, plan, k_tnf=k_tnf if want_tnf else None, table=table if want_abd else None,
                             window=window, vsize=vsize)
+    if dump_path and want_abd:
+        if world > 1:
+            logging.info(f"{dump_path} is not written on {world} ranks: the table is spread over its owners")
+        else:
+            lines, nbytes = table.write_dump(dump_path)
+            logging.info(f"wrote {dump_path}: {lines} k-mers, {nbytes} bytes")
     names = list(rows.names)
     host = lambda t: t.cpu().numpy() if t is not None else None
     if world == 1 or gather == "none":
@@ -241,9 +251,12 @@ class Feature:
             logging.info("GPU feature pass: ingest + k-mer table + TNF/abundance rows")
             # PANGAEA_STREAM_CACHE=1 keeps the packed read stream next to the feature caches (1.features/reads.*.pgstream)
             cache = os.path.join(self.feature_dir, "reads") if os.environ.get("PANGAEA_STREAM_CACHE", "0") not in ("", "0") else None
+            # PANGAEA_WRITE_DUMP=1 leaves the table as 1.features/abundance.k{k}.dump, the file of feature.py:87,103
+            dump = (os.path.join(self.feature_dir, f"abundance.k{self.kmer}.dump")
+                    if os.environ.get("PANGAEA_WRITE_DUMP", "0") not in ("", "0") else None)
             out = compute_features(r1, r2, int(self.kmer), int(self.tnf_k), int(self.ws), int(self.vs), int(self.minl),
                                            device=getattr(self.args, "device", None), want_tnf=want_tnf, want_abd=want_abd,
-                                           stream_cache=cache, gather="rank0",
+                                           stream_cache=cache, gather="rank0", dump_path=dump,
                                            # jellyfish's rules for the multiplicity table (feature.py:76-94): lower-case bases
                                            # count (soft-masked input; PANGAEA_LOWERCASE_IS_BASE=0 turns that off), bases
                                            # below --min-qual-char=? of paired files do not (ReadStream.table_valid)

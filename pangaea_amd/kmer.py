@@ -214,9 +214,17 @@ class KmerTable:
     @classmethod
     def from_items(cls, k: int, codes, counts, device, kind: str | None = None) -> "KmerTable":
         """table holding exactly the given (canonical code, count) entries -- e.g. a parsed jellyfish dump
-        (count_kmer.cpp:139-170 assigns, it does not add: later duplicates must already be resolved)"""
-        codes = torch.as_tensor(np.asarray(codes).astype(np.int64))
-        counts = torch.as_tensor(np.asarray(counts).astype(np.int64))
+        (count_kmer.cpp:139-170 assigns, it does not add: later duplicates must already be resolved).  ``codes`` a tensor on a
+        GPU (then ``counts`` too; int64 or uint64): the entries stay on the device -- what ``from_dump`` hands over -- and the
+        table is the one the same entries make as numpy arrays."""
+        on_device = isinstance(codes, torch.Tensor) and codes.is_cuda
+        if on_device:
+            if not (isinstance(counts, torch.Tensor) and counts.is_cuda) or codes.numel() != counts.numel():
+                raise ValueError("codes on the device need as many counts on the device")
+            codes, counts = codes.reshape(-1).view(torch.int64), counts.reshape(-1).view(torch.int64)
+        else:
+            codes = torch.as_tensor(np.asarray(codes).astype(np.int64))
+            counts = torch.as_tensor(np.asarray(counts).astype(np.int64))
         table = cls.alloc(k, device, kind, distinct_hint=max(1024, codes.numel()))
         if table.kind in ("wide", "miniw"):
             c = codes.to(table.device).contiguous()
@@ -233,9 +241,145 @@ class KmerTable:
             table.merge(((codes << _lib.HASH_COUNT_BITS) | sat)[sat > 0])
         else:
             sat = torch.clamp(counts, max=_lib.HASH_COUNT_SAT)
-            keys = torch.from_numpy(key42(codes.numpy().view(np.uint64)).view(np.int64))
+            keys = key42_torch(codes) if on_device else torch.from_numpy(key42(codes.numpy().view(np.uint64)).view(np.int64))
             table.merge(((keys << _lib.HASH_COUNT_BITS) | sat)[sat > 0])
         return table
+
+    # ------------------------------------------------------------------ jellyfish's text dump (feature.py:87,103; count_kmer.cpp:139-170)
+
+    DUMP_PIECE_BYTES = 256 << 20           # text per piece of ``write_dump`` / ``from_dump`` (device buffer + pinned host buffer)
+
+    @staticmethod
+    def _dump_piece_bytes() -> int:
+        """PG_DUMP_PIECE_BYTES overrides the piece size (tests: pieces that start mid-table, lines across every boundary)"""
+        want = os.environ.get("PG_DUMP_PIECE_BYTES")
+        return max(256, int(want)) if want else KmerTable.DUMP_PIECE_BYTES
+
+    @property
+    def n_entries(self) -> int:
+        return 4 ** self.k if self.kind == "dense" else 1 << self.log2_slots
+
+    def write_dump(self, path: str, lower: int = 1) -> tuple:
+        """the table as ``jellyfish dump -c -t -L lower`` writes it (the abundance.k{k}.dump of src/feature.py:87,103): one line
+        ``<k-mer>\t<count>\n`` per entry with count >= ``lower``, in slot order -- for a given table always the same bytes.  A
+        packed table (k <= 21, not dense) writes HASH_COUNT_SAT for every count at or above it.  Formatted on the device unit
+        range by unit range, each piece at most ``DUMP_PIECE_BYTES`` of text, copied to pinned memory and appended; the file
+        appears under its name only when it is complete.  Returns (lines, bytes)."""
+        lower = int(lower)
+        if lower < 1:
+            raise ValueError(f"lower must be at least 1 (got {lower})")
+        self._require_readable()
+        L = _lib.load()
+        n_units = (self.n_entries + _lib.DUMP_UNIT_SLOTS - 1) // _lib.DUMP_UNIT_SLOTS
+        dev = self.device
+        tmp = path + ".tmp"
+        try:
+            with torch.cuda.device(dev), open(tmp, "wb") as f:
+                sizes = torch.empty((2, n_units), dtype=torch.int64, device=dev)
+                _lib.check(L.pg_table_dump_sizes(self.desc(), lower, sizes[0].data_ptr(), sizes[1].data_ptr(), _stream_ptr(dev)))
+                offsets = torch.zeros(n_units + 1, dtype=torch.int64, device=dev)
+                torch.cumsum(sizes[0], 0, out=offsets[1:])
+                lines = int(sizes[1].sum().item())
+                off = offsets.cpu().numpy()
+                total = int(off[-1])
+                # unit ranges of at most a piece of text (a single unit may be more than a small piece: it then is a piece)
+                piece = self._dump_piece_bytes()
+                ranges, u0 = [], 0
+                while u0 < n_units:
+                    u1 = max(u0 + 1, int(np.searchsorted(off, off[u0] + piece, side="right")) - 1)
+                    ranges.append((u0, u1))
+                    u0 = u1
+                room = max((int(off[b] - off[a]) for a, b in ranges), default=0)
+                if room:
+                    text = torch.empty(room, dtype=torch.uint8, device=dev)
+                    host = torch.empty(room, dtype=torch.uint8, pin_memory=True)
+                for a, b in ranges:
+                    nb = int(off[b] - off[a])
+                    if nb == 0:
+                        continue
+                    _lib.check(L.pg_table_dump_text(self.desc(), lower, a, b, offsets.data_ptr(), int(off[a]), nb, text.data_ptr(), room,
+                                                    _stream_ptr(dev)))
+                    host[:nb].copy_(text[:nb], non_blocking=True)
+                    torch.cuda.current_stream(dev).synchronize()
+                    f.write(memoryview(host.numpy())[:nb])
+            os.replace(tmp, path)
+        finally:
+            if os.path.exists(tmp):
+                os.remove(tmp)
+        return lines, total
+
+    @classmethod
+    def from_dump(cls, path: str, k: int, device, kind: str | None = None) -> "KmerTable":
+        """table of a jellyfish text dump (``dump -c -t``; plain text, as the reference reads it), with the loader semantics of
+        count_kmer.cpp:139-170 as ``cli.load_dump`` states them: later lines override earlier ones, k-mers with a character
+        outside ACGT are dropped, blank lines skipped, CRLF tolerated; a k-mer of another length than ``k`` or a malformed count
+        raises ValueError with the line.  The file is read piece by piece (cut behind the last newline, the rest carried into the
+        next piece) into pinned memory, parsed on the device, and the entries never come back to the host."""
+        k = int(k)
+        if not 1 <= k <= _lib.WIDE_MAX_K:
+            raise ValueError(f"k-mer size {k} unsupported (1..{_lib.WIDE_MAX_K}, as the reference)")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"the dump is parsed on a GPU: there is no CPU path (got {device})")
+        L = _lib.load()
+        piece = cls._dump_piece_bytes()
+        codes, counts, ordinals = [], [], []
+        with torch.cuda.device(device), open(path, "rb", buffering=0) as f:
+            sp = _stream_ptr(device)
+            host = torch.empty(piece, dtype=torch.uint8, pin_memory=True)
+            buf = host.numpy()
+            text = torch.empty(piece + 16, dtype=torch.uint8, device=device)
+            cap = piece // (k + 2) + 1                                    # a kept line has k + 2 bytes at least
+            out = torch.empty((3, cap), dtype=torch.int64, device=device)
+            ws = torch.empty(_lib.check(L.pg_dump_parse_workspace_bytes(piece)), dtype=torch.uint8, device=device)
+            word = torch.empty(3, dtype=torch.int64, device=device)       # kept lines, lines, status
+            have, line0, eof = 0, 0, False
+            while not eof:
+                end = have
+                while end < piece:
+                    got = f.readinto(memoryview(buf)[end:])
+                    if not got:
+                        break
+                    end += got
+                eof = end < piece
+                cut = end
+                if not eof:
+                    # behind the last newline; a piece without any holds a line no dump has (the parser says which)
+                    at = end
+                    while at > 0:
+                        lo = max(0, at - 4096)
+                        j = buf[lo:at].tobytes().rfind(b"\n")
+                        if j >= 0:
+                            cut = lo + j + 1
+                            break
+                        at = lo
+                if cut:
+                    text[:cut].copy_(host[:cut], non_blocking=True)
+                    _lib.check(L.pg_dump_parse(text.data_ptr(), cut, k, line0, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), cap,
+                                               word.data_ptr(), word[2:].data_ptr(), ws.data_ptr(), ws.numel(), sp))
+                    n_kept, n_lines, status = (int(v) for v in word.cpu())   # (waits for the copy and the parse: ``host`` is free again)
+                    if status != -1:
+                        raise ValueError(_dump_error(path, k, status & ((1 << 64) - 1)))
+                    if n_kept:
+                        codes.append(out[0, :n_kept].clone())
+                        counts.append(out[1, :n_kept].clone())
+                        ordinals.append(out[2, :n_kept].clone())
+                    line0 += n_lines
+                have = end - cut
+                if have:
+                    buf[:have] = buf[cut:end].copy()
+            del text, out, ws
+            if not codes:
+                empty = torch.zeros(0, dtype=torch.int64, device=device)
+                return cls.from_items(k, empty, empty, device, kind)
+            codes, counts, ordinals = torch.cat(codes), torch.cat(counts), torch.cat(ordinals)
+            # later lines override earlier ones (count_kmer.cpp:166): file order, then a stable sort by code, the last of a run stays
+            order = torch.argsort(ordinals)
+            del ordinals
+            sc, idx = torch.sort(codes[order], stable=True)
+            last = torch.ones(sc.numel(), dtype=torch.bool, device=device)
+            last[:-1] = sc[1:] != sc[:-1]
+            return cls.from_items(k, sc[last], counts[order[idx[last]]], device, kind)
 
     @property
     def device(self) -> torch.device:
@@ -1212,6 +1356,29 @@ def key42(codes: np.ndarray) -> np.ndarray:
         x = (x * np.uint64(m)) & _KEY_MASK
     x ^= x >> np.uint64(21)
     return x
+
+
+def key42_torch(codes: torch.Tensor) -> torch.Tensor:
+    """``key42`` of an int64 tensor of codes below 2^42, wherever it lives: int64 products wrap modulo 2^64, of which the low 42
+    bits are kept, and every intermediate is non-negative, so the shifts are logical"""
+    x = codes.clone()
+    for m in (_lib.KEY42_M1, _lib.KEY42_M2):
+        x ^= x >> 21
+        x = (x * m) & ((1 << 42) - 1)
+    x ^= x >> 21
+    return x
+
+
+_DUMP_REASONS = {_lib.DUMP_NO_TAB: "no TAB between k-mer and count", _lib.DUMP_BAD_COUNT: f"the count is not 1 to {_lib.DUMP_MAX_DIGITS} decimal digits",
+                 _lib.DUMP_CAPACITY: "more lines than the parser was given room for"}
+
+
+def _dump_error(path: str, k: int, status: int) -> str:
+    """the message for pg_dump_parse's status word: (1-based line << 8) | reason"""
+    line, reason = status >> 8, status & 0xFF
+    if reason == _lib.DUMP_BAD_LENGTH:
+        return f"{path}: dump holds k-mers whose length is not {k} (line {line})"
+    return f"{path}: line {line}: {_DUMP_REASONS.get(reason, f'malformed (reason {reason})')}"
 
 
 def key42_inverse(keys: np.ndarray) -> np.ndarray:
