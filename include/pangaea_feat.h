@@ -435,6 +435,35 @@ int pg_dump_parse(const uint8_t *text, int64_t n_bytes, int k, int64_t first_ord
                   void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Merging finished tables (device; one GPU, any of the five kinds).  The reference counts every read of a sample into ONE
+ * jellyfish table (src/feature.py:76-94); a sample that arrives as several files -- lanes, runs, a dump from elsewhere plus new
+ * reads -- becomes that table through `jellyfish merge`: one table that holds the sum of several.  All three entries are additive
+ * to ABI 9; every argument is checked before anything is enqueued (PG_EINVAL with a pg_last_error text: a null pointer, differing
+ * k, a kind that does not admit k, differing geometry for the aligned form, dst overlapping a source, n_srcs outside 1..16);
+ * sources are only read (plain loads), every t->data must be 16-byte aligned.  Sums of 2^32 and more are outside the contract,
+ * as they are for counting.
+ *   pg_table_merge          replaces `jellyfish merge` over the tables of feature.py:76-94, general form: every entry of `src`
+ *                           is ADDED to what `dst` holds, whatever the two kinds and geometries (both must admit the same k).
+ *                           Dense: atomic adds; hash / mini: counts saturate at PG_HASH_COUNT_SAT exactly (a packed source's
+ *                           saturated count travels as the value it stores, 2^21); wide / wide mini: 32-bit sums.  A
+ *                           destination without room sets PG_STATUS_TABLE_FULL in status[0] (device uint32_t[2], zeroed by the
+ *                           caller; may be NULL for a dense dst): enlarge it and merge again.
+ *   pg_table_merge_aligned  replaces `jellyfish merge` over the tables of feature.py:76-94 where dst and the n_srcs sources
+ *                           (1..16; the same source may appear twice) are all PG_TABLE_MINI, or all PG_TABLE_HASH in buckets of
+ *                           at most 2^PG_BUCKET_MAX_LOG2_SLOTS slots, with one k, log2_slots and log2_bucket_slots: a k-mer
+ *                           then lies in the same bucket of every table, one workgroup per bucket sums the sources' slices
+ *                           inside LDS and writes the slice of dst once -- only streams, no global atomics.  dst is REBUILT:
+ *                           its old content is neither read nor need be initialised.  A bucket whose union does not fit sets
+ *                           PG_STATUS_TABLE_FULL (dst is then incomplete: take pg_table_merge into a larger table).
+ *   pg_table_merge_aligned_applies  replaces nothing of the reference: the one statement of the rule above -- 1 when tables a
+ *                           and b (kinds, k and geometry, their data is not looked at) may stand together in a
+ *                           pg_table_merge_aligned call (`jellyfish merge` over the tables of feature.py:76-94), else 0.
+ * ---------------------------------------------------------------------------------------------- */
+int pg_table_merge(const pg_table *dst, const pg_table *src, uint32_t *status, void *stream);
+int pg_table_merge_aligned(const pg_table *dst, const pg_table *const *srcs, int n_srcs, uint32_t *status, void *stream);
+int pg_table_merge_aligned_applies(const pg_table *a, const pg_table *b);
+
+/* ----------------------------------------------------------------------------------------------
  * Per-run feature rows (device).  One launch fills both matrices.
  *   tnf_out [n_rows, ncols(k_tnf)] int32: canonical k_tnf-mer counts        (count_tnf.cpp:78-113)
  *   abd_out [n_rows, vsize]        int32: hist[count(kmer)/window]++ where the bin is < vsize

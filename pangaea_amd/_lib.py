@@ -177,6 +177,9 @@ def load() -> C.CDLL:
         "pg_table_dump_text": (i32, [tp, i64, i64, i64, vp, i64, i64, vp, i64, vp]),
         "pg_dump_parse_workspace_bytes": (i64, [i64]),
         "pg_dump_parse": (i32, [vp, i64, i32, i64, vp, vp, vp, i64, vp, vp, vp, i64, vp]),
+        "pg_table_merge": (i32, [tp, tp, vp, vp]),
+        "pg_table_merge_aligned": (i32, [tp, C.POINTER(tp), i32, vp, vp]),
+        "pg_table_merge_aligned_applies": (i32, [tp, tp]),
         "pg_features": (i32, [vp, vp, i64, vp, vp, vp, i64, i32, vp, vp, tp, i32, i32, vp, vp]),
         "pg_normalize_rows": (i32, [vp, i64, i32, vp, vp, vp]),
         "pg_write_csv_gz": (i32, [cp, cp, vp, i64, i64]),
@@ -209,6 +212,7 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_mini_plan_masked", "pg_mini_count_half_masked", "pg_mini_count_half_piece_masked", "pg_mini_merge_bins_masked",
            "pg_table_query", "pg_table_spectrum",
            "pg_table_dump_units", "pg_table_dump_sizes", "pg_table_dump_text", "pg_dump_parse_workspace_bytes", "pg_dump_parse",
+           "pg_table_merge", "pg_table_merge_aligned", "pg_table_merge_aligned_applies",
            "pg_features", "pg_normalize_rows", "pg_write_csv_gz", "pg_extract_reads"]
 
 

@@ -6,6 +6,7 @@
     kmer_table histo {-i F | -1 F -2 F | -g DUMP} -k K [--high 10000] [--full] -o OUT
     kmer_table query {-i F | -1 F -2 F | -g DUMP} -k K [-q FILE] [KMER ...]
     kmer_table dump  {-i F | -1 F -2 F | -g DUMP} -k K [-L LOWER] -o OUT
+    kmer_table merge -k K [-g DUMP]... [-i F]... [-L LOWER] -o OUT     (two inputs or more; `jellyfish merge` + `dump -c -t`)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -118,13 +119,19 @@ def _table_for(a):
     with the table's rule as ``Feature`` applies it (lower-case bases count unless PANGAEA_LOWERCASE_IS_BASE=0; bases of paired
     files below the quality threshold never do)"""
     import torch
-    from .kmer import KmerTable, count_kmers
-    from .reads import ReadStream
+    from .kmer import KmerTable
     device = torch.device("cuda", torch.cuda.current_device())
     if a.global_:
         return KmerTable.from_dump(a.global_, a.kmer, device)
-    stream = ReadStream.from_fastq(a.interleaved or a.reads1, None if a.interleaved else a.reads2, device=device).to(device)
-    return count_kmers(stream, a.kmer, lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+    return _counted(a.interleaved or a.reads1, None if a.interleaved else a.reads2, a.kmer, device)
+
+
+def _counted(r1: str, r2, k: int, device):
+    """the table of a FASTQ input (``r2`` None: interleaved), counted with the table's rule as ``_table_for`` states it"""
+    from .kmer import count_kmers
+    from .reads import ReadStream
+    stream = ReadStream.from_fastq(r1, r2, device=device).to(device)
+    return count_kmers(stream, k, lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
 
 
 def main_kmer_table(argv=None) -> int:
@@ -135,7 +142,10 @@ def main_kmer_table(argv=None) -> int:
     writes it, one line ``"<k-mer>\t<count>"`` per canonical k-mer of count >= LOWER (``KmerTable.write_dump``; the file
     ``count_kmer -g`` and ``kmer_table -g`` read).  The two formats of histo and query follow jellyfish's documented ``histo`` and ``query``
     output; jellyfish is not at hand to compare with, so they are unpinned (like the two rules of DESIGN section 2) -- what the
-    tests pin is the content, against the oracle.  Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
+    tests pin is the content, against the oracle.  ``kmer_table merge``: the sum of two or more inputs -- every ``-g DUMP`` loaded
+    as ``-g`` elsewhere, every ``-i FASTQ`` counted as ``-i`` elsewhere, both repeatable -- as one table (``KmerTable.merged``: what
+    `jellyfish merge` makes of the tables of feature.py:76-94), written as ``kmer_table dump`` writes it.  Exit status 0, or 1 with
+    a message on stderr, as ``main_count_kmer``."""
     p = _Parser(prog="kmer_table")
     sub = p.add_subparsers(dest="cmd", required=True)
     for name in ("histo", "query", "dump"):
@@ -155,9 +165,28 @@ def main_kmer_table(argv=None) -> int:
         else:
             q.add_argument("-q", "--queries", default="")
             q.add_argument("kmers", nargs="*")
+    q = sub.add_parser("merge")
+    q.add_argument("-g", "--global", dest="global_", action="append", default=[])
+    q.add_argument("-i", "--interleaved", action="append", default=[])
+    q.add_argument("-k", "--kmer", type=int, required=True)
+    q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
+    q.add_argument("-o", "--output", required=True)
     a = p.parse_args(argv)
     from . import _lib
     try:
+        if a.cmd == "merge":
+            if len(a.global_) + len(a.interleaved) < 2:
+                raise ValueError("merge needs two inputs or more (-g DUMP and -i FASTQ, both repeatable)")
+            if not 1 <= a.kmer <= _lib.WIDE_MAX_K:
+                raise ValueError(f"k-mer size {a.kmer} unsupported (1..{_lib.WIDE_MAX_K})")
+            if a.lower < 1:
+                raise ValueError(f"-L must be at least 1 (got {a.lower})")
+            import torch
+            from .kmer import KmerTable
+            device = torch.device("cuda", torch.cuda.current_device())
+            tables = [KmerTable.from_dump(g, a.kmer, device) for g in a.global_] + [_counted(f, None, a.kmer, device) for f in a.interleaved]
+            KmerTable.merged(tables).write_dump(a.output, a.lower)
+            return 0
         if not (a.global_ or a.interleaved or (a.reads1 and a.reads2)):
             raise ValueError("no input: -i F, -1 F -2 F or -g DUMP is needed")
         if not 1 <= a.kmer <= _lib.WIDE_MAX_K:

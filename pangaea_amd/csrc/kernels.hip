@@ -1444,6 +1444,17 @@ __device__ __forceinline__ bool lds_merge(unsigned long long *tab, uint32_t smas
     return false;
 }
 
+// one foreign slot `e` (slot format, 0 = nothing) into the LDS table, its first probe (`first` = tab[s]) already fetched: the
+// inner step of bucket_merge_kernel and table_merge_aligned_kernel.  false = the bucket has no room for it.
+__device__ __forceinline__ bool lds_merge_entry(unsigned long long *tab, uint32_t smask, uint32_t limit, uint64_t e, uint32_t s,
+                                                unsigned long long first)
+{
+    if (e == 0) return true;
+    uint32_t add = (uint32_t)(e & HASH_CMASK);
+    if (add > HASH_SAT) add = HASH_SAT;
+    return lds_merge(tab, smask, limit, e >> HASH_CBITS, add, s, first);
+}
+
 // The launch covers buckets [bucket_base, bucket_base + gridDim.x); seg has n_seg + 1 entries per part, entry j for
 // bucket bucket_base + j (a whole-table launch: base 0, n_seg = number of buckets).
 __global__ __launch_bounds__(BIG_BLOCK) void bucket_merge_kernel(const uint64_t *__restrict__ pairs, const long long *__restrict__ seg,
@@ -1479,12 +1490,7 @@ __global__ __launch_bounds__(BIG_BLOCK) void bucket_merge_kernel(const uint64_t 
                 ss[j] = (uint32_t)((e[j] >> HASH_CBITS) >> hsh) & smask;
                 first[j] = e[j] ? tab[ss[j]] : 0ull;
             }
-#define PG_MERGE(J)                                                                                                         \
-            if (e[J]) {                                                                                                     \
-                uint32_t add = (uint32_t)(e[J] & HASH_CMASK);                                                               \
-                if (add > HASH_SAT) add = HASH_SAT;                                                                         \
-                full |= !lds_merge(tab, smask, limit, e[J] >> HASH_CBITS, add, ss[J], first[J]);                            \
-            }
+#define PG_MERGE(J) full |= !lds_merge_entry(tab, smask, limit, e[J], ss[J], first[J]);
             PG_MERGE(0) PG_MERGE(1) PG_MERGE(2) PG_MERGE(3)
 #undef PG_MERGE
         }
@@ -1552,6 +1558,139 @@ __global__ __launch_bounds__(BIG_BLOCK) void bucket_merge32_kernel(const uint64_
     if (full) atomicOr(status, 1u);
     __syncthreads();
     slice_from_planes(tags, cnts, n_slots, tag_mask, (uint64_t)bucket << tag_bits, slice);
+}
+
+// -------------------------------------------------------------------------------- merging finished tables
+//
+// What `jellyfish merge` gives over the tables of feature.py:76-94: one table that holds the sum of several.  Two forms.
+//
+// ALIGNED (table_merge_aligned_kernel): sources and destination are all MINI tables, or all bucketed HASH tables, of one geometry.
+// A k-mer's bucket is a function of the k-mer and the geometry alone (a hash of its minimizer; the top bits of its key), so the
+// merge is per bucket: one workgroup zeroes an LDS table of 2^log2_bucket slots, streams that bucket's slice of every source in
+// turn -- 16 bytes (two slots) per lane and load, ALIGNED_PAIRS loads in flight -- adds every occupied slot with lds_merge from
+// its home slot as the builders derive it, and writes the slice once (16-byte stores).  HBM sees only streams, no global atomic
+// is issued.  The destination's old slice is neither read nor assumed initialised.  A bucket whose union does not fit sets
+// PG_STATUS_TABLE_FULL (its slice then holds part of the union; nothing outside the slice is ever stored).
+// LDS: 8 B per slot -- 128 KiB for 2^14-slot buckets (one workgroup per CU), 64 KiB and less below (two and more).
+constexpr int ALIGNED_MAX_SRCS = 16;
+constexpr int ALIGNED_PAIRS = 4;           // the resolve macro below is written for exactly 2 * 4 slots
+struct MergeSources {
+    const ulonglong2 *p[ALIGNED_MAX_SRCS];
+};
+
+template <bool MINI>
+__global__ __launch_bounds__(BIG_BLOCK) void table_merge_aligned_kernel(MergeSources srcs, int n_srcs, HashView t, uint32_t *status)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long tab[];
+    const uint32_t n_slots = 1u << t.log2_bucket;
+    const uint32_t smask = n_slots - 1;
+    const uint32_t limit = t.limit();
+    const int hsh = KEY_BITS - t.log2_slots;
+    const uint32_t n_pairs = n_slots >> 1;                                       // (buckets have at least 2^4 slots)
+    const uint64_t first_pair = (uint64_t)blockIdx.x << (t.log2_bucket - 1);     // the bucket's slice, in 16-byte pairs of slots
+    ulonglong2 *tab2 = reinterpret_cast<ulonglong2 *>(tab);
+    for (uint32_t i = threadIdx.x; i < n_pairs; i += BIG_BLOCK) tab2[i] = make_ulonglong2(0ull, 0ull);
+    __syncthreads();
+    bool full = false;
+    for (int p = 0; p < n_srcs; ++p) {
+        const ulonglong2 *__restrict__ src = srcs.p[p] + first_pair;
+        for (uint32_t base = 0; base < n_pairs; base += BIG_BLOCK * ALIGNED_PAIRS) {
+            uint64_t e[2 * ALIGNED_PAIRS];
+#pragma unroll
+            for (int j = 0; j < ALIGNED_PAIRS; ++j) {
+                const uint32_t i = base + (uint32_t)j * BIG_BLOCK + threadIdx.x;
+                const ulonglong2 v = i < n_pairs ? src[i] : make_ulonglong2(0ull, 0ull);
+                e[2 * j] = v.x;
+                e[2 * j + 1] = v.y;
+            }
+            uint32_t ss[2 * ALIGNED_PAIRS];
+            unsigned long long first[2 * ALIGNED_PAIRS];
+#pragma unroll
+            for (int j = 0; j < 2 * ALIGNED_PAIRS; ++j) {
+                const uint64_t code = e[j] >> HASH_CBITS;                        // (hash: the key; mini: the code itself)
+                ss[j] = (MINI ? mini_slot_hash<true>(code) : (uint32_t)(code >> hsh)) & smask;
+                first[j] = e[j] ? tab[ss[j]] : 0ull;
+            }
+#define PG_MERGE(J) full |= !lds_merge_entry(tab, smask, limit, e[J], ss[J], first[J]);
+            PG_MERGE(0) PG_MERGE(1) PG_MERGE(2) PG_MERGE(3) PG_MERGE(4) PG_MERGE(5) PG_MERGE(6) PG_MERGE(7)
+#undef PG_MERGE
+        }
+    }
+    if (full) atomicOr(status, PG_STATUS_TABLE_FULL);
+    __syncthreads();
+    ulonglong2 *out = reinterpret_cast<ulonglong2 *>(t.slots) + first_pair;
+    for (uint32_t i = threadIdx.x; i < n_pairs; i += BIG_BLOCK) out[i] = tab2[i];
+}
+
+// GENERAL (table_merge_kernel): any source kind into any destination kind, whatever the geometries.  The source's storage is
+// streamed with the dump kernels' 16-byte loads (dump_load: four dense counters, four packed slots, or four keys with their four
+// counts), MERGE_QUADS of them in flight per lane; an entry's code is the index (dense), key42_inverse of the key (hash), the
+// slot's high bits (mini), key - 1 (planes).  It is ADDED to what the destination holds: atomicAdd (dense), the saturating
+// compare-and-swap of kmer_merge_kernel placed by key42 + home_key / home_mini (hash / mini; the first probes of a lane's batch
+// are issued before any is resolved, as table_query_kernel does), wide_add (wide / miniw: 32-bit sums).  A packed source's
+// saturated count travels as the value it stores; a count that enters a packed table is clamped to HASH_COUNT_SAT first.
+constexpr int MERGE_QUADS = 2;
+
+// `add` more of `key` into a packed table, the sum stopping at HASH_COUNT_SAT exactly; s / cur = home slot and what a plain load
+// found there (stale at worst: the compare-and-swap then returns the slot's real content)
+__device__ __forceinline__ void hash_merge_from(const HashView &t, uint64_t s, uint64_t cur, uint64_t key, uint32_t add, uint32_t *status)
+{
+    const uint32_t limit = t.limit();
+    for (uint32_t tries = 0; tries < limit; ++tries) {
+        for (;;) {
+            if (cur != 0 && (cur >> HASH_CBITS) != key) break;                   // occupied by another key
+            const uint32_t have = (uint32_t)(cur & HASH_CMASK);
+            const uint32_t sum = have + add > HASH_SAT ? HASH_SAT : have + add;
+            const uint64_t old = atomicCAS((unsigned long long *)&t.slots[s], (unsigned long long)cur, (unsigned long long)((key << HASH_CBITS) | sum));
+            if (old == cur) return;
+            cur = old;
+        }
+        s = t.next(s);
+        cur = __hip_atomic_load(&t.slots[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    atomicOr(status, PG_STATUS_TABLE_FULL);
+}
+
+template <int FORM, int TK>
+__global__ __launch_bounds__(BLOCK) void table_merge_kernel(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t n_quads, int k,
+                                                            uint32_t *dense, HashView t, uint32_t *status)
+{
+    constexpr int N = MERGE_QUADS * DUMP_PER;
+    constexpr bool PACKED = TK == TK_HASH || TK == TK_MINI;
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    for (int64_t q0 = (int64_t)blockIdx.x * BLOCK + threadIdx.x; q0 < n_quads; q0 += stride * MERGE_QUADS) {
+        uint64_t code[N], key[N], hh[N], cur[N];
+        uint32_t add[N];
+#pragma unroll
+        for (int u = 0; u < MERGE_QUADS; ++u) {
+            const int64_t q = q0 + u * stride;
+            uint64_t raw[DUMP_PER] = {0, 0, 0, 0};
+            uint32_t cnt[DUMP_PER] = {0, 0, 0, 0};
+            bool present[DUMP_PER] = {false, false, false, false};
+            if (q < n_quads) dump_load<FORM>(slots, counts, q, raw, cnt, present);
+#pragma unroll
+            for (int j = 0; j < DUMP_PER; ++j) {
+                const int i = u * DUMP_PER + j;
+                add[i] = present[j] ? cnt[j] : 0u;
+                if (PACKED && add[i] > HASH_SAT) add[i] = HASH_SAT;
+                code[i] = FORM == DUMP_HASH ? key42_inverse(raw[j]) : raw[j];
+                key[i] = TK != TK_HASH ? code[i] : FORM == DUMP_HASH ? raw[j] : key42(code[i]);
+                hh[i] = cur[i] = 0;
+                if (PACKED && add[i]) {
+                    hh[i] = TK == TK_HASH ? t.home_key(key[i]) : t.home_mini(code[i], k);
+                    cur[i] = t.slots[hh[i]];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (add[i] == 0) continue;
+            if (TK == TK_DENSE) { if ((code[i] >> (2 * k)) == 0) atomicAdd(&dense[(uint32_t)code[i]], add[i]); }   // (never indexed beyond 4^k)
+            else if (TK == TK_WIDE) wide_add(t, code[i], add[i], status);
+            else if (TK == TK_MINIW) wide_add(t, code[i], add[i], status, k);
+            else hash_merge_from(t, hh[i], cur[i], key[i], add[i], status);
+        }
+    }
 }
 
 // occupied slots of every bucket: the segment lengths of a bucket-ordered compaction (one workgroup per bucket)
@@ -2785,6 +2924,111 @@ extern "C" int pg_table_dump_text(const pg_table *t, int64_t lower, int64_t unit
     PG_DUMP_BY_FORM(v.form, PG_LAUNCH);
 #undef PG_LAUNCH
     return check_launch("pg_table_dump_text");
+}
+
+// ---- merging finished tables: what `jellyfish merge` gives over the tables of feature.py:76-94
+
+// bytes of a table's storage
+static int64_t table_bytes(const pg_table *t)
+{
+    if (t->kind == PG_TABLE_DENSE) return (int64_t)4 << (2 * t->k);
+    return (int64_t)(t->kind == PG_TABLE_HASH || t->kind == PG_TABLE_MINI ? 8 : 12) << t->log2_slots;
+}
+
+static bool tables_overlap(const pg_table *a, const pg_table *b)
+{
+    const uintptr_t a0 = (uintptr_t)a->data, b0 = (uintptr_t)b->data;
+    return a0 < b0 + (uint64_t)table_bytes(b) && b0 < a0 + (uint64_t)table_bytes(a);
+}
+
+// a geometry the aligned form takes: MINI, or HASH in LDS-sized buckets (at most 2^30 of them: one launch)
+static bool aligned_kind(const pg_table *t)
+{
+    if (!t) return false;
+    if (t->kind == PG_TABLE_MINI)
+        return t->k >= PG_MINI_MIN_K && t->k <= PG_HASH_MAX_K && t->log2_bucket_slots >= 4 && t->log2_bucket_slots <= PG_BUCKET_MAX_LOG2_SLOTS &&
+               t->log2_slots >= t->log2_bucket_slots && t->log2_slots - t->log2_bucket_slots <= PG_MINI_MAX_LOG2_BUCKETS;
+    if (t->kind == PG_TABLE_HASH)
+        return t->k >= 1 && t->k <= PG_HASH_MAX_K && t->log2_slots >= 10 && t->log2_slots <= 40 && t->log2_bucket_slots >= 4 &&
+               t->log2_bucket_slots <= PG_BUCKET_MAX_LOG2_SLOTS && t->log2_bucket_slots <= t->log2_slots && t->log2_slots - t->log2_bucket_slots <= 30;
+    return false;
+}
+
+extern "C" int pg_table_merge_aligned_applies(const pg_table *a, const pg_table *b)
+{
+    return aligned_kind(a) && aligned_kind(b) && a->kind == b->kind && a->k == b->k && a->log2_slots == b->log2_slots &&
+                   a->log2_bucket_slots == b->log2_bucket_slots
+               ? 1 : 0;
+}
+
+extern "C" int pg_table_merge_aligned(const pg_table *dst, const pg_table *const *srcs, int n_srcs, uint32_t *status, void *stream)
+{
+    if (!dst) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: dst is null");
+    if (!srcs) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: srcs is null");
+    if (!status) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: status is null");
+    if (n_srcs < 1 || n_srcs > ALIGNED_MAX_SRCS) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: n_srcs %d outside [1, %d]", n_srcs, ALIGNED_MAX_SRCS);
+    int rc = check_table(dst);
+    if (rc) return rc;
+    if ((uintptr_t)dst->data & 15) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: dst->data is not 16-byte aligned");
+    MergeSources ms;
+    for (int i = 0; i < ALIGNED_MAX_SRCS; ++i) ms.p[i] = nullptr;
+    for (int i = 0; i < n_srcs; ++i) {
+        if (!srcs[i]) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: srcs[%d] is null", i);
+        if ((rc = check_table(srcs[i]))) return rc;
+        if (srcs[i]->k != dst->k) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: k differs (dst %d, srcs[%d] %d)", dst->k, i, srcs[i]->k);
+        if (!pg_table_merge_aligned_applies(dst, srcs[i]))
+            return pg_fail(PG_EINVAL, "pg_table_merge_aligned: dst and srcs[%d] are not mini tables, or bucketed hash tables, of one geometry "
+                                      "(kind %d / %d, 2^%d / 2^%d slots, buckets of 2^%d / 2^%d)", i, dst->kind, srcs[i]->kind, dst->log2_slots,
+                           srcs[i]->log2_slots, dst->log2_bucket_slots, srcs[i]->log2_bucket_slots);
+        if ((uintptr_t)srcs[i]->data & 15) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: srcs[%d]->data is not 16-byte aligned", i);
+        if (tables_overlap(dst, srcs[i])) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: dst aliases srcs[%d]", i);
+        ms.p[i] = (const ulonglong2 *)srcs[i]->data;
+    }
+    if (!aligned_kind(dst)) return pg_fail(PG_EINVAL, "pg_table_merge_aligned: needs mini tables or bucketed hash tables with LDS-sized buckets");
+    const int bits = dst->log2_slots - dst->log2_bucket_slots;
+    const size_t lds = (size_t)8 << dst->log2_bucket_slots;
+    const bool mini = dst->kind == PG_TABLE_MINI;
+    const void *fn = mini ? (const void *)table_merge_aligned_kernel<true> : (const void *)table_merge_aligned_kernel<false>;
+    if ((rc = raise_lds_limit(fn, lds, "pg_table_merge_aligned"))) return rc;
+    if (mini)
+        hipLaunchKernelGGL((table_merge_aligned_kernel<true>), dim3(1u << bits), dim3(BIG_BLOCK), lds, (hipStream_t)stream, ms, n_srcs, view_of(dst), status);
+    else
+        hipLaunchKernelGGL((table_merge_aligned_kernel<false>), dim3(1u << bits), dim3(BIG_BLOCK), lds, (hipStream_t)stream, ms, n_srcs, view_of(dst), status);
+    return check_launch("pg_table_merge_aligned");
+}
+
+extern "C" int pg_table_merge(const pg_table *dst, const pg_table *src, uint32_t *status, void *stream)
+{
+    if (!dst) return pg_fail(PG_EINVAL, "pg_table_merge: dst is null");
+    if (!src) return pg_fail(PG_EINVAL, "pg_table_merge: src is null");
+    int rc = check_table(dst);
+    if (rc) return rc;
+    DumpView v;
+    if ((rc = dump_view(src, "pg_table_merge", &v))) return rc;
+    if (dst->k != src->k) return pg_fail(PG_EINVAL, "pg_table_merge: k differs (dst %d, src %d)", dst->k, src->k);
+    if (!status && dst->kind != PG_TABLE_DENSE) return pg_fail(PG_EINVAL, "pg_table_merge: status is null");
+    if (tables_overlap(dst, src)) return pg_fail(PG_EINVAL, "pg_table_merge: dst aliases src");
+    const int64_t n_quads = v.n_entries / DUMP_PER;                       // (4^k and 2^log2_slots are whole numbers of quads)
+    const int grid = grid_for((n_quads + MERGE_QUADS - 1) / MERGE_QUADS);
+    const HashView t = dst->kind == PG_TABLE_DENSE ? HashView{nullptr, 0, 0} : view_of(dst);
+    uint32_t *dense = dst->kind == PG_TABLE_DENSE ? (uint32_t *)dst->data : nullptr;
+#define PG_LAUNCH_TO(FORM, TK)                                                                                                     \
+    hipLaunchKernelGGL((table_merge_kernel<FORM, TK>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, (const uint4 *)src->data, v.counts, \
+                       n_quads, dst->k, dense, t, status)
+#define PG_LAUNCH(FORM)                                                   \
+    do {                                                                  \
+        switch (dst->kind) {                                              \
+        case PG_TABLE_DENSE: PG_LAUNCH_TO(FORM, TK_DENSE); break;         \
+        case PG_TABLE_HASH: PG_LAUNCH_TO(FORM, TK_HASH); break;           \
+        case PG_TABLE_WIDE: PG_LAUNCH_TO(FORM, TK_WIDE); break;           \
+        case PG_TABLE_MINI: PG_LAUNCH_TO(FORM, TK_MINI); break;           \
+        default: PG_LAUNCH_TO(FORM, TK_MINIW); break;                     \
+        }                                                                 \
+    } while (0)
+    PG_DUMP_BY_FORM(v.form, PG_LAUNCH);
+#undef PG_LAUNCH
+#undef PG_LAUNCH_TO
+    return check_launch("pg_table_merge");
 }
 #undef PG_DUMP_BY_FORM
 

@@ -113,6 +113,7 @@ class KmerTable:
         self._half_pieces = None         # ([_Piece], held tensors) of a count half in pieces
         self._half_world = 1             # ranks the count half's exchange goes to (its buffers count in the pieces decision)
         self._merge_ws = None            # the provisional words of the merged lookups (fixed slots per record)
+        self.merge_form = None           # "aligned" / "general": which kernel built a table that ``merged`` returned
 
     # ------------------------------------------------------------------ construction
 
@@ -1290,6 +1291,108 @@ class KmerTable:
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pg_table_spectrum(self.desc(), high, hist.data_ptr(), _stream_ptr(self.device)))
         return hist.cpu().numpy()
+
+    # ------------------------------------------------------------------ summing finished tables (jellyfish merge)
+
+    @staticmethod
+    def kind_admits(kind: str, k: int) -> bool:
+        """may a table of this kind hold k-mers of this size?"""
+        lo, hi = {"dense": (1, _lib.DENSE_MAX_K), "hash": (1, _lib.HASH_MAX_K), "wide": (1, _lib.WIDE_MAX_K),
+                  "mini": (_lib.MINI_MIN_K, _lib.HASH_MAX_K), "miniw": (_lib.HASH_MAX_K + 1, _lib.WIDE_MAX_K)}.get(kind, (1, 0))
+        return lo <= k <= hi
+
+    def _n_occupied(self) -> int:
+        """entries the table holds (a host wait)"""
+        if self.kind == "dense":
+            return int(torch.count_nonzero(self.data).item())
+        n = 1 << self.log2_slots
+        return int(torch.count_nonzero(self.data[:n]).item())
+
+    def _check_mergeable(self, other: "KmerTable") -> None:
+        """what ``add_table`` and ``merged`` refuse, before anything is launched"""
+        if not isinstance(other, KmerTable):
+            raise TypeError(f"a KmerTable is needed (got {type(other).__name__})")
+        if other.k != self.k:
+            raise ValueError(f"tables of different k cannot be merged ({self.k} and {other.k})")
+        if other.device != self.device:
+            raise ValueError(f"tables on different devices cannot be merged ({self.device} and {other.device})")
+        _require_gpu(other.data, "the table")
+        other._require_counts()
+
+    def add_table(self, other: "KmerTable", check: bool = True) -> "KmerTable":
+        """add every count of ``other`` -- any kind, any geometry, the same k and device -- to this table (``jellyfish merge`` over the
+        tables of src/feature.py:76-94, two tables at a time): pg_table_merge.  Packed kinds (hash, mini) stop at HASH_COUNT_SAT,
+        dense, wide and miniw sum in 32 bits.  ``other`` is only read.  The row records this table kept from its own count no
+        longer describe it and are dropped."""
+        if other is self:
+            raise ValueError("a table cannot be added to itself (merged([t, t]) doubles a table)")
+        self._check_mergeable(other)
+        self._require_counts()
+        if other.data.data_ptr() == self.data.data_ptr():
+            raise ValueError("the two tables share their storage")
+        self._require_readable()
+        other._require_readable()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pg_table_merge(self.desc(), other.desc(), self.status.data_ptr(), _stream_ptr(self.device)))
+        self._empty = False
+        self._records = None
+        self._emitted = None
+        if check:
+            self.check_status()
+        return self
+
+    @classmethod
+    def merged(cls, tables, kind: str | None = None) -> "KmerTable":
+        """a fresh table that holds the sum of ``tables`` (``jellyfish merge`` over the tables of src/feature.py:76-94); the sources
+        are only read, and one may appear more than once.  ``kind``: the result's kind, the first table's by default.  Where all
+        sources are of the wanted kind and of one geometry that the library's aligned form takes (pg_table_merge_aligned_applies:
+        mini, or hash in LDS-sized buckets), the result has that geometry and is built bucket by bucket inside LDS
+        (``merge_form == "aligned"``); where that does not apply, or a bucket of the union overflows, the result is sized for the
+        sum of the sources' entries and every source is added with ``add_table`` (``merge_form == "general"``), in a larger table
+        when that one fills up too."""
+        tables = list(tables)
+        if not tables:
+            raise ValueError("merged() needs at least one table")
+        first = tables[0]
+        if not isinstance(first, KmerTable):
+            raise TypeError(f"a KmerTable is needed (got {type(first).__name__})")
+        _require_gpu(first.data, "the table")
+        first._require_counts()
+        for t in tables[1:]:
+            first._check_mergeable(t)
+        kind = kind or first.kind
+        if not cls.kind_admits(kind, first.k):
+            raise ValueError(f"{kind!r} tables do not admit k = {first.k}")
+        for t in tables:
+            t._require_readable()
+        L = _lib.load()
+        dev = first.device
+        if kind == first.kind and len(tables) <= 16 and all(L.pg_table_merge_aligned_applies(first.desc(), t.desc()) == 1 for t in tables):
+            # (the kernel overwrites every slot: no clearing)
+            out = cls(first.k, kind, torch.empty(1 << first.log2_slots, dtype=torch.int64, device=dev), first.log2_slots, first.log2_bucket)
+            srcs = (C.POINTER(_lib.pg_table) * len(tables))(*[C.pointer(t._desc) for t in tables])
+            with torch.cuda.device(dev):
+                _lib.check(L.pg_table_merge_aligned(out.desc(), srcs, len(tables), out.status.data_ptr(), _stream_ptr(dev)))
+            if not int(out.status[0].item()) & _lib.STATUS_TABLE_FULL:
+                out._empty = False
+                out.merge_form = "aligned"
+                out.check_status()
+                return out
+            del out
+        hint = max(1024, sum(t._n_occupied() for t in tables))
+        while True:
+            out = cls.alloc(first.k, dev, kind, distinct_hint=hint)
+            for t in tables:
+                out.add_table(t, check=False)
+            out.merge_form = "general"
+            try:
+                out.check_status()
+                return out
+            except _lib.PangaeaError as e:
+                if e.code != _lib.PG_ETABLEFULL or out.kind == "dense" or out.log2_slots >= 40:
+                    raise
+            del out
+            hint *= 2                       # (grow and try again, as counting does)
 
 
 def encode_kmers(strings, k: int) -> np.ndarray:
