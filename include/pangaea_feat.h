@@ -621,6 +621,29 @@ int pg_mini_lookup_half_piece(const pg_table *local, const pg_rows *rows, const 
  * 2^(32 - log2_bucket_slots) - 1 rows; fewer than 2^20 rows; row bits + bin bits + 6 <= 28, i.e. at most 2^19 rows at vsize 400;
  * PG_MINI_MERGE=0 in the environment: never), 0 where they do not, < 0 for a bad table: the rule every pieces entry checks */
 int pg_mini_merge_form_applies(const pg_table *t, int64_t n_rows, int vsize);
+/* ---- abundance rows against a FINISHED table, in super-k-mer form.  Replaces count_kmer -g DUMP: the per-occurrence lookups of
+ * cpptools/count_kmer.cpp:55-108 in a table that was loaded, merged or counted from other reads (count_kmer.cpp:139-170); a k-mer
+ * the table does not hold adds nothing (count_kmer.cpp:87).  pg_mini_count answers a bucket's lookups while it counts the bucket,
+ * which only serves the stream the table is counted from; here the bucket workgroup FINDS instead of inserting: the bucket's slice
+ * of `t` is loaded into LDS, every k-mer of the stream's row-tagged records walks its probe chain read-only (home slot, linear,
+ * wrapping inside the bucket, until its key or an empty slot), and the slots found are looked up as the fused kernel looks up the
+ * slots it made.  `t` is never written.
+ *   pg_mini_find_applies  the one statement of where the form applies: 1 for a PG_TABLE_MINI table (PG_MINI_MIN_K <= k <= 21) where
+ *                         pg_mini_merge_form_applies(t, n_rows, vsize) is 1, 1 <= window, 1 <= vsize <= PG_SHUFFLE_MAX_VSIZE and
+ *                         window * vsize <= PG_HASH_COUNT_SAT; 0 otherwise; < 0 for a bad descriptor.
+ *   pg_mini_find          the calls and workspaces of pg_mini_count -- the same pg_mini_plan (of the stream whose rows are wanted, on
+ *                         the table's geometry), plan_ws, rec_ws, shuffle_ws (pg_mini_shuffle_bytes_merged) and merge_ws
+ *                         (pg_mini_merge_words) --, `rows` required.  Leaves the (row, bin) words in shuffle_ws for
+ *                         pg_mini_abundance_from_emitted.  PG_EINVAL, before anything is enqueued, for null rows, a table of
+ *                         another kind, workspaces too small or not 256-byte aligned, and where pg_mini_find_applies is not 1.
+ *                         status[0]: PG_STATUS_PLAN_MISMATCH as for pg_mini_count; PG_STATUS_TABLE_FULL when a k-mer that the table
+ *                         lacks met a bucket of 2^13 (2^14: the 1024-thread form) slots without one free slot -- the words are
+ *                         then incomplete and the rows must come from pg_features. */
+int pg_mini_find_applies(const pg_table *t, int64_t n_rows, int window, int vsize);
+int pg_mini_find(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *t,
+                 const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                 int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
+                 uint32_t *status, void *stream);
 /* byte offset of the second meta plane ("meta B": the bucket-ordered records' meta words that the pieces keep) inside a record
  * workspace of rec_ws_bytes bytes: [bases A | bases B | meta A | meta B] of the largest capacity that fits, a multiple of 256 */
 int64_t pg_mini_records_meta_offset(int64_t rec_ws_bytes, const pg_table *t);

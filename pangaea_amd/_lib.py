@@ -152,6 +152,8 @@ def load() -> C.CDLL:
         "pg_mini_shuffle_bytes_merged": (i64, [i64, i64, i32, tp]),
         "pg_mini_count": (i32, [vp, vp, i64, i64, tp, rp, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, vp]),
         "pg_mini_merge_words": (i64, [i64, i64, i64, tp]),
+        "pg_mini_find_applies": (i32, [tp, i64, i32, i32]),
+        "pg_mini_find": (i32, [vp, vp, i64, i64, tp, rp, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, vp]),
         "pg_mini_count_piece": (i32, [vp, vp, i64, i64, tp, rp, vp, i64, vp, i64, i32, i32, vp, i64, i32, vp, vp]),
         "pg_mini_lookup_begin": (i32, [tp, rp, i64, i32, vp, i64, vp]),
         "pg_mini_lookup_piece": (i32, [tp, rp, vp, i64, i64, vp, i64, i32, i32, vp, i64, vp, vp, vp]),
@@ -213,6 +215,7 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_table_query", "pg_table_spectrum",
            "pg_table_dump_units", "pg_table_dump_sizes", "pg_table_dump_text", "pg_dump_parse_workspace_bytes", "pg_dump_parse",
            "pg_table_merge", "pg_table_merge_aligned", "pg_table_merge_aligned_applies",
+           "pg_mini_find_applies", "pg_mini_find",
            "pg_features", "pg_normalize_rows", "pg_write_csv_gz", "pg_extract_reads"]
 
 

@@ -105,7 +105,11 @@ def main_count_kmer(argv=None) -> int:
     try:
         table = None
         if os.path.isfile(a.global_):
-            table = KmerTable.from_dump(a.global_, a.kmer, torch.device("cuda", torch.cuda.current_device()))
+            # 13 <= k <= 21: a mini table, whose buckets find the k-mers of the reads' super-k-mer records (KmerTable.abundance_of);
+            # elsewhere the default kind and the lookup kernel (dense, hash below 13, wide above 21)
+            from .kmer import mini_find_wanted
+            kind = "mini" if KmerTable.kind_admits("mini", a.kmer) and mini_find_wanted() else None
+            table = KmerTable.from_dump(a.global_, a.kmer, torch.device("cuda", torch.cuda.current_device()), kind=kind)
         names, _, abd = feature.compute_features(r1, r2, a.kmer, 0, a.window, a.vector, a.len, want_tnf=False, table=table)
         feature.write_csv_gz(a.output, names, abd)
     except Exception as e:

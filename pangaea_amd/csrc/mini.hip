@@ -2241,6 +2241,142 @@ __global__ __launch_bounds__(BLK, 4) void mini_lookup_slice_merge_kernel(const u
     merged_lookup<CAP, BLK, DIG>(mc);
 }
 
+// ---- FIND (pg_mini_find): the bucket workgroup that finds instead of inserting -- abundance rows against a FINISHED table
+// (count_kmer -g DUMP, cpptools/count_kmer.cpp:55-108; a k-mer the table lacks adds nothing, :87).  The records are those of
+// any stream, delivered bucket by bucket by the plan and the two scatter passes as for a count; the table is only read.
+//   1  the bucket's slice of the given table -> LDS (16-byte loads), the bucket's range of the MERGE layout claimed
+//   2  every record that lies in a row is expanded as the count loop does and each k-mer walks its chain read-only: home slot,
+//      linear, wrapping inside the bucket, until its key or an empty slot, at most `limit` steps; the slot where the walk ended
+//      goes to the k-mer's fixed halfword (MergeArgs).  An empty slot's bin reads 0xffff, which is what an absent k-mer needs.
+//   3  slots -> 2-byte bins at the start of the dynamic LDS, merged_lookup as in the fused kernel.
+// A walk that sees `limit` = all slots of the bucket without its key or an empty one (an absent k-mer in a bucket without a free
+// slot) leaves halfword n_slots: the bins area has room for that entry (set to 0xffff) wherever the bucket is smaller than the
+// area.  Where it is not (2^13 slots on 512 threads, 2^14 on 1024) the bucket writes nothing and sets PG_STATUS_TABLE_FULL:
+// the caller takes the lookup form (KmerTable.abundance_of).
+template <int CAP, int BLK, int DIG>
+__global__ __launch_bounds__(BLK, 4) void mini_find_kernel(const uint64_t *__restrict__ bases, const uint32_t *__restrict__ meta,
+                                                              const unsigned long long *__restrict__ off, const unsigned long long *__restrict__ n_short,
+                                                              MiniView t, uint32_t window, uint32_t vsize, int vbits,
+                                                              unsigned long long *__restrict__ word_cursor, ShufArgs sh, MergeArgs mg,
+                                                              unsigned long long rec_cap, uint32_t *status)
+{
+    // (a plan of another stream: see mini_count_kernel)
+    if (word_cursor[-1] > rec_cap || (*status & PG_STATUS_PLAN_MISMATCH)) {
+        if (threadIdx.x == 0 && blockIdx.x == 0) atomicOr(status, PG_STATUS_PLAN_MISMATCH);
+        return;
+    }
+    extern __shared__ __attribute__((aligned(16))) unsigned long long tab[];
+    __shared__ unsigned long long wbase;
+    __shared__ uint32_t no_room;                                 // some absent k-mer saw every slot of the bucket taken
+    const uint32_t n_slots = 1u << t.log2_bucket, smask = n_slots - 1u;
+    const uint32_t limit = n_slots < MAX_PROBE ? n_slots : MAX_PROBE;
+    const int64_t r0 = (int64_t)off[blockIdx.x], r1 = (int64_t)off[blockIdx.x + 1];
+    if (r1 == r0) return;                                        // (uniform: no record of this bucket)
+    const int64_t rs = n_short && CAP > SHORT_MAX ? r0 + (int64_t)n_short[blockIdx.x] : r0;
+    const uint32_t lane = lane_id(), wave = threadIdx.x >> 6;
+    const int rc_sh0 = 2 * (32 - t.k);
+    constexpr uint32_t CXS_ = CAP > SHORT_MAX ? SHORT_MAX : CAP;
+    const uint32_t n_sb = (uint32_t)((rs - r0 + 63) >> 6), n_lb = (uint32_t)((r1 - rs + 63) >> 6);
+    // ---- 1: the slice (two slots per load; a bucket has at least 16), the bucket's range of fixed places (dwords; see MergeArgs)
+    {
+        const ulonglong2 *src = reinterpret_cast<const ulonglong2 *>(t.slots + ((uint64_t)blockIdx.x << t.log2_bucket));
+        ulonglong2 *dst = reinterpret_cast<ulonglong2 *>(tab);
+        for (uint32_t i = threadIdx.x; i < n_slots / 2; i += BLK) dst[i] = src[i];
+    }
+    const unsigned long long fixed_words = 32ull * n_sb * CXS_ + 32ull * n_lb * CAP;
+    if (threadIdx.x == 0) { wbase = atomicAdd(word_cursor, fixed_words); no_room = 0; }
+    __syncthreads();
+    {
+        const unsigned long long need = fixed_words + (unsigned long long)MergeStep<CAP>::SLACK;
+        if (wbase + need > mg.cap || 2ull * need >= (unsigned long long)RING_NOPLACE) {      // (uniform; a plan of other reads, as in mini_count_kernel)
+            if (threadIdx.x == 0) atomicOr(status, PG_STATUS_PLAN_MISMATCH);
+            return;
+        }
+    }
+    const unsigned long long wb = ((unsigned long long)uniform32((uint32_t)(wbase >> 32)) << 32) | uniform32((uint32_t)wbase);
+    uint32_t *const prov_b = mg.prov + wb;
+    uint16_t *const prov_h = reinterpret_cast<uint16_t *>(prov_b);
+    const uint32_t long_base = n_sb * 64u * CXS_;                // (halfwords)
+    const uint32_t np_half = long_base + n_lb * 64u * CAP;
+    // ---- 2: wavefront w takes the batches [ra + 64 (w + BLK / 64 t), + 64) of a class; CX = k-mers per record at most there
+    bool lost = false;
+    auto find_range = [&](auto cx, int64_t ra, int64_t rb) {
+        constexpr int CX = decltype(cx)::value;
+        for (int64_t i0 = ra + (int64_t)wave * 64; i0 < rb; i0 += BLK) {
+            const bool live = i0 + lane < rb;
+            const uint64_t R = live ? bases[i0 + lane] : 0ull;
+            const uint32_t m = live ? meta[i0 + lane] : 0xffffffffu;
+            // (a record outside every row is looked up by nobody: merged_lookup skips its halfwords)
+            const int n = (m >> META_ROW_SHIFT) != MINI_ROW_NONE ? (int)((m >> META_D2_BITS) & (MINI_MAX_LEN - 1)) + 1 : 0;
+            if (!__any(n > 0)) continue;                         // (uniform)
+            const uint32_t place0 = (CX < CAP ? 0u : long_base) + (uint32_t)((i0 - ra) >> 6) * (64u * CX) + lane;
+            const uint64_t FW = rev2_64(R), RC = R ^ 0xAAAAAAAAAAAAAAAAull;
+            uint64_t code[CX];
+            uint32_t sl[CX];
+            unsigned long long cur[CX];
+#pragma unroll
+            for (int j = 0; j < CX; ++j) {                       // the home slots of the record's k-mers, all reads in flight
+                const uint64_t fw = FW << ((rc_sh0 - 2 * j) & 63), rc = RC << (2 * j);        // (as the count loop: j beyond n selects some slot, read and ignored)
+                code[j] = (fw < rc ? fw : rc) >> rc_sh0;
+                sl[j] = mini_slot_hash<false>(code[j]) & smask;
+                cur[j] = tab[sl[j]];
+            }
+#pragma unroll
+            for (int j = 0; j < CX; ++j) {
+                uint32_t s = sl[j], res = n_slots;
+                bool todo = j < n;
+                // one slot of the chain: the walk ends at the k-mer's own slot or at an empty one
+                auto visit = [&](unsigned long long c) { if (todo && (c == 0ull || (c >> HASH_CBITS) == code[j])) { res = s; todo = false; } };
+                visit(cur[j]);
+                // (a lane walks its own chain; the round ends with the longest one, after `limit` slots at the latest)
+                for (uint32_t q = 1; q < limit && __any(todo); ++q) {
+                    s = (s + 1u) & smask;
+                    visit(tab[s]);
+                }
+                lost |= todo;
+                if (j < n) gstore(prov_h, (uint64_t)place0 + 64u * j, (uint64_t)np_half, (uint16_t)res, status);
+            }
+        }
+    };
+    find_range(std::integral_constant<int, (CAP > SHORT_MAX ? SHORT_MAX : CAP)>{}, r0, rs);
+    find_range(std::integral_constant<int, CAP>{}, rs, r1);
+    if (lost) atomicOr(&no_room, 1u);
+    __syncthreads();                                             // (the last probe of the bucket is done: the slots may go)
+    const bool spare = 2u * (n_slots + 1u) <= MergeLds<BLK, DIG>::BUF;           // (the bins area holds one entry more than the bucket has slots)
+    if (no_room && !spare) {                                     // (uniform)
+        if (threadIdx.x == 0) atomicOr(status, PG_STATUS_TABLE_FULL);
+        return;
+    }
+    // ---- 3: the 2-byte bins (every lane reads all its slots first: the bins land on top of the first quarter of the slots)
+    uint16_t mybin[16];
+    const float rcp_window = 1.0f / (float)window;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const uint32_t i = q * BLK + threadIdx.x;
+        mybin[q] = 0xffffu;
+        if (i < n_slots) {
+            const unsigned long long v = tab[i];
+            const uint32_t bin = div_uniform((uint32_t)(v & HASH_CMASK), window, rcp_window);
+            mybin[q] = (uint16_t)(v && bin < vsize ? bin : 0xffffu);        // (merged_lookup reads the bin itself, 0xffff = none)
+        }
+    }
+    __syncthreads();
+    uint16_t *bins16 = reinterpret_cast<uint16_t *>(tab);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const uint32_t i = q * BLK + threadIdx.x;
+        if (i < n_slots) bins16[i] = mybin[q];
+    }
+    if (spare && threadIdx.x == 0) bins16[n_slots] = 0xffffu;    // (what a walk without an end left)
+    __syncthreads();
+    MergeCtx mc;
+    mc.lds = reinterpret_cast<unsigned char *>(tab); mc.smask = smask; mc.vbits = vbits; mc.sh = sh; mc.status = status;
+    mc.prov_b = prov_b;
+    mc.meta_s = meta + r0; mc.meta_l = meta + rs; mc.n_s = (uint32_t)(rs - r0); mc.n_l = (uint32_t)(r1 - rs);
+    mc.dbg = nullptr;
+    merged_lookup<CAP, BLK, DIG>(mc);
+}
+
 // ---- workspace of the plan: header | region_tot | region_off | off | hist | cur2 | cur2l | kwords | wbeg | round_row | chunk table
 struct MiniPlan {
     int bits, bits1, bits2;
@@ -2758,6 +2894,7 @@ struct CountArgs {
     const uint64_t *codes; const uint32_t *valid, *tabv; int64_t word_begin, word_end; const pg_table *t; const pg_rows *rows;
     void *plan_ws; int64_t plan_ws_bytes; void *rec_ws; int64_t rec_ws_bytes; int window, vsize;
     void *shuffle_ws; int64_t shuffle_ws_bytes; void *merge_ws; int64_t merge_ws_words; const HalfArgs *half; uint32_t *status; void *stream;
+    bool find = false;                                          // pg_mini_find: the table is finished and only read (mini_find_kernel)
 };
 
 static int mini_count_impl(const CountArgs &a)
@@ -2765,34 +2902,35 @@ static int mini_count_impl(const CountArgs &a)
     const pg_table *t = a.t; const pg_rows *rows = a.rows;
     const int window = a.window, vsize = a.vsize;
     const int64_t n_words = a.word_end - a.word_begin;
+    const char *who = a.find ? "pg_mini_find" : "pg_mini_count";
     // ---- every refusal comes before anything is enqueued
-    if (!a.codes || !a.valid || !a.plan_ws || !a.rec_ws || !a.status) return pg_fail(PG_EINVAL, "pg_mini_count: null argument");
-    if (a.word_begin < 0 || a.word_end < a.word_begin) return pg_fail(PG_EINVAL, "pg_mini_count: bad word range");
-    int rc = check_mini(t, "pg_mini_count");
+    if (!a.codes || !a.valid || !a.plan_ws || !a.rec_ws || !a.status) return pg_fail(PG_EINVAL, "%s: null argument", who);
+    if (a.word_begin < 0 || a.word_end < a.word_begin) return pg_fail(PG_EINVAL, "%s: bad word range", who);
+    int rc = check_mini(t, who);
     if (rc) return rc;
-    if ((rc = check_mini_rows(rows, "pg_mini_count"))) return rc;
+    if ((rc = check_mini_rows(rows, who))) return rc;
     const bool with_rows = rows && rows->n_rows > 0, some_words = n_words > 0;
-    if (window < 0 || vsize < 0 || (window > 0) != (vsize > 0)) return pg_fail(PG_EINVAL, "pg_mini_count: window %d / vector size %d", window, vsize);
+    if (window < 0 || vsize < 0 || (window > 0) != (vsize > 0)) return pg_fail(PG_EINVAL, "%s: window %d / vector size %d", who, window, vsize);
     const bool half = a.half != nullptr, piece = half && a.half->accum;
     if (window > 0) {
-        if (!with_rows) return pg_fail(PG_EINVAL, "pg_mini_count: the lookup pass needs rows");
-        if (!a.shuffle_ws && !piece) return pg_fail(PG_EINVAL, "pg_mini_count: null shuffle workspace");
+        if (!with_rows) return pg_fail(PG_EINVAL, "%s: the lookup pass needs rows", who);
+        if (!a.shuffle_ws && !piece) return pg_fail(PG_EINVAL, "%s: null shuffle workspace", who);
         if (vsize > PG_SHUFFLE_MAX_VSIZE || (t->kind == PG_TABLE_MINI && (int64_t)window * vsize > (int64_t)PG_HASH_COUNT_SAT))
-            return pg_fail(PG_EINVAL, "pg_mini_count: window %d x vector size %d outside the exact range of the table", window, vsize);
+            return pg_fail(PG_EINVAL, "%s: window %d x vector size %d outside the exact range of the table", who, window, vsize);
     }
     PlanView p;
     RecView rec;
-    if ((rc = plan_view(t, n_words, a.plan_ws, a.plan_ws_bytes, "pg_mini_count", true, &p))) return rc;
-    if ((rc = rec_view(a.rec_ws, a.rec_ws_bytes, "pg_mini_count", &rec))) return rc;
+    if ((rc = plan_view(t, n_words, a.plan_ws, a.plan_ws_bytes, who, true, &p))) return rc;
+    if ((rc = rec_view(a.rec_ws, a.rec_ws_bytes, who, &rec))) return rc;
     const bool slots_form = window > 0 && mini_slots_form(t, rows);
     const bool merge = window > 0 && a.merge_ws && a.merge_ws_words > 0 && mini_merge_form(t, rows, vsize);
     pg_shuffle_layout sl{0, 0, 0, 0, 0};
     if (window > 0 && !piece) {
         if ((rc = pg_internal_shuffle_layout(n_words * 32, rows->n_rows, vsize, &sl, slots_form ? MINI_ONE_PASS_BITS : PG_SHUFFLE_ONE_PASS_BITS, merge ? 1 : 0))) return rc;
         if ((int64_t)sl.total > a.shuffle_ws_bytes || misaligned(a.shuffle_ws))
-            return pg_fail(PG_EINVAL, "pg_mini_count: shuffle workspace of %lld bytes (256-byte aligned), %lld needed", (long long)a.shuffle_ws_bytes, (long long)sl.total);
+            return pg_fail(PG_EINVAL, "%s: shuffle workspace of %lld bytes (256-byte aligned), %lld needed", who, (long long)a.shuffle_ws_bytes, (long long)sl.total);
     }
-    if (a.merge_ws && misaligned(a.merge_ws)) return pg_fail(PG_EINVAL, "pg_mini_count: workspaces must be 256-byte aligned");
+    if (a.merge_ws && misaligned(a.merge_ws)) return pg_fail(PG_EINVAL, "%s: workspaces must be 256-byte aligned", who);
     if (half && (t->kind == PG_TABLE_MINI_WIDE || !slots_form))
         return pg_fail(PG_EINVAL, "pg_mini_count_half: needs packed slots (k <= %d), rows and fewer than 2^(32 - log2 bucket slots) of them", PG_HASH_MAX_K);
     if (half && !p.bits2) return pg_fail(PG_EINVAL, "pg_mini_count_half: needs more than 256 buckets");
@@ -2803,7 +2941,7 @@ static int mini_count_impl(const CountArgs &a)
     const int nb = 1 << p.bits, cap_k = mini_cap(t->k);
     // ---- clear: hist | cur2 | cur2l | kwords (they lie in a row), and the word cursor
     if (hipMemsetAsync(p.hist, 0, (size_t)((char *)p.wbeg - (char *)p.hist), s) != hipSuccess || hipMemsetAsync(p.header + 1, 0, 8, s) != hipSuccess)
-        return pg_fail(PG_EHIP, "pg_mini_count: memset failed");
+        return pg_fail(PG_EHIP, "%s: memset failed", who);
     // ---- first pass: the stream -> records, sorted by region
     if (some_words) {
         rc = with_flag(a.tabv != nullptr, [&](auto masked) {
@@ -2811,7 +2949,7 @@ static int mini_count_impl(const CountArgs &a)
                 using Win = decltype(w);
                 constexpr bool MASKED = decltype(masked)::value;
                 const size_t lds1 = MASKED ? sizeof(Scatter1LdsMasked<256>) : sizeof(Scatter1Lds<256>);
-                return launch(mini_scatter_kernel<Win::W, Win::DELAY, Win::M, 256, MASKED>, dim3((unsigned)p.n_chunks), dim3(S1_BLOCK), lds1, s, "pg_mini_count",
+                return launch(mini_scatter_kernel<Win::W, Win::DELAY, Win::M, 256, MASKED>, dim3((unsigned)p.n_chunks), dim3(S1_BLOCK), lds1, s, who,
                               a.codes, a.valid, a.word_begin, a.word_end, t->k, woff, p.bits, p.bits2, cap_k,
                               with_rows ? rows->row_start : nullptr, with_rows ? rows->row_end : nullptr, with_rows ? rows->n_rows : (int64_t)0,
                               with_rows ? rows->strict_valid : nullptr, p.round_row, rec.bases_a, rec.meta_a, p.chunk_tab, p.n_chunks, p.chunk_stride,
@@ -2822,8 +2960,8 @@ static int mini_count_impl(const CountArgs &a)
     }
     // (for pg_mini_wait_first_pass: what is enqueued on another stream behind this event runs beside the second pass and the count)
     if (!first_pass_event && hipEventCreateWithFlags(&first_pass_event, hipEventDisableTiming) != hipSuccess)
-        return pg_fail(PG_EHIP, "pg_mini_count: event creation failed");
-    if (hipEventRecord(first_pass_event, s) != hipSuccess) return pg_fail(PG_EHIP, "pg_mini_count: event record failed");
+        return pg_fail(PG_EHIP, "%s: event creation failed", who);
+    if (hipEventRecord(first_pass_event, s) != hipSuccess) return pg_fail(PG_EHIP, "%s: event record failed", who);
     // ---- bucket offsets: records per bucket from the regions' meta plane -> where every bucket starts (an empty range: all zero)
     if (p.bits2) {
         const int tiles_h = 32;
@@ -2847,7 +2985,7 @@ static int mini_count_impl(const CountArgs &a)
             constexpr int DIG = decltype(dig)::value, BLK = decltype(blk)::value, RPL = decltype(rpl)::value;
             // (the merged lookups size their buffer from record counts: the second pass need not tally the k-mers in rows per bucket)
             return launch(mini_scatter2_kernel<DIG, BLK, RPL, decltype(prefetch)::value>, dim3((unsigned)(tiles_x << p.bits1)), dim3(BLK),
-                          sizeof(Scatter2Lds<DIG, BLK, RPL>), s, "pg_mini_count", rec.bases_a, rec.meta_a, off, p.bits2, tiles_x,
+                          sizeof(Scatter2Lds<DIG, BLK, RPL>), s, who, rec.bases_a, rec.meta_a, off, p.bits2, tiles_x,
                           cap_k > SHORT_MAX ? SHORT_MAX : 0, rec.bases_b, rec.meta_b, p.cur2, p.cur2l, merge ? nullptr : p.kwords, p.header,
                           (unsigned long long)rec.cap, a.status);
         };
@@ -2867,12 +3005,26 @@ static int mini_count_impl(const CountArgs &a)
         if ((rc = pg_internal_shuffle_prepare(n_words * 32, rows, vsize, a.shuffle_ws, a.shuffle_ws_bytes, a.stream, &ctx, MINI_ONE_PASS_BITS, merge ? 1 : 0))) return rc;
         sh = ShufArgs{ctx.goff, ctx.gcur1, ctx.words_out, ctx.gb1, ctx.gb2, ctx.dshift, merge ? 0 : ctx.narrow, ctx.words_cap};
         words_a = ctx.words_in;                          // the provisional words wait in the shuffle's input buffer
-        if (sh.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "pg_mini_count: %d first-pass digits of the row shuffle", sh.gb1);
+        if (sh.gb1 > MINI_ONE_PASS_BITS) return pg_fail(PG_EINVAL, "%s: %d first-pass digits of the row shuffle", who, sh.gb1);
     }
     const CountForm form = count_form(t, rows, slots_form, merge, half, a.tabv != nullptr, sh.gb1);
     const MergeArgs mg{(uint32_t *)a.merge_ws, (unsigned long long)(a.merge_ws ? a.merge_ws_words : 0)};
     HalfArgs hv = half ? *a.half : HalfArgs{nullptr, nullptr, nullptr, nullptr, 0, nullptr};
     hv.meta_w = a.tabv ? (p.bits2 ? rec.meta_b : rec.meta_a) : nullptr;    // (the plane the count kernel reads: the lookup half reads it again)
+    if (a.find) {
+        // the find form: the count's geometry (512 threads, two workgroups per CU, on buckets of at most 2^13 slots), the slots and
+        // then the lookup stage in the same LDS
+        rc = with_cap(cap_k, [&](auto cap_c) {
+            return with_lookup_geom(form.blk, form.dig, [&](auto geom) {
+                using G = decltype(geom);
+                const size_t lds = std::max((size_t)8 << t->log2_bucket_slots, (size_t)MergeLds<G::BLK, G::DIG>::END);
+                return launch(mini_find_kernel<decltype(cap_c)::value, G::BLK, G::DIG>, dim3(nb), dim3(G::BLK), lds, s, who,
+                              p.bits2 ? rec.bases_b : rec.bases_a, p.bits2 ? rec.meta_b : rec.meta_a, off, p.n_short(t->k), mini_view(t), window, vsize,
+                              sl.vbits, p.header + 1, sh, mg, (unsigned long long)rec.cap, a.status);
+            });
+        });
+        return rc ? rc : check_launch(who);
+    }
     rc = with_cap(cap_k, [&](auto cap_c) {
         return with_count_kernel<decltype(cap_c)::value>(form, [&](auto kernel) {
             return launch(kernel, dim3(nb), dim3(form.blk), form.lds, s, "pg_mini_count", p.bits2 ? rec.bases_b : rec.bases_a, p.bits2 ? rec.meta_b : rec.meta_a,
@@ -2890,6 +3042,37 @@ extern "C" int pg_mini_count(const uint64_t *codes, const uint32_t *valid, int64
 {
     return mini_count_impl(CountArgs{codes, valid, nullptr, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
                                      shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, nullptr, status, stream});
+}
+
+// ---- abundance rows against a finished table (mini_find_kernel).  The one statement of where that form applies:
+extern "C" int pg_mini_find_applies(const pg_table *t, int64_t n_rows, int window, int vsize)
+{
+    int rc = check_mini(t, "pg_mini_find_applies");
+    if (rc) return rc;
+    if (n_rows < 0) return pg_fail(PG_EINVAL, "pg_mini_find_applies: negative row count");
+    if (t->kind != PG_TABLE_MINI) return 0;                       // (packed slots: 13 <= k <= 21)
+    if (window < 1 || vsize < 1 || vsize > PG_SHUFFLE_MAX_VSIZE || (int64_t)window * vsize > (int64_t)PG_HASH_COUNT_SAT) return 0;
+    const pg_rows r{nullptr, nullptr, n_rows, nullptr};
+    return mini_merge_form(t, &r, vsize) ? 1 : 0;
+}
+
+extern "C" int pg_mini_find(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, const pg_table *t,
+                            const pg_rows *rows, void *plan_ws, int64_t plan_ws_bytes, void *rec_ws, int64_t rec_ws_bytes,
+                            int window, int vsize, void *shuffle_ws, int64_t shuffle_ws_bytes, void *merge_ws, int64_t merge_ws_words,
+                            uint32_t *status, void *stream)
+{
+    int rc = check_mini(t, "pg_mini_find");
+    if (rc) return rc;
+    if (t->kind != PG_TABLE_MINI) return pg_fail(PG_EINVAL, "pg_mini_find: packed mini tables (%d <= k <= %d)", PG_MINI_MIN_K, PG_HASH_MAX_K);
+    if (!rows || rows->n_rows < 1) return pg_fail(PG_EINVAL, "pg_mini_find: needs rows");
+    if (!shuffle_ws || !merge_ws || merge_ws_words <= 0) return pg_fail(PG_EINVAL, "pg_mini_find: needs the shuffle workspace and the slot buffer");
+    if ((rc = check_mini_rows(rows, "pg_mini_find"))) return rc;
+    if (pg_mini_find_applies(t, rows->n_rows, window, vsize) != 1)
+        return pg_fail(PG_EINVAL, "pg_mini_find: does not apply to %lld rows, window %d, vector size %d (pg_mini_find_applies)", (long long)rows->n_rows, window, vsize);
+    CountArgs a{codes, valid, nullptr, word_begin, word_end, t, rows, plan_ws, plan_ws_bytes, rec_ws, rec_ws_bytes, window, vsize,
+                shuffle_ws, shuffle_ws_bytes, merge_ws, merge_ws_words, nullptr, status, stream};
+    a.find = true;
+    return mini_count_impl(a);
 }
 
 // ---- a stream counted in pieces (one GPU; see HalfArgs / mini_lookup_slice_merge_kernel)

@@ -160,6 +160,12 @@ def compute_features(reads1: str, reads2: str | None, k: int, k_tnf: int, window
     rows = stream.rows(min_len)
     plan = Plan(rows, device)
     tnf = abd = None
+    if (want_abd and table is not None and world == 1 and table.kind == "hash" and _kmer.KmerTable.kind_admits("mini", table.k)
+            and _kmer.mini_find_wanted()):
+        # a finished hash table: one streaming pass makes it a mini table, whose buckets find the k-mers of the stream's
+        # super-k-mer records (KmerTable.abundance_of) instead of one random table line per k-mer occurrence
+        logging.info(f"converting the given hash table (k = {table.k}, 2^{table.log2_slots} slots) to a mini table for the abundance rows")
+        table = _kmer.KmerTable.merged([table], kind="mini")
     if want_abd and table is None and world > 1 and _sharded_mini_applies(stream, plan, k, window, vsize, lowercase_is_base):
         # several ranks: the super-k-mer pipeline on every rank's own reads, entries to bucket owners, bins back
         tnf, abd, _ = pdist.features_sharded_mini(stream, plan, k, k_tnf if want_tnf else None, window, vsize, lowercase_is_base=lowercase_is_base)

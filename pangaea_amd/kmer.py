@@ -35,6 +35,12 @@ def _merged_lookups() -> bool:
     return os.environ.get("PG_MINI_MERGE", "1") not in ("", "0")
 
 
+def mini_find_wanted() -> bool:
+    """abundance rows against a finished mini table in super-k-mer form (``KmerTable.abundance_of``); PG_MINI_FIND=0, read at call
+    time: the lookup form everywhere, as before that form existed"""
+    return os.environ.get("PG_MINI_FIND", "1") not in ("", "0")
+
+
 def _slack(n: int) -> int:
     """3 % of slack on a plan's counts: the next batch of the same size then finds room without asking"""
     return n + n // 32 + 4096
@@ -114,6 +120,7 @@ class KmerTable:
         self._half_world = 1             # ranks the count half's exchange goes to (its buffers count in the pieces decision)
         self._merge_ws = None            # the provisional words of the merged lookups (fixed slots per record)
         self.merge_form = None           # "aligned" / "general": which kernel built a table that ``merged`` returned
+        self.rows_form = None            # "find" / "lookup": how the last ``abundance_of`` built its rows
 
     # ------------------------------------------------------------------ construction
 
@@ -976,6 +983,84 @@ class KmerTable:
         self._emitted = None            # the row shuffle reuses the emitted words' buffer: they are gone now
         return out
 
+    def abundance_of(self, stream: ReadStream, rows: "Plan | Rows", window: int = 10, vsize: int = 400,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+        """abundance rows (int32, n_rows x vsize) of ``rows`` of ``stream`` against this FINISHED table -- loaded, merged, or counted
+        from whatever reads: ``count_kmer -g DUMP`` (count_kmer.cpp:55-108; a k-mer the table lacks adds nothing, :87).  The table
+        is only read.
+
+        A mini table (13 <= k <= 21) takes the super-k-mer form where the library says it applies (pg_mini_find_applies): the
+        stream's row-tagged records go bucket by bucket to workgroups that find their k-mers in the table's slices inside LDS
+        (pg_mini_find), then the row shuffle writes the rows; ``rows_form`` is "find".  The rows follow the reference's own rule
+        (the strict plane ``stream.valid``) whatever the table was counted with.  Everything else -- other kinds, rows the
+        merged lookups do not take, a stream whose scratch would not fit in one piece, PG_MINI_FIND=0 -- goes through the lookup
+        kernel (pg_features), as ``features`` always did; ``rows_form`` is "lookup".  The records this table kept from its own
+        count are dropped."""
+        self._require_counts()
+        _require_gpu(stream.codes, "the read stream")
+        if stream.device != self.device:
+            raise ValueError("stream and table are on different devices")
+        plan = rows if isinstance(rows, Plan) else Plan(rows, self.device)
+        window, vsize = int(window), int(vsize)
+        shape = (plan.n_rows, vsize)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.int32 or out.device != self.device):
+            raise ValueError(f"out must be an int32 tensor of shape {shape} on {self.device}")
+        self._records = None
+        self._emitted = None
+        L = _lib.load()
+        n_words = stream.n_words
+        find = (self.kind == "mini" and mini_find_wanted() and plan.shuffle_ok and plan.n_segs > 0 and n_words > 0
+                and plan.n_rows <= _lib.MINI_MAX_ROWS and _lib.check(L.pg_mini_find_applies(self.desc(), plan.n_rows, window, vsize)) == 1
+                and self._piece_words(n_words, True) is None)
+        if find:
+            self._require_readable()
+            abd = out if out is not None else torch.empty(shape, dtype=torch.int32, device=self.device)      # (every row is overwritten)
+            if self._find(stream, plan, window, vsize, abd):
+                self.rows_form = "find"
+                return abd
+            out = abd                                            # (a bucket without a free slot: the lookup form below)
+        abd = out.zero_() if out is not None else torch.zeros(shape, dtype=torch.int32, device=self.device)
+        self.rows_form = "lookup"
+        if plan.n_segs:
+            self._require_readable()
+            with torch.cuda.device(self.device):
+                _lib.check(L.pg_features(stream.codes.data_ptr(), stream.valid.data_ptr(), stream.n_words,
+                                         plan.seg_row.data_ptr(), plan.seg_start.data_ptr(), plan.seg_end.data_ptr(), plan.n_segs,
+                                         0, None, None, self.desc(), window, vsize, abd.data_ptr(), _stream_ptr(self.device)))
+        return abd
+
+    def _find(self, stream: ReadStream, plan: "Plan", window: int, vsize: int, abd: torch.Tensor) -> bool:
+        """pg_mini_plan (cached as for a count: the plan depends on the stream, the rows and the geometry only) + pg_mini_find +
+        the row shuffle.  False: a k-mer the table lacks met a bucket without a free slot (PG_STATUS_TABLE_FULL from the find
+        kernel; the table itself is fine) and nothing was written to ``abd``."""
+        L = _lib.load()
+        n_words = stream.n_words
+        rows_ref = self._rows_ref(plan, stream, False)
+        key = self._plan_key(stream.codes, stream.valid, 0, n_words, plan, False, self.log2_slots, self.log2_bucket)
+        sp = _stream_ptr(self.device)
+        with torch.cuda.device(self.device):
+            if self._mini_plan is None or self._mini_plan.key != key:
+                self._compute_plan(key, stream, stream.valid, None, 0, n_words, plan, rows_ref, (stream.codes, stream.valid))
+            n_records, n_long = self.plan_counts()
+            plan_ws = self._mini_plan.ws
+            self._mini_optimistic = None
+            rec_ws = self._grown("_mini_rec_ws", _lib.check(L.pg_mini_records_bytes(_slack(n_records), self.desc())), shrink=True)
+            self._mini_sized_for = (n_words, self.log2_slots, self.log2_bucket)
+            sws = self._grown("_shuffle_ws", _lib.check(L.pg_mini_shuffle_bytes_merged(n_words, plan.n_rows, vsize, self.desc())))
+            mws = self._grown("_merge_ws", _lib.check(L.pg_mini_merge_words(n_words, _slack(n_records), min(_slack(n_long), _slack(n_records)), self.desc())),
+                              dtype=torch.int32)
+            _lib.check(L.pg_mini_find(stream.codes.data_ptr(), stream.valid.data_ptr(), 0, n_words, self.desc(), rows_ref,
+                                      plan_ws.data_ptr(), plan_ws.numel(), rec_ws.data_ptr(), rec_ws.numel(), window, vsize,
+                                      sws.data_ptr(), sws.numel(), mws.data_ptr(), mws.numel(), self.status.data_ptr(), sp))
+            st = int(self.status[0].item())
+            if st == _lib.STATUS_TABLE_FULL:
+                self.status.zero_()
+                return False
+            self.check_status()
+            _lib.check(L.pg_mini_abundance_from_emitted(self.desc(), C.byref(plan.rows_desc), vsize, abd.data_ptr(), plan_ws.data_ptr(),
+                                                        plan_ws.numel(), n_words, sws.data_ptr(), sws.numel(), sp))
+        return True
+
     def release_workspaces(self) -> None:
         """give the scratch of the counting pipelines back (record buffers, word buffers, plans: tens of GB at BASELINE sizes); the
         table keeps its counts, the next count allocates again"""
@@ -1728,6 +1813,13 @@ def features(stream: ReadStream, rows: Rows | Plan, k_tnf: int | None = 4, table
         if tnf is None:
             return tnf, abd
         table = None                         # the lookup kernel below only counts TNF
+    elif table is not None and table.kind == "mini" and mini_find_wanted():
+        # a finished mini table without records of these rows (loaded, merged, counted from other reads or without rows): its
+        # buckets find the k-mers of the stream's records (``abundance_of``; the lookup form where that does not apply)
+        table.abundance_of(stream, plan, window, vsize, out=abd)
+        if tnf is None:
+            return tnf, abd
+        table = None
     with torch.cuda.device(dev):
         _lib.check(_lib.load().pg_features(
             stream.codes.data_ptr(), stream.valid.data_ptr(), stream.n_words,
