@@ -76,7 +76,8 @@ _MiniNext = namedtuple("_MiniNext", "key ws event rows held")                  #
 _Half = namedtuple("_Half", "fill n_words rows window vsize")                  # between count_half and lookup_half
 # a word range of a count in pieces: its plan, its 2-byte provisional slots, its bucket-ordered records' meta words, its words
 _Piece = namedtuple("_Piece", "plan_ws merge_ws meta n_words")
-_Optimistic = namedtuple("_Optimistic", "stream word_begin word_end rows emit half")   # the arguments of a count to do again
+# the arguments of a count to do again -- every one of them: ``lowercase_is_base`` decides the planes, ``world`` (a count half) the pieces
+_Optimistic = namedtuple("_Optimistic", "stream word_begin word_end rows emit half lowercase_is_base world")
 
 
 class KmerTable:
@@ -113,6 +114,7 @@ class KmerTable:
         self._mini_rec_ws = None
         self._mini_sized_for = None      # (n_words, geometry) the record / slot workspaces were sized for (with slack)
         self._mini_optimistic = None     # _Optimistic: the arguments of a count that ran on them without reading its plan's counts
+        self.recounts = 0                # counts ``check_status`` did again because the kernels refused the kept workspaces (see ``count``)
         self._mini_pieces = 1            # word ranges the last count of a mini table was done in (``_count_mini_pieces``)
         self._half = None                # _Half, between count_half and lookup_half (N > 1 ranks)
         self._half_ws = None
@@ -458,7 +460,14 @@ class KmerTable:
         reference's own row counters reset on them (count_kmer.cpp:73-78), so k-mers that are only valid under this rule
         enter the table but belong to no row.  Only matters for soft-masked input (``stream.valid_lower`` is not None).
         Paired input with bases below the quality threshold (``stream.valid_lowq``, jellyfish's --min-qual-char=? of
-        feature.py:76-83) is always counted without them, and without ``rows`` / ``emit`` (see ``ReadStream.table_valid``)."""
+        feature.py:76-83) is always counted without them, and without ``rows`` / ``emit`` (see ``ReadStream.table_valid``).
+
+        ``check=False`` on a mini table, the contract: a count that picked up a plan computed ahead (``prefetch_plan``) may run on
+        the workspaces the previous batch sized without having read its plan's record counts.  If they turn out too small the
+        kernels count NOTHING, and ``check_status()`` counts again with workspaces of the right size and adds one to
+        ``self.recounts``.  So whatever was derived from the table between this call and ``check_status()`` -- ``features`` rows,
+        ``items()``, an encode of those rows -- is void if ``recounts`` moved across ``check_status()``, and must be derived
+        again.  (``check=True`` calls ``check_status()`` itself: nothing can lie in between.)"""
         _require_gpu(stream.codes, "the read stream")
         if stream.device != self.device:
             raise ValueError("stream and table are on different devices")
@@ -477,7 +486,7 @@ class KmerTable:
         if self.kind in ("mini", "miniw"):
             if deferred_group is not None:
                 raise ValueError("mini tables have no deferred form")
-            return self._count_mini(stream, word_begin, word_end, table_plane, rows, emit, lenient, check)
+            return self._count_mini(stream, word_begin, word_end, table_plane, rows, emit, lenient, check, lowercase_is_base=lowercase_is_base)
         if deferred_group is not None:
             if not self.can_defer(word_end - word_begin):
                 raise ValueError("deferred counting needs a fresh bucketed table with more than 256 buckets and a single pass")
@@ -568,14 +577,16 @@ class KmerTable:
         _require_gpu(stream.codes, "the read stream")
         self._half_world = int(world)
         if not self.half_masked(stream, lowercase_is_base):
-            return self._count_mini(stream, 0, stream.n_words, stream.table_valid(False), rows, emit, False, check, half=True)
+            return self._count_mini(stream, 0, stream.n_words, stream.table_valid(False), rows, emit, False, check, half=True,
+                                    lowercase_is_base=lowercase_is_base)
         if rows is None or rows.n_rows > _lib.MINI_MASKED_MAX_ROWS or not _merged_lookups():
             raise ValueError(f"count_half() of masked input needs the merged lookups and at most {_lib.MINI_MASKED_MAX_ROWS} rows")
         # (the rows' own rule: the strict plane rides along, as in ``count``)
         return self._count_mini(stream, 0, stream.n_words, stream.union_valid(lowercase_is_base), rows, emit, True, check,
-                                half=True, tab_plane=stream.table_valid(lowercase_is_base))
+                                half=True, tab_plane=stream.table_valid(lowercase_is_base), lowercase_is_base=lowercase_is_base)
 
-    def _count_mini(self, stream, word_begin, word_end, table_plane, rows, emit, lenient, check, half=False, tab_plane=None):
+    def _count_mini(self, stream, word_begin, word_end, table_plane, rows, emit, lenient, check, half=False, tab_plane=None,
+                    lowercase_is_base=False):
         """the super-k-mer pipeline (pg_mini_plan + pg_mini_count): a fresh table, one piece.  The partition plan depends on
         the stream, the rows and the geometry only and is kept: counting the same range again skips pg_mini_plan.
         ``tab_plane`` (a masked count half): the table plane, ``table_plane`` then being the union plane the kernels segment."""
@@ -647,7 +658,9 @@ class KmerTable:
         self._mini_pieces = 1
         self._records = (keep, n_words) if fuse and not half else None
         self._emitted = (window, vsize) if fuse and not half else None
-        self._mini_optimistic = _Optimistic(stream, word_begin, word_end, rows, emit, half) if optimistic else None
+        self._mini_optimistic = (_Optimistic(stream, word_begin, word_end, rows, emit, half, bool(lowercase_is_base),
+                                             self._half_world if half else 1)
+                                 if optimistic else None)
         if check:
             self.check_status()
         return self
@@ -914,7 +927,10 @@ class KmerTable:
         """compute the partition plan of the NEXT count of ``stream`` (whole range, strict validity) on the stream ``side``, into a
         workspace of its own: ``side`` waits for what the current stream has enqueued so far -- call this right after ``count`` and
         the plan of batch i + 1 runs under the row histograms and the encode of batch i instead of in front of its own count.
-        The next ``count`` of the same stream and rows picks it up (and waits for it); any other count ignores it."""
+        The next ``count`` of the same stream and rows picks it up (and waits for it); any other count ignores it.
+
+        Where workspaces of a batch of the same size exist, that count does not read the plan's record counts on the host: see
+        ``count`` for what that means to a caller who passes ``check=False`` (``recounts``)."""
         if self.kind not in ("mini", "miniw"):
             raise ValueError("prefetch_plan() is for mini tables")
         if stream.table_valid(False) is not stream.valid or not stream.rows_inside_table:
@@ -1073,7 +1089,8 @@ class KmerTable:
             torch.cuda.empty_cache()
 
     def check_status(self) -> None:
-        """raise what the kernels reported in the status word (include/pangaea_feat.h: PG_STATUS_*)"""
+        """raise what the kernels reported in the status word (include/pangaea_feat.h: PG_STATUS_*).  A count that ran on kept
+        workspaces and was refused by the kernels is done again here, silently but for ``recounts`` (see ``count``)."""
         if self.kind == "dense":
             return
         st = int(self.status[0].item())
@@ -1085,13 +1102,16 @@ class KmerTable:
                 # the count ran on the previous batch's workspaces without waiting for its plan's record counts, and this batch has
                 # more records than they hold: nothing was written -- read the counts, size the workspaces, count again
                 self._mini_optimistic = None
+                self.recounts += 1
                 self.status.zero_()
                 self.plan_counts()
                 self._empty = True
                 if again.half:
-                    self.count_half(again.stream, again.rows, again.emit, check=False)
+                    self.count_half(again.stream, again.rows, again.emit, check=False, world=again.world,
+                                    lowercase_is_base=again.lowercase_is_base)
                 else:
-                    self.count(again.stream, again.word_begin, again.word_end, check=False, rows=again.rows, emit=again.emit)
+                    self.count(again.stream, again.word_begin, again.word_end, check=False, rows=again.rows, emit=again.emit,
+                               lowercase_is_base=again.lowercase_is_base)
                 return self.check_status()
             self._mini_plan = None
             raise RuntimeError("the partition plan did not describe this stream (PG_STATUS_PLAN_MISMATCH): nothing was counted")
