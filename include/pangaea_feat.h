@@ -464,6 +464,57 @@ int pg_table_merge_aligned(const pg_table *dst, const pg_table *const *srcs, int
 int pg_table_merge_aligned_applies(const pg_table *a, const pg_table *b);
 
 /* ----------------------------------------------------------------------------------------------
+ * Combining finished tables otherwise than by their sum (device; one GPU, any of the five kinds).  The tables are those of
+ * src/feature.py:76-94 and the dump count_kmer.cpp:139-170 reads; the reference itself never combines two of them, so these
+ * entries stand beside those lines and replace nothing of the reference.  For a canonical k-mer let a be the count table `a`
+ * STORES for it and b the count table `b` stores, 0 where absent (a packed kind stops at PG_HASH_COUNT_SAT: the stored value
+ * counts, as in pg_table_merge).  The result holds r, and only where lower <= r <= upper (lower >= 1; upper < 0: no upper bound):
+ *   PG_COMBINE_MIN   min(a, b)              intersection, the smaller count
+ *   PG_COMBINE_MAX   max(a, b)              union, the larger count
+ *   PG_COMBINE_DIFF  a > b ? a - b : 0      counter subtraction
+ *   PG_COMBINE_LEFT  b > 0 ? a : 0          intersection, a's counts
+ *   PG_COMBINE_ONLY  b == 0 ? a : 0         k-mer subtraction
+ *   PG_COMBINE_KEEP  a                      a filter; b must be NULL (and must not be for the others)
+ * Sources are only read (plain loads); a and b may be the same table.  All three entries are additive to ABI 9; every argument
+ * is checked before anything is enqueued (PG_EINVAL with a pg_last_error text: a null table or status, differing k, a kind that
+ * does not admit k, an unknown op, KEEP with a b or another op without, lower < 1, 0 <= upper < lower, data not 16-byte aligned,
+ * dst aliasing a source, the aligned entry on tables pg_table_merge_aligned_applies does not pair, cap < 0).
+ *   pg_table_combine_aligned  stands beside the tables of feature.py:76-94 (replaces nothing of the reference): dst, a and b are
+ *                             all PG_TABLE_MINI, or all PG_TABLE_HASH in LDS-sized buckets, of one k and geometry
+ *                             (pg_table_merge_aligned_applies(dst, a) and (dst, b) are 1).  One workgroup per bucket combines
+ *                             the two slices inside LDS and writes the slice of dst once, 16 bytes per store -- only streams, no
+ *                             global atomics.  dst is REBUILT: its old content is neither read nor need be initialised, and a
+ *                             bucket that loses entries has its probing chains built anew.  Only PG_COMBINE_MAX can run out of
+ *                             room: a bucket whose union does not fit sets PG_STATUS_TABLE_FULL in status[0] (device
+ *                             uint32_t[2], zeroed by the caller; dst is then incomplete: take pg_table_combine_items).
+ *   pg_table_combine_items    stands beside the tables of feature.py:76-94 and the dump count_kmer.cpp:139-170 reads
+ *                             (replaces nothing of the reference), general form: every entry of `a` is looked up in `b`, whatever
+ *                             the two kinds and geometries, and the survivors leave as items codes[i] (canonical code), counts[i] = r,
+ *                             in no particular order, at i = the old n_out[0] and up; n_out[0] (device, zeroed by the caller
+ *                             before the first call) grows by the number of survivors.  An item at cap or beyond is not stored
+ *                             and sets PG_STATUS_OVERFLOW_LIST in status[0]; cap = a's entries always suffices.  r is not
+ *                             clamped: a value that enters a packed table is clamped to PG_HASH_COUNT_SAT by the insert
+ *                             (pg_kmer_merge).  PG_COMBINE_MAX emits max(a, b) for the entries of `a` only: the union is that
+ *                             call followed by (b, a, PG_COMBINE_ONLY) -- every k-mer leaves exactly one of the two.
+ *   pg_table_compare          stands beside the tables of feature.py:76-94 (replaces nothing of the reference): one pass over
+ *                             `a` that looks every entry up in `b` -- out[0] = a's entries, out[1] = the sum of a's counts, out[2] = entries b
+ *                             holds too, out[3] = the sum of min(a, b) (device uint64_t[4], cleared on `stream` first and
+ *                             written whole).  b == NULL: out[2] = out[3] = 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_COMBINE_MIN 0
+#define PG_COMBINE_MAX 1
+#define PG_COMBINE_DIFF 2
+#define PG_COMBINE_LEFT 3
+#define PG_COMBINE_ONLY 4
+#define PG_COMBINE_KEEP 5
+int pg_table_combine_aligned(const pg_table *dst, const pg_table *a, const pg_table *b /* NULL: keep */, int op,
+                             int64_t lower, int64_t upper /* < 0: none */, uint32_t *status, void *stream);
+int pg_table_combine_items(const pg_table *a, const pg_table *b /* NULL: keep */, int op, int64_t lower, int64_t upper,
+                           uint64_t *codes, uint32_t *counts, int64_t cap, int64_t *n_out /* device [1] */,
+                           uint32_t *status, void *stream);
+int pg_table_compare(const pg_table *a, const pg_table *b /* may be NULL */, uint64_t *out /* device [4] */, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Per-run feature rows (device).  One launch fills both matrices.
  *   tnf_out [n_rows, ncols(k_tnf)] int32: canonical k_tnf-mer counts        (count_tnf.cpp:78-113)
  *   abd_out [n_rows, vsize]        int32: hist[count(kmer)/window]++ where the bin is < vsize

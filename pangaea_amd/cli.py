@@ -5,8 +5,10 @@
                                                                                   (count_kmer.cpp:112-123)
     kmer_table histo {-i F | -1 F -2 F | -g DUMP} -k K [--high 10000] [--full] -o OUT
     kmer_table query {-i F | -1 F -2 F | -g DUMP} -k K [-q FILE] [KMER ...]
-    kmer_table dump  {-i F | -1 F -2 F | -g DUMP} -k K [-L LOWER] -o OUT
+    kmer_table dump  {-i F | -1 F -2 F | -g DUMP} -k K [-L LOWER] [-U UPPER] -o OUT
     kmer_table merge -k K [-g DUMP]... [-i F]... [-L LOWER] -o OUT     (two inputs or more; `jellyfish merge` + `dump -c -t`)
+    kmer_table combine --op {min,max,diff,left,only} -k K {-ga DUMP | -ia F} {-gb DUMP | -ib F} [-L LOWER] [-U UPPER] -o OUT
+    kmer_table compare -k K {-ga DUMP | -ia F} {-gb DUMP | -ib F}      (one JSON line on stdout)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -138,6 +140,13 @@ def _counted(r1: str, r2, k: int, device):
     return count_kmers(stream, k, lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
 
 
+def _check_window(lower: int, upper) -> None:
+    if lower < 1:
+        raise ValueError(f"-L must be at least 1 (got {lower})")
+    if upper is not None and upper < lower:
+        raise ValueError(f"-U ({upper}) is below -L ({lower})")
+
+
 def main_kmer_table(argv=None) -> int:
     """``kmer_table histo``: the count spectrum, one line ``"<count> <distinct k-mers>"`` for count = 1 .. high + 1 (the last
     line gathers every count above ``--high``); lines of 0 are left out unless ``--full``.  ``kmer_table query``: one line
@@ -148,8 +157,13 @@ def main_kmer_table(argv=None) -> int:
     output; jellyfish is not at hand to compare with, so they are unpinned (like the two rules of DESIGN section 2) -- what the
     tests pin is the content, against the oracle.  ``kmer_table merge``: the sum of two or more inputs -- every ``-g DUMP`` loaded
     as ``-g`` elsewhere, every ``-i FASTQ`` counted as ``-i`` elsewhere, both repeatable -- as one table (``KmerTable.merged``: what
-    `jellyfish merge` makes of the tables of feature.py:76-94), written as ``kmer_table dump`` writes it.  Exit status 0, or 1 with
-    a message on stderr, as ``main_count_kmer``."""
+    `jellyfish merge` makes of the tables of feature.py:76-94), written as ``kmer_table dump`` writes it.  ``kmer_table combine``:
+    two inputs -- A from ``-ga DUMP`` or ``-ia FASTQ``, B from ``-gb`` or ``-ib``, loaded or counted as ``-g`` / ``-i`` are elsewhere
+    -- met by ``--op`` (``KmerTable.combined``: min, max, diff = counts subtracted, left = A's counts of the shared k-mers, only =
+    A's k-mers that B lacks), kept where LOWER <= count <= UPPER and written as ``kmer_table dump`` writes a table.  ``kmer_table
+    compare``: one JSON line of ``KmerTable.compare`` on the same two inputs.  ``kmer_table dump -U UPPER`` writes only the
+    entries of count <= UPPER (``KmerTable.filtered``); without ``-U`` nothing about ``dump`` changes.  Exit status 0, or 1 with a
+    message on stderr, as ``main_count_kmer``."""
     p = _Parser(prog="kmer_table")
     sub = p.add_subparsers(dest="cmd", required=True)
     for name in ("histo", "query", "dump"):
@@ -165,6 +179,7 @@ def main_kmer_table(argv=None) -> int:
             q.add_argument("-o", "--output", required=True)
         elif name == "dump":
             q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
+            q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
             q.add_argument("-o", "--output", required=True)
         else:
             q.add_argument("-q", "--queries", default="")
@@ -175,9 +190,42 @@ def main_kmer_table(argv=None) -> int:
     q.add_argument("-k", "--kmer", type=int, required=True)
     q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
     q.add_argument("-o", "--output", required=True)
+    for name in ("combine", "compare"):
+        q = sub.add_parser(name)
+        q.add_argument("-ga", "--global-a", dest="global_a", default="")
+        q.add_argument("-ia", "--interleaved-a", dest="interleaved_a", default="")
+        q.add_argument("-gb", "--global-b", dest="global_b", default="")
+        q.add_argument("-ib", "--interleaved-b", dest="interleaved_b", default="")
+        q.add_argument("-k", "--kmer", type=int, required=True)
+        if name == "combine":
+            q.add_argument("--op", required=True)
+            q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
+            q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
+            q.add_argument("-o", "--output", required=True)
     a = p.parse_args(argv)
     from . import _lib
     try:
+        if a.cmd in ("combine", "compare"):
+            for side, g, i in (("A", a.global_a, a.interleaved_a), ("B", a.global_b, a.interleaved_b)):
+                if bool(g) == bool(i):
+                    raise ValueError(f"input {side} is -g{side.lower()} DUMP or -i{side.lower()} FASTQ (one of the two)")
+            if not 1 <= a.kmer <= _lib.WIDE_MAX_K:
+                raise ValueError(f"k-mer size {a.kmer} unsupported (1..{_lib.WIDE_MAX_K})")
+            if a.cmd == "combine":
+                if a.op not in ("min", "max", "diff", "left", "only"):
+                    raise ValueError(f"--op must be one of min, max, diff, left, only (got {a.op!r})")
+                _check_window(a.lower, a.upper)
+            import torch
+            from .kmer import KmerTable
+            device = torch.device("cuda", torch.cuda.current_device())
+            A, B = (KmerTable.from_dump(g, a.kmer, device) if g else _counted(i, None, a.kmer, device)
+                    for g, i in ((a.global_a, a.interleaved_a), (a.global_b, a.interleaved_b)))
+            if a.cmd == "compare":
+                import json
+                sys.stdout.write(json.dumps(A.compare(B)) + "\n")
+            else:
+                KmerTable.combined(A, B, a.op, lower=a.lower, upper=a.upper).write_dump(a.output)
+            return 0
         if a.cmd == "merge":
             if len(a.global_) + len(a.interleaved) < 2:
                 raise ValueError("merge needs two inputs or more (-g DUMP and -i FASTQ, both repeatable)")
@@ -202,9 +250,11 @@ def main_kmer_table(argv=None) -> int:
             with open(a.output, "w") as f:
                 f.writelines(f"{c} {int(hist[c])}\n" for c in range(1, a.high + 2) if a.full or hist[c])
         elif a.cmd == "dump":
-            if a.lower < 1:
-                raise ValueError(f"-L must be at least 1 (got {a.lower})")
-            _table_for(a).write_dump(a.output, a.lower)
+            _check_window(a.lower, a.upper)
+            if a.upper is None:
+                _table_for(a).write_dump(a.output, a.lower)
+            else:
+                _table_for(a).filtered(a.lower, a.upper).write_dump(a.output)
         else:
             from .kmer import encode_kmers
             asked = list(a.kmers)

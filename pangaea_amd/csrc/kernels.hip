@@ -1693,6 +1693,324 @@ __global__ __launch_bounds__(BLOCK) void table_merge_kernel(const uint4 *__restr
     }
 }
 
+// -------------------------------------------------------------------------------- combining finished tables
+//
+// Two tables of feature.py:76-94 met otherwise than by their sum.  For a canonical k-mer let a, b be the counts tables A and B
+// STORE for it (0: absent); the result stores r where lower <= r <= upper:
+//   MIN min(a, b)   MAX max(a, b)   DIFF a > b ? a - b : 0   LEFT b ? a : 0   ONLY b ? 0 : a   KEEP a (no B)
+// Two forms, as for the sum.
+//
+// ALIGNED (table_combine_aligned_kernel): A, B and the result are all MINI tables, or all bucketed HASH tables, of one geometry;
+// one workgroup per bucket, the slice is written exactly once with 16-byte stores, its old content is never read.
+//   MAX: the LDS table is zeroed, A's slice and B's slice are streamed as table_merge_aligned_kernel streams them, a key that is
+//        already there keeps the larger count (lds_larger).  A union that does not fit sets PG_STATUS_TABLE_FULL.
+//   the others: the result is a subset of A's bucket.  A's slice is loaded into LDS, B's slice is streamed and every B entry walks
+//        A's chain (read-only but for the matched slot, at most the view's limit() steps).  Each A slot is matched by at most one B
+//        entry, which rewrites the slot's count to r where r > 0 -- the key bits, all a walking lane compares, stay -- and sets the
+//        slot's bit of an LDS bitmap: "matched" for MIN / LEFT (no bit: b == 0, the slot dies), "dead" for DIFF / ONLY (r == 0;
+//        a slot cannot be cleared in place, an emptied slot would cut the chains the other lanes are walking).
+// Removing entries breaks linear-probing chains, so a bucket that loses entries is REBUILT: every lane takes its slots (at most
+// 2^14 / 1024 = 16) into registers, dropping the dead ones and those outside the window, the table is zeroed, the survivors are
+// inserted again with lds_merge_entry from their home slots (they fit: a subset of what fitted), and the slice is written.
+// LDS: 8 B per slot + 1 bit per slot (128 KiB + 2 KiB for 2^14-slot buckets), all of it dynamic.
+enum { COMBINE_MIN = PG_COMBINE_MIN, COMBINE_MAX = PG_COMBINE_MAX, COMBINE_DIFF = PG_COMBINE_DIFF, COMBINE_LEFT = PG_COMBINE_LEFT,
+       COMBINE_ONLY = PG_COMBINE_ONLY, COMBINE_KEEP = PG_COMBINE_KEEP };
+constexpr int COMBINE_PER_LANE = (1 << PG_BUCKET_MAX_LOG2_SLOTS) / BIG_BLOCK;
+static_assert(COMBINE_PER_LANE == 16, "a lane holds its share of the largest bucket in registers while the bucket is rebuilt");
+
+// r of the table above for an entry of A (a > 0)
+__device__ __forceinline__ uint32_t combine_result(int op, uint32_t a, uint32_t b)
+{
+    switch (op) {
+    case COMBINE_MIN: return a < b ? a : b;
+    case COMBINE_MAX: return a > b ? a : b;
+    case COMBINE_DIFF: return a > b ? a - b : 0u;
+    case COMBINE_LEFT: return b ? a : 0u;
+    case COMBINE_ONLY: return b ? 0u : a;
+    default: return a;
+    }
+}
+
+// lds_merge with "the larger count" in place of the saturating sum
+__device__ __forceinline__ bool lds_larger(unsigned long long *tab, uint32_t smask, uint32_t limit, uint64_t e, uint32_t s, unsigned long long cur)
+{
+    if (e == 0) return true;
+    const uint64_t code = e >> HASH_CBITS;
+    uint32_t cnt = (uint32_t)(e & HASH_CMASK);
+    if (cnt > HASH_SAT) cnt = HASH_SAT;
+    for (uint32_t tries = 0; tries < limit; ++tries) {
+        for (;;) {
+            if (cur != 0 && (cur >> HASH_CBITS) != code) break;
+            const uint32_t have = (uint32_t)(cur & HASH_CMASK);
+            if (cur != 0 && have >= cnt) return true;
+            const unsigned long long old = atomicCAS(&tab[s], cur, (unsigned long long)((code << HASH_CBITS) | cnt));
+            if (old == cur) return true;
+            cur = old;
+        }
+        s = (s + 1) & smask;
+        cur = tab[s];
+    }
+    return false;
+}
+
+template <bool MINI>
+__global__ __launch_bounds__(BIG_BLOCK) void table_combine_aligned_kernel(const ulonglong2 *__restrict__ a, const ulonglong2 *__restrict__ b, int op,
+                                                                          uint64_t lower, uint64_t upper, HashView t, uint32_t *status)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned long long tab[];
+    const uint32_t n_slots = 1u << t.log2_bucket;
+    const uint32_t smask = n_slots - 1;
+    const uint32_t limit = t.limit();
+    const int hsh = KEY_BITS - t.log2_slots;
+    const uint32_t n_pairs = n_slots >> 1;                                       // (buckets have at least 2^4 slots)
+    const uint64_t first_pair = (uint64_t)blockIdx.x << (t.log2_bucket - 1);     // the bucket's slice, in 16-byte pairs of slots
+    const uint32_t n_flag_words = (n_slots + 31) >> 5;
+    uint32_t *flags = reinterpret_cast<uint32_t *>(tab + n_slots);               // one bit per slot, behind the table
+    ulonglong2 *tab2 = reinterpret_cast<ulonglong2 *>(tab);
+    ulonglong2 *out = reinterpret_cast<ulonglong2 *>(t.slots) + first_pair;
+    a += first_pair;
+    if (b) b += first_pair;
+#define PG_HOME(CODE) ((MINI ? mini_slot_hash<true>(CODE) : (uint32_t)((CODE) >> hsh)) & smask)
+    if (op == COMBINE_MAX) {
+        for (uint32_t i = threadIdx.x; i < n_pairs; i += BIG_BLOCK) tab2[i] = make_ulonglong2(0ull, 0ull);
+        __syncthreads();
+        bool full = false;
+        for (int p = 0; p < 2; ++p) {
+            const ulonglong2 *__restrict__ src = p ? b : a;
+            for (uint32_t base = 0; base < n_pairs; base += BIG_BLOCK * ALIGNED_PAIRS) {
+                uint64_t e[2 * ALIGNED_PAIRS];
+#pragma unroll
+                for (int j = 0; j < ALIGNED_PAIRS; ++j) {
+                    const uint32_t i = base + (uint32_t)j * BIG_BLOCK + threadIdx.x;
+                    const ulonglong2 v = i < n_pairs ? src[i] : make_ulonglong2(0ull, 0ull);
+                    e[2 * j] = v.x;
+                    e[2 * j + 1] = v.y;
+                }
+                uint32_t ss[2 * ALIGNED_PAIRS];
+                unsigned long long first[2 * ALIGNED_PAIRS];
+#pragma unroll
+                for (int j = 0; j < 2 * ALIGNED_PAIRS; ++j) {
+                    ss[j] = PG_HOME(e[j] >> HASH_CBITS);
+                    first[j] = e[j] ? tab[ss[j]] : 0ull;
+                }
+#pragma unroll
+                for (int j = 0; j < 2 * ALIGNED_PAIRS; ++j)
+                    if (e[j] & HASH_CMASK) full |= !lds_larger(tab, smask, limit, e[j], ss[j], first[j]);
+            }
+        }
+        if (full) atomicOr(status, PG_STATUS_TABLE_FULL);
+        __syncthreads();
+        if (lower <= 1 && upper >= HASH_CMASK) {                                 // (the same for the whole grid) nothing leaves: no rebuild
+            for (uint32_t i = threadIdx.x; i < n_pairs; i += BIG_BLOCK) out[i] = tab2[i];
+            return;
+        }
+    } else {
+        for (uint32_t i = threadIdx.x; i < n_pairs; i += BIG_BLOCK) tab2[i] = a[i];
+        for (uint32_t i = threadIdx.x; i < n_flag_words; i += BIG_BLOCK) flags[i] = 0u;
+        __syncthreads();
+        if (b) {
+            for (uint32_t base = 0; base < n_pairs; base += BIG_BLOCK * ALIGNED_PAIRS) {
+                uint64_t e[2 * ALIGNED_PAIRS];
+#pragma unroll
+                for (int j = 0; j < ALIGNED_PAIRS; ++j) {
+                    const uint32_t i = base + (uint32_t)j * BIG_BLOCK + threadIdx.x;
+                    const ulonglong2 v = i < n_pairs ? b[i] : make_ulonglong2(0ull, 0ull);
+                    e[2 * j] = v.x;
+                    e[2 * j + 1] = v.y;
+                }
+#pragma unroll
+                for (int j = 0; j < 2 * ALIGNED_PAIRS; ++j) {
+                    const uint32_t cb = (uint32_t)(e[j] & HASH_CMASK);
+                    if (cb == 0) continue;                                       // (an empty slot; a stored count of 0 is b == 0)
+                    const uint64_t code = e[j] >> HASH_CBITS;
+                    uint32_t s = PG_HOME(code);
+                    for (uint32_t tries = 0; tries < limit; ++tries) {
+                        const unsigned long long cur = tab[s];
+                        if (cur == 0) break;
+                        if ((cur >> HASH_CBITS) == code) {
+                            const uint32_t r = combine_result(op, (uint32_t)(cur & HASH_CMASK), cb);
+                            if (r) tab[s] = (unsigned long long)((code << HASH_CBITS) | r);
+                            if (op == COMBINE_MIN || op == COMBINE_LEFT || r == 0) atomicOr(&flags[s >> 5], 1u << (s & 31));
+                            break;
+                        }
+                        s = (s + 1) & smask;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // the rebuild: survivors into registers, an empty table, every survivor in again from its home slot
+    const bool marked_live = op == COMBINE_MIN || op == COMBINE_LEFT;
+    const bool use_flags = op != COMBINE_MAX && op != COMBINE_KEEP;
+    uint64_t v[COMBINE_PER_LANE];
+#pragma unroll
+    for (int j = 0; j < COMBINE_PER_LANE; ++j) {
+        const uint32_t i = (uint32_t)j * BIG_BLOCK + threadIdx.x;
+        uint64_t x = i < n_slots ? tab[i] : 0ull;
+        if (x != 0 && use_flags && (((flags[i >> 5] >> (i & 31)) & 1u) != 0) != marked_live) x = 0ull;
+        const uint64_t c = x & HASH_CMASK;
+        if (c < lower || c > upper) x = 0ull;                                    // (lower >= 1: a count of 0 never stays)
+        v[j] = x;
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_pairs; i += BIG_BLOCK) tab2[i] = make_ulonglong2(0ull, 0ull);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < COMBINE_PER_LANE; ++j) {
+        if (v[j] == 0) continue;
+        const uint32_t s = PG_HOME(v[j] >> HASH_CBITS);
+        lds_merge_entry(tab, smask, limit, v[j], s, tab[s]);                     // (always finds room: fewer entries than the bucket held)
+    }
+#undef PG_HOME
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < n_pairs; i += BIG_BLOCK) out[i] = tab2[i];
+}
+
+// GENERAL (table_combine_items_kernel): any kind against any kind, whatever the geometries.  A's storage is streamed as
+// table_merge_kernel streams a source (dump_load, MERGE_QUADS 16-byte loads in flight per lane); every entry of A is looked up in B
+// as table_query_kernel looks a code up -- the first probes of a lane's batch issued before any is resolved, hash_probe / wide_probe,
+// dense by index; TK_NONE: no B, b = 0 --, r is computed, and the entries inside the window leave as (canonical code, count) items
+// through one cursor.  The cursor is aggregated further than table_compact_kernel's ballot per turn: a lane counts the survivors
+// of its batch (at most 8), the workgroup scans the counts (dump_block_scan) and claims its range with ONE 64-bit atomic add per
+// batch -- 2^29 slots are 2^18 adds on the one word; one add per wavefront and turn, 2^23 of them, took 90 ms of a 113 ms
+// combine on the bench tables.  An item past `cap` is not stored and sets PG_STATUS_OVERFLOW_LIST; the cursor goes on counting.  The destination's kind is no
+// template axis: the result table is built from the items by the inserts the library has (pg_kmer_merge, pg_kmer_merge_wide).
+// MAX over both tables is two launches: A against B with MAX, B against A with ONLY.
+
+// entries q, q + stride, .. (MERGE_QUADS quads) of A with B's count of each: code = the canonical code, ca = A's count (0: no
+// entry), cb = B's count (0: not in B)
+template <int FORM, int TK>
+__device__ __forceinline__ void combine_load_probe(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t q0, int64_t stride,
+                                                   int64_t n_quads, int k, const uint32_t *__restrict__ dense_b, const HashView &b,
+                                                   uint64_t (&code)[MERGE_QUADS * DUMP_PER], uint32_t (&ca)[MERGE_QUADS * DUMP_PER],
+                                                   uint32_t (&cb)[MERGE_QUADS * DUMP_PER])
+{
+    constexpr int N = MERGE_QUADS * DUMP_PER;
+    uint64_t key[N], hh[N], cur[N];
+#pragma unroll
+    for (int u = 0; u < MERGE_QUADS; ++u) {
+        const int64_t q = q0 + u * stride;
+        uint64_t raw[DUMP_PER] = {0, 0, 0, 0};
+        uint32_t cnt[DUMP_PER] = {0, 0, 0, 0};
+        bool present[DUMP_PER] = {false, false, false, false};
+        if (q < n_quads) dump_load<FORM>(slots, counts, q, raw, cnt, present);
+#pragma unroll
+        for (int j = 0; j < DUMP_PER; ++j) {
+            const int i = u * DUMP_PER + j;
+            ca[i] = present[j] ? cnt[j] : 0u;
+            code[i] = FORM == DUMP_HASH ? key42_inverse(raw[j]) : raw[j];
+            key[i] = hh[i] = cur[i] = 0;
+            if (TK == TK_NONE || ca[i] == 0) continue;
+            if (TK == TK_DENSE) {
+                cur[i] = (code[i] >> (2 * k)) == 0 ? dense_b[(uint32_t)code[i]] : 0u;          // (never indexed beyond 4^k)
+            } else {
+                key[i] = TK != TK_HASH ? code[i] : FORM == DUMP_HASH ? raw[j] : key42(code[i]);
+                hh[i] = TK == TK_WIDE ? b.home_wide(code[i]) : (TK == TK_MINI || TK == TK_MINIW) ? b.home_mini(code[i], k) : b.home_key(key[i]);
+                cur[i] = b.slots[hh[i]];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        cb[i] = 0;
+        if (TK == TK_NONE || ca[i] == 0) continue;
+        bool found;
+        if (TK == TK_DENSE) cb[i] = (uint32_t)cur[i];
+        else if (TK == TK_WIDE || TK == TK_MINIW) cb[i] = wide_probe(b, hh[i], cur[i], key[i], &found);
+        else cb[i] = hash_probe(b, hh[i], cur[i], key[i], &found);
+    }
+}
+
+template <int FORM, int TK>
+__global__ __launch_bounds__(BLOCK) void table_combine_items_kernel(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t n_quads,
+                                                                    int k, const uint32_t *__restrict__ dense_b, HashView b, int op, uint64_t lower,
+                                                                    uint64_t upper, uint64_t *__restrict__ out_codes, uint32_t *__restrict__ out_counts,
+                                                                    unsigned long long cap, unsigned long long *__restrict__ n_out, uint32_t *status)
+{
+    constexpr int N = MERGE_QUADS * DUMP_PER;
+    __shared__ uint32_t part[WAVES];
+    __shared__ unsigned long long cursor;
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    // (the trip count is the same for the whole workgroup: the scan and its barriers run with every lane)
+    for (int64_t base = (int64_t)blockIdx.x * BLOCK; base < n_quads; base += stride * MERGE_QUADS) {
+        uint64_t code[N];
+        uint32_t ca[N], cb[N];
+        combine_load_probe<FORM, TK>(slots, counts, base + threadIdx.x, stride, n_quads, k, dense_b, b, code, ca, cb);
+        uint32_t mine = 0;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const uint32_t r = ca[i] ? combine_result(op, ca[i], cb[i]) : 0u;
+            ca[i] = r != 0 && r >= lower && r <= upper ? r : 0u;                 // (from here on: the count that leaves, 0 = none)
+            mine += ca[i] != 0;
+        }
+        uint32_t total;
+        const uint32_t before = dump_block_scan(mine, part, &total);
+        if (total == 0) continue;                                                // (the same for the whole workgroup)
+        if (threadIdx.x == 0) cursor = atomicAdd(n_out, (unsigned long long)total);
+        lds_sync();                                                              // (the next write of `cursor` lies behind the scan's barriers)
+        unsigned long long pos = cursor + before;
+        bool over = false;
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (ca[i] == 0) continue;
+            if (pos < cap) {
+                out_codes[pos] = code[i];
+                out_counts[pos] = ca[i];
+            } else {
+                over = true;
+            }
+            ++pos;
+        }
+        if (over) atomicOr(status, PG_STATUS_OVERFLOW_LIST);
+    }
+}
+
+// COMPARE (table_compare_kernel): the same pass over A with B probed, no output but four 64-bit sums -- out[0] += A's entries,
+// out[1] += A's total count, out[2] += entries B holds too, out[3] += the sum of min(a, b).  A lane sums in registers, a wavefront
+// by shuffles, the workgroup in LDS, and each workgroup leaves with one global 64-bit add per value (integer sums: the same
+// whatever the order), as table_spectrum_kernel leaves its bins.
+template <int FORM, int TK>
+__global__ __launch_bounds__(BLOCK) void table_compare_kernel(const uint4 *__restrict__ slots, const uint4 *__restrict__ counts, int64_t n_quads, int k,
+                                                              const uint32_t *__restrict__ dense_b, HashView b, unsigned long long *__restrict__ out)
+{
+    constexpr int N = MERGE_QUADS * DUMP_PER;
+    __shared__ unsigned long long part[4];
+    if (threadIdx.x < 4) part[threadIdx.x] = 0ull;
+    __syncthreads();
+    const int64_t stride = (int64_t)gridDim.x * BLOCK;
+    unsigned long long acc[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int64_t base = (int64_t)blockIdx.x * BLOCK; base < n_quads; base += stride * MERGE_QUADS) {
+        uint64_t code[N];
+        uint32_t ca[N], cb[N];
+        combine_load_probe<FORM, TK>(slots, counts, base + threadIdx.x, stride, n_quads, k, dense_b, b, code, ca, cb);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (ca[i] == 0) continue;
+            acc[0] += 1ull;
+            acc[1] += ca[i];
+            if (cb[i]) {
+                acc[2] += 1ull;
+                acc[3] += ca[i] < cb[i] ? ca[i] : cb[i];
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t lo = (uint32_t)acc[j], hi = (uint32_t)(acc[j] >> 32);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const unsigned long long o = ((unsigned long long)(uint32_t)__shfl_down((int)hi, d) << 32) | (uint32_t)__shfl_down((int)lo, d);
+            const unsigned long long s = (((unsigned long long)hi << 32) | lo) + o;
+            lo = (uint32_t)s;
+            hi = (uint32_t)(s >> 32);
+        }
+        if ((threadIdx.x & 63) == 0) atomicAdd(&part[j], ((unsigned long long)hi << 32) | lo);
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && part[threadIdx.x]) atomicAdd(&out[threadIdx.x], part[threadIdx.x]);
+}
+
 // occupied slots of every bucket: the segment lengths of a bucket-ordered compaction (one workgroup per bucket)
 __global__ __launch_bounds__(BLOCK) void bucket_fill_kernel(const uint64_t *__restrict__ slots, int log2_bucket, long long *__restrict__ fill)
 {
@@ -3030,6 +3348,125 @@ extern "C" int pg_table_merge(const pg_table *dst, const pg_table *src, uint32_t
 #undef PG_LAUNCH_TO
     return check_launch("pg_table_merge");
 }
+
+// ---- combining finished tables (min, max, diff, left, only, keep): beside the tables of feature.py:76-94, replacing nothing
+
+// what the three entries refuse alike; `b` may be null where the op says so
+static int combine_args(const char *who, const pg_table *a, const pg_table *b, int op, int64_t lower, int64_t upper)
+{
+    if (!a) return pg_fail(PG_EINVAL, "%s: a is null", who);
+    if (op < PG_COMBINE_MIN || op > PG_COMBINE_KEEP) return pg_fail(PG_EINVAL, "%s: unknown op %d", who, op);
+    if (op == PG_COMBINE_KEEP && b) return pg_fail(PG_EINVAL, "%s: PG_COMBINE_KEEP takes no b", who);
+    if (op != PG_COMBINE_KEEP && !b) return pg_fail(PG_EINVAL, "%s: b is null (only PG_COMBINE_KEEP takes none)", who);
+    if (lower < 1) return pg_fail(PG_EINVAL, "%s: lower is below 1 (%lld)", who, (long long)lower);
+    if (upper >= 0 && upper < lower) return pg_fail(PG_EINVAL, "%s: upper %lld is below lower %lld", who, (long long)upper, (long long)lower);
+    int rc = check_table(a);
+    if (rc) return rc;
+    if (b && (rc = check_table(b))) return rc;
+    if (b && a->k != b->k) return pg_fail(PG_EINVAL, "%s: k differs (a %d, b %d)", who, a->k, b->k);
+    if ((uintptr_t)a->data & 15) return pg_fail(PG_EINVAL, "%s: a->data is not 16-byte aligned", who);
+    if (b && ((uintptr_t)b->data & 15)) return pg_fail(PG_EINVAL, "%s: b->data is not 16-byte aligned", who);
+    return PG_OK;
+}
+
+extern "C" int pg_table_combine_aligned(const pg_table *dst, const pg_table *a, const pg_table *b, int op, int64_t lower, int64_t upper,
+                                        uint32_t *status, void *stream)
+{
+    const char *who = "pg_table_combine_aligned";
+    if (!dst) return pg_fail(PG_EINVAL, "%s: dst is null", who);
+    if (!status) return pg_fail(PG_EINVAL, "%s: status is null", who);
+    int rc = combine_args(who, a, b, op, lower, upper);
+    if (rc) return rc;
+    if ((rc = check_table(dst))) return rc;
+    if (dst->k != a->k) return pg_fail(PG_EINVAL, "%s: k differs (dst %d, a %d)", who, dst->k, a->k);
+    if ((uintptr_t)dst->data & 15) return pg_fail(PG_EINVAL, "%s: dst->data is not 16-byte aligned", who);
+    if (!pg_table_merge_aligned_applies(dst, a) || (b && !pg_table_merge_aligned_applies(dst, b)))
+        return pg_fail(PG_EINVAL, "%s: dst, a and b are not mini tables, or bucketed hash tables, of one geometry (kind %d / %d / %d, 2^%d / 2^%d / 2^%d "
+                                  "slots, buckets of 2^%d / 2^%d / 2^%d)", who, dst->kind, a->kind, b ? b->kind : a->kind, dst->log2_slots, a->log2_slots,
+                       b ? b->log2_slots : a->log2_slots, dst->log2_bucket_slots, a->log2_bucket_slots, b ? b->log2_bucket_slots : a->log2_bucket_slots);
+    if (tables_overlap(dst, a)) return pg_fail(PG_EINVAL, "%s: dst aliases a", who);
+    if (b && tables_overlap(dst, b)) return pg_fail(PG_EINVAL, "%s: dst aliases b", who);
+    const int bits = dst->log2_slots - dst->log2_bucket_slots;
+    // the bucket's slots and one bit for each, the bitmap rounded up to 16 bytes
+    const size_t lds = ((size_t)8 << dst->log2_bucket_slots) + ((((size_t)1 << dst->log2_bucket_slots) / 8 + 15) & ~(size_t)15);
+    const bool mini = dst->kind == PG_TABLE_MINI;
+    const void *fn = mini ? (const void *)table_combine_aligned_kernel<true> : (const void *)table_combine_aligned_kernel<false>;
+    if ((rc = raise_lds_limit(fn, lds, who))) return rc;
+    const uint64_t up = upper < 0 ? ~0ull : (uint64_t)upper;
+    const ulonglong2 *pa = (const ulonglong2 *)a->data, *pb = b ? (const ulonglong2 *)b->data : nullptr;
+    if (mini)
+        hipLaunchKernelGGL((table_combine_aligned_kernel<true>), dim3(1u << bits), dim3(BIG_BLOCK), lds, (hipStream_t)stream, pa, pb, op, (uint64_t)lower,
+                           up, view_of(dst), status);
+    else
+        hipLaunchKernelGGL((table_combine_aligned_kernel<false>), dim3(1u << bits), dim3(BIG_BLOCK), lds, (hipStream_t)stream, pa, pb, op, (uint64_t)lower,
+                           up, view_of(dst), status);
+    return check_launch(who);
+}
+
+// the probed table of the general form and of the comparison: kernel by (form of a, kind of b; TK_NONE: no b)
+#define PG_COMBINE_BY_KIND(FORM, b, LAUNCH)                               \
+    do {                                                                  \
+        if (!(b)) LAUNCH(FORM, TK_NONE);                                  \
+        else switch ((b)->kind) {                                         \
+        case PG_TABLE_DENSE: LAUNCH(FORM, TK_DENSE); break;               \
+        case PG_TABLE_HASH: LAUNCH(FORM, TK_HASH); break;                 \
+        case PG_TABLE_WIDE: LAUNCH(FORM, TK_WIDE); break;                 \
+        case PG_TABLE_MINI: LAUNCH(FORM, TK_MINI); break;                 \
+        default: LAUNCH(FORM, TK_MINIW); break;                           \
+        }                                                                 \
+    } while (0)
+
+extern "C" int pg_table_combine_items(const pg_table *a, const pg_table *b, int op, int64_t lower, int64_t upper, uint64_t *codes, uint32_t *counts,
+                                      int64_t cap, int64_t *n_out, uint32_t *status, void *stream)
+{
+    const char *who = "pg_table_combine_items";
+    if (!status) return pg_fail(PG_EINVAL, "%s: status is null", who);
+    int rc = combine_args(who, a, b, op, lower, upper);
+    if (rc) return rc;
+    if (cap < 0) return pg_fail(PG_EINVAL, "%s: cap is negative (%lld)", who, (long long)cap);
+    if (!n_out) return pg_fail(PG_EINVAL, "%s: n_out is null", who);
+    if (cap > 0 && (!codes || !counts)) return pg_fail(PG_EINVAL, "%s: codes or counts is null", who);
+    DumpView v;
+    if ((rc = dump_view(a, who, &v))) return rc;
+    const int64_t n_quads = v.n_entries / DUMP_PER;                       // (4^k and 2^log2_slots are whole numbers of quads)
+    const int grid = grid_for((n_quads + MERGE_QUADS - 1) / MERGE_QUADS);
+    const HashView hb = !b || b->kind == PG_TABLE_DENSE ? HashView{nullptr, 0, 0} : view_of(b);
+    const uint32_t *dense_b = b && b->kind == PG_TABLE_DENSE ? (const uint32_t *)b->data : nullptr;
+    const uint64_t up = upper < 0 ? ~0ull : (uint64_t)upper;
+#define PG_LAUNCH_ON(FORM, TK)                                                                                                     \
+    hipLaunchKernelGGL((table_combine_items_kernel<FORM, TK>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, (const uint4 *)a->data, v.counts, \
+                       n_quads, a->k, dense_b, hb, op, (uint64_t)lower, up, codes, counts, (unsigned long long)cap, (unsigned long long *)n_out, status)
+#define PG_LAUNCH(FORM) PG_COMBINE_BY_KIND(FORM, b, PG_LAUNCH_ON)
+    PG_DUMP_BY_FORM(v.form, PG_LAUNCH);
+#undef PG_LAUNCH
+#undef PG_LAUNCH_ON
+    return check_launch(who);
+}
+
+extern "C" int pg_table_compare(const pg_table *a, const pg_table *b, uint64_t *out, void *stream)
+{
+    const char *who = "pg_table_compare";
+    if (!a) return pg_fail(PG_EINVAL, "%s: a is null", who);
+    if (!out) return pg_fail(PG_EINVAL, "%s: out is null", who);
+    int rc = combine_args(who, a, b, b ? PG_COMBINE_MIN : PG_COMBINE_KEEP, 1, -1);
+    if (rc) return rc;
+    DumpView v;
+    if ((rc = dump_view(a, who, &v))) return rc;
+    const int64_t n_quads = v.n_entries / DUMP_PER;
+    const int grid = grid_for((n_quads + MERGE_QUADS - 1) / MERGE_QUADS);
+    const HashView hb = !b || b->kind == PG_TABLE_DENSE ? HashView{nullptr, 0, 0} : view_of(b);
+    const uint32_t *dense_b = b && b->kind == PG_TABLE_DENSE ? (const uint32_t *)b->data : nullptr;
+    if (hipMemsetAsync(out, 0, 4 * sizeof(uint64_t), (hipStream_t)stream) != hipSuccess) return pg_fail(PG_EHIP, "%s: cannot clear out", who);
+#define PG_LAUNCH_ON(FORM, TK)                                                                                                     \
+    hipLaunchKernelGGL((table_compare_kernel<FORM, TK>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, (const uint4 *)a->data, v.counts, n_quads, \
+                       a->k, dense_b, hb, (unsigned long long *)out)
+#define PG_LAUNCH(FORM) PG_COMBINE_BY_KIND(FORM, b, PG_LAUNCH_ON)
+    PG_DUMP_BY_FORM(v.form, PG_LAUNCH);
+#undef PG_LAUNCH
+#undef PG_LAUNCH_ON
+    return check_launch(who);
+}
+#undef PG_COMBINE_BY_KIND
 #undef PG_DUMP_BY_FORM
 
 extern "C" int64_t pg_dump_parse_workspace_bytes(int64_t n_bytes)

@@ -122,6 +122,7 @@ class KmerTable:
         self._half_world = 1             # ranks the count half's exchange goes to (its buffers count in the pieces decision)
         self._merge_ws = None            # the provisional words of the merged lookups (fixed slots per record)
         self.merge_form = None           # "aligned" / "general": which kernel built a table that ``merged`` returned
+        self.combine_form = None         # "aligned" / "general": which kernel built a table that ``combined`` / ``filtered`` returned
         self.rows_form = None            # "find" / "lookup": how the last ``abundance_of`` built its rows
 
     # ------------------------------------------------------------------ construction
@@ -222,11 +223,12 @@ class KmerTable:
         return cls(k, "hash", torch.zeros(1 << log2_slots, dtype=torch.int64, device=device), log2_slots, lb)
 
     @classmethod
-    def from_items(cls, k: int, codes, counts, device, kind: str | None = None) -> "KmerTable":
+    def from_items(cls, k: int, codes, counts, device, kind: str | None = None, distinct_hint: int | None = None) -> "KmerTable":
         """table holding exactly the given (canonical code, count) entries -- e.g. a parsed jellyfish dump
         (count_kmer.cpp:139-170 assigns, it does not add: later duplicates must already be resolved).  ``codes`` a tensor on a
         GPU (then ``counts`` too; int64 or uint64): the entries stay on the device -- what ``from_dump`` hands over -- and the
-        table is the one the same entries make as numpy arrays."""
+        table is the one the same entries make as numpy arrays.  ``distinct_hint``: size the table for that many entries
+        rather than for the number given (a caller that grows the table after PG_ETABLEFULL)."""
         on_device = isinstance(codes, torch.Tensor) and codes.is_cuda
         if on_device:
             if not (isinstance(counts, torch.Tensor) and counts.is_cuda) or codes.numel() != counts.numel():
@@ -235,7 +237,7 @@ class KmerTable:
         else:
             codes = torch.as_tensor(np.asarray(codes).astype(np.int64))
             counts = torch.as_tensor(np.asarray(counts).astype(np.int64))
-        table = cls.alloc(k, device, kind, distinct_hint=max(1024, codes.numel()))
+        table = cls.alloc(k, device, kind, distinct_hint=max(1024, codes.numel(), distinct_hint or 0))
         if table.kind in ("wide", "miniw"):
             c = codes.to(table.device).contiguous()
             n = counts.to(table.device, torch.int32).contiguous()
@@ -1498,6 +1500,122 @@ class KmerTable:
                     raise
             del out
             hint *= 2                       # (grow and try again, as counting does)
+
+    # ------------------------------------------------------------------ two finished tables met otherwise than by their sum
+
+    @classmethod
+    def combined(cls, a: "KmerTable", b: "KmerTable | None", op: str, kind: str | None = None, lower: int = 1,
+                 upper: int | None = None) -> "KmerTable":
+        """a fresh table of r(x) for every canonical k-mer x, a and b being the counts the two tables STORE for it (0: absent):
+        ``min`` min(a, b); ``max`` max(a, b); ``diff`` a - b where a > b; ``left`` a where b > 0; ``only`` a where b == 0;
+        ``keep`` a (``b`` is None: see ``filtered``).  Only lower <= r <= upper is kept (``upper`` None: no bound).  The sources --
+        any kinds and geometries, the same k and device; the same table twice is fine -- are only read.  ``kind``: the result's
+        kind, ``a``'s by default.  Where both sources are of the wanted kind and of one geometry that the library's aligned form
+        takes (pg_table_merge_aligned_applies: mini, or hash in LDS-sized buckets), the result has that geometry and is built bucket
+        by bucket inside LDS (pg_table_combine_aligned, ``combine_form == "aligned"``); elsewhere, and when a bucket of an aligned
+        ``max`` overflows, the surviving entries leave as items (pg_table_combine_items) and the result is built from them as
+        ``from_items`` builds a table, sized for their number and grown while it fills up (``combine_form == "general"``).  A value
+        that enters a packed kind (hash, mini) is clamped to HASH_COUNT_SAT, as everywhere."""
+        code = _lib.COMBINE_OPS.get(op) if isinstance(op, str) else None
+        if code is None:
+            raise ValueError(f"unknown op {op!r} (one of {', '.join(_lib.COMBINE_OPS)})")
+        if (op == "keep") != (b is None):
+            raise ValueError("'keep' takes one table and no other" if op == "keep" else f"{op!r} needs two tables")
+        if not isinstance(a, KmerTable):
+            raise TypeError(f"a KmerTable is needed (got {type(a).__name__})")
+        lower, up = int(lower), -1 if upper is None else int(upper)
+        if lower < 1:
+            raise ValueError(f"lower must be at least 1 (got {lower})")
+        if upper is not None and up < lower:
+            raise ValueError(f"upper ({up}) is below lower ({lower})")
+        _require_gpu(a.data, "the table")
+        a._require_counts()
+        if b is not None:
+            a._check_mergeable(b)
+        kind = kind or a.kind
+        if not cls.kind_admits(kind, a.k):
+            raise ValueError(f"{kind!r} tables do not admit k = {a.k}")
+        a._require_readable()
+        if b is not None:
+            b._require_readable()
+        L = _lib.load()
+        dev = a.device
+        others = [a] if b is None else [a, b]
+        if all(t.kind == kind and L.pg_table_merge_aligned_applies(a.desc(), t.desc()) == 1 for t in others):
+            # (the kernel overwrites every slot: no clearing)
+            out = cls(a.k, kind, torch.empty(1 << a.log2_slots, dtype=torch.int64, device=dev), a.log2_slots, a.log2_bucket)
+            with torch.cuda.device(dev):
+                _lib.check(L.pg_table_combine_aligned(out.desc(), a.desc(), None if b is None else b.desc(), code, lower, up,
+                                                      out.status.data_ptr(), _stream_ptr(dev)))
+            if not int(out.status[0].item()) & _lib.STATUS_TABLE_FULL:      # (only a union can outgrow a bucket)
+                out._empty = False
+                out.combine_form = "aligned"
+                out.check_status()
+                return out
+            del out
+        return cls._combined_general(a, b, op, kind, lower, up)
+
+    @classmethod
+    def _combined_general(cls, a: "KmerTable", b: "KmerTable | None", op: str, kind: str, lower: int, up: int) -> "KmerTable":
+        """the general form of ``combined`` (arguments already checked; ``up`` < 0: no upper bound)"""
+        L = _lib.load()
+        dev = a.device
+        code = _lib.COMBINE_OPS[op]
+        # every launch emits a subset of the entries of the table it streams
+        cap = a._n_occupied() + (b._n_occupied() if op == "max" else 0)
+        codes = torch.empty(max(1, cap), dtype=torch.int64, device=dev)
+        counts = torch.empty(max(1, cap), dtype=torch.int32, device=dev)
+        n_out = torch.zeros(1, dtype=torch.int64, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
+        launches = [(a, b, code)] if op != "max" else [(a, b, code), (b, a, _lib.COMBINE_ONLY)]     # (b's own k-mers: the rest of the union)
+        with torch.cuda.device(dev):
+            for x, y, c in launches:
+                _lib.check(L.pg_table_combine_items(x.desc(), None if y is None else y.desc(), c, lower, up, codes.data_ptr(), counts.data_ptr(),
+                                                    cap, n_out.data_ptr(), status.data_ptr(), _stream_ptr(dev)))
+        n = int(n_out.item())
+        if int(status[0].item()) or n > cap:
+            raise RuntimeError(f"pg_table_combine_items emitted {n} items into room for {cap}")
+        codes, counts = codes[:n], counts[:n].to(torch.int64) & 0xFFFFFFFF
+        hint = max(1024, n)
+        while True:
+            try:
+                out = cls.from_items(a.k, codes, counts, dev, kind, distinct_hint=hint)
+                out.check_status()
+                break
+            except _lib.PangaeaError as e:
+                if e.code != _lib.PG_ETABLEFULL or kind == "dense" or hint >= 1 << 39:
+                    raise
+            hint *= 2                       # (grow and try again, as ``merged`` does)
+        out._empty = False
+        out.combine_form = "general"
+        return out
+
+    def filtered(self, lower: int = 1, upper: int | None = None, kind: str | None = None) -> "KmerTable":
+        """a fresh table of this one's k-mers with lower <= count <= upper (``upper`` None: no bound) -- e.g. the solid k-mers as
+        the ``-g`` table of count_kmer: ``combined(self, None, "keep", ...)``, through the same two forms"""
+        return KmerTable.combined(self, None, "keep", kind=kind, lower=lower, upper=upper)
+
+    def compare(self, other: "KmerTable") -> dict:
+        """how much two tables share, from two passes on the GPU (pg_table_compare): ``n_a``, ``n_b`` entries, ``sum_a``, ``sum_b``
+        total counts, ``n_shared`` k-mers both hold, ``sum_min`` the sum of min(a, b) over them (ints); ``jaccard`` =
+        n_shared / (n_a + n_b - n_shared), ``containment_a`` = n_shared / n_a, ``containment_b`` = n_shared / n_b, ``bray_curtis`` =
+        1 - 2 sum_min / (sum_a + sum_b) (floats; a ratio over nothing is 0.0).  Counts are the stored ones."""
+        self._check_mergeable(other)
+        _require_gpu(self.data, "the table")
+        self._require_readable()
+        other._require_readable()
+        L = _lib.load()
+        out = torch.empty(8, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(L.pg_table_compare(self.desc(), other.desc(), out[:4].data_ptr(), _stream_ptr(self.device)))
+            _lib.check(L.pg_table_compare(other.desc(), None, out[4:].data_ptr(), _stream_ptr(self.device)))
+        n_a, sum_a, n_shared, sum_min, n_b, sum_b = (int(v) for v in out.cpu().tolist()[:6])
+
+        def ratio(x, y):
+            return x / y if y else 0.0
+        return {"n_a": n_a, "n_b": n_b, "n_shared": n_shared, "sum_a": sum_a, "sum_b": sum_b, "sum_min": sum_min,
+                "jaccard": ratio(n_shared, n_a + n_b - n_shared), "containment_a": ratio(n_shared, n_a), "containment_b": ratio(n_shared, n_b),
+                "bray_curtis": 1.0 - 2.0 * sum_min / (sum_a + sum_b) if sum_a + sum_b else 0.0}
 
 
 def encode_kmers(strings, k: int) -> np.ndarray:
