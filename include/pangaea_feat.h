@@ -388,6 +388,60 @@ int pg_table_query(const pg_table *t, const uint64_t *codes, int64_t n, uint32_t
 int pg_table_spectrum(const pg_table *t, int high, uint64_t *hist /* device, [high + 2], written whole */, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Depth of sequences in a finished table (device; one GPU, any of the five kinds; the table is only read: plain loads, no
+ * atomics on it).  The sequences are character ranges of a read stream (layout at the top of this header); `valid` is the plane
+ * that says what a base is, jellyfish's lenient one or the strict one.  Both entries are additive to ABI 9; every argument is
+ * checked before the first HIP call.
+ *   A position i HOLDS a k-mer iff i + k <= n_chars and characters i .. i + k - 1 are all set in `valid`; its COUNT is the
+ *   table's multiplicity of that k-mer (made canonical as the counting kernels do), 0 if the table lacks it.  The k-mer at i
+ *   BELONGS to the range [a, b) iff a <= i and i + k <= b.  Its VALUE is its count where count >= lower, else 0.
+ *   pg_table_profile  stands in for `jellyfish query -s FILE` on feature.py:87's table (the multiplicity of every k-mer of a
+ *                     sequence file): counts[i - char_begin] = the count at i for char_begin <= i < char_end, PG_PROFILE_NONE
+ *                     where i holds no k-mer.  A wide count of 2^32 - 1 cannot be told from that.  0 <= char_begin <= char_end
+ *                     <= n_chars, else PG_EINVAL; an empty range: PG_OK, nothing launched.
+ *   pg_table_depth    stands beside the contig depth of scripts/bin_assembly.sh:43 (bwa + samtools +
+ *                     jgi_summarize_bam_contig_depths -> contigs.megahit.depth) that scripts/low_abd_reads.sh:10 cuts at 10
+ *                     and 30: a k-mer depth from a table already in device memory, the same kind of number, NOT the alignment
+ *                     depth.  Per range r < n_ranges, [range_start[r], range_end[r]) (device arrays; ranges are independent:
+ *                     they may overlap, repeat, be unsorted, empty, shorter than k or full of invalid characters), five
+ *                     results out[r][0 .. 4] over the values of the k-mers that belong to it:
+ *                       PG_DEPTH_N_KMERS  how many there are      PG_DEPTH_N_PRESENT  those with value > 0
+ *                       PG_DEPTH_SUM      the sum of the values   PG_DEPTH_MAX        the largest value
+ *                       PG_DEPTH_MEDIAN   the LOWER median: the value at sorted index (n_kmers - 1) / 2, zeros included
+ *                     all 0 for a range without k-mers.  Preconditions 0 <= start <= end <= n_chars; whatever the device
+ *                     arrays hold, bounds are clipped to [0, n_chars] and nothing outside the stream is read.  A stored count
+ *                     of 2^32 - 1 (wide kinds) is taken for "no k-mer" by the long form.  Two forms, chosen per range:
+ *                       short  at most PG_DEPTH_SHORT_MAX characters (reads): one wavefront per range keeps the values in
+ *                              registers, selects the median there and writes the 40 bytes -- no count goes through memory;
+ *                       long   anything longer (contigs, barcodes, a whole stream): the counts of its length - k + 1 positions
+ *                              are stored once in the workspace, 4 bytes each, then one workgroup per range reads them for the
+ *                              sums and selects the median by radix passes with a histogram in LDS.
+ *                     workspace: pg_table_depth_workspace_bytes(n_long, long_positions) -- how many ranges are long and the sum
+ *                     of their (length - k + 1), which the caller knows from its ranges: 256 bytes + 4 per position + 32 per
+ *                     long range (at most PG_DEPTH_MAX_LONG of them in one call, else < 0); 256-byte aligned device memory,
+ *                     at least pg_table_depth_workspace_bytes(0, 0) bytes (its head is cleared on `stream` by every call).  status (device uint32_t[2], zeroed by the caller): a long
+ *                     range that finds no room in the workspace sets PG_STATUS_DEPTH_WORKSPACE in status[0]; the rows of the
+ *                     SHORT ranges are then still right, those of the long ranges must not be used (status[0] must be 0 or
+ *                     free of that bit on entry: the long form does nothing while it is set).  PG_EINVAL: a null pointer, a bad descriptor, negative sizes, lower < 1, n_ranges > 0 without
+ *                     range arrays, a workspace too small or not 256-byte aligned.  n_ranges == 0: PG_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_PROFILE_NONE 0xFFFFFFFFu
+#define PG_DEPTH_SHORT_MAX 512 /* characters; 8 positions per lane of a wavefront, all of them in registers */
+#define PG_DEPTH_MAX_LONG ((1 << 24) - 1) /* long ranges of one call: the workspace's list cursor has 24 bits */
+#define PG_DEPTH_N_KMERS 0
+#define PG_DEPTH_N_PRESENT 1
+#define PG_DEPTH_SUM 2
+#define PG_DEPTH_MAX 3
+#define PG_DEPTH_MEDIAN 4
+#define PG_STATUS_DEPTH_WORKSPACE 16u /* pg_table_depth: a long range found no room in the workspace: no long range's row is valid */
+int pg_table_profile(const pg_table *t, const uint64_t *codes, const uint32_t *valid, int64_t n_chars, int64_t char_begin,
+                     int64_t char_end, uint32_t *counts /* device, [char_end - char_begin] */, void *stream);
+int64_t pg_table_depth_workspace_bytes(int64_t n_long, int64_t long_positions);
+int pg_table_depth(const pg_table *t, const uint64_t *codes, const uint32_t *valid, int64_t n_chars, const int64_t *range_start,
+                   const int64_t *range_end, int64_t n_ranges, int64_t lower, int64_t *out /* device, [n_ranges][5] */,
+                   void *workspace, int64_t workspace_bytes, uint32_t *status, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
  * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
  * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for

@@ -21,6 +21,7 @@ LIB_PATH = (os.path.join(_HERE, "libpangaea_feat.so") if not _WANT else os.path.
             else os.path.abspath(_WANT))
 BUILD_CHECKED, BUILD_STAMPS, BUILD_VARIANT = 1, 2, 4
 STATUS_TABLE_FULL, STATUS_OVERFLOW_LIST, STATUS_PLAN_MISMATCH, STATUS_BOUNDS = 1, 2, 4, 8
+STATUS_DEPTH_WORKSPACE = 16        # PG_STATUS_DEPTH_WORKSPACE: a long range of pg_table_depth found no room in the workspace
 _LIB = None
 
 PG_OK = 0
@@ -43,6 +44,10 @@ KEY42_M2 = 0x1fe1a85ec53
 HLL_REGISTERS = 4096
 QUERY_INVALID = 0xFFFFFFFF         # PG_QUERY_INVALID: pg_table_query's answer to a code with bits at or above 2k
 SPECTRUM_MAX_HIGH = 16382          # PG_SPECTRUM_MAX_HIGH
+PROFILE_NONE = 0xFFFFFFFF          # PG_PROFILE_NONE: pg_table_profile's answer for a position that holds no k-mer
+DEPTH_SHORT_MAX = 512              # PG_DEPTH_SHORT_MAX: the longest range (characters) pg_table_depth keeps in a wavefront's registers
+DEPTH_MAX_LONG = (1 << 24) - 1     # PG_DEPTH_MAX_LONG: longer ranges than that in one pg_table_depth call
+DEPTH_N_KMERS, DEPTH_N_PRESENT, DEPTH_SUM, DEPTH_MAX, DEPTH_MEDIAN = 0, 1, 2, 3, 4      # PG_DEPTH_*: the columns of a depth row
 DUMP_UNIT_SLOTS = 1024             # PG_DUMP_UNIT_SLOTS: entries per unit of pg_table_dump_sizes / pg_table_dump_text
 DUMP_MAX_DIGITS = 18               # PG_DUMP_MAX_DIGITS
 DUMP_CLEAN = (1 << 64) - 1         # PG_DUMP_CLEAN: pg_dump_parse's status word when every line was fine
@@ -177,6 +182,9 @@ def load() -> C.CDLL:
         "pg_mini_wait_first_pass": (i32, [vp]),
         "pg_table_query": (i32, [tp, vp, i64, vp, vp]),
         "pg_table_spectrum": (i32, [tp, i32, vp, vp]),
+        "pg_table_profile": (i32, [tp, vp, vp, i64, i64, i64, vp, vp]),
+        "pg_table_depth_workspace_bytes": (i64, [i64, i64]),
+        "pg_table_depth": (i32, [tp, vp, vp, i64, vp, vp, i64, i64, vp, vp, i64, vp, vp]),
         "pg_table_dump_units": (i64, [tp]),
         "pg_table_dump_sizes": (i32, [tp, i64, vp, vp, vp]),
         "pg_table_dump_text": (i32, [tp, i64, i64, i64, vp, i64, i64, vp, i64, vp]),
@@ -218,7 +226,7 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_abundance_from_records", "pg_abundance_from_emitted", "pg_kmer_count_bucketed_emit",
            "pg_mini_plan_bytes", "pg_mini_plan", "pg_mini_records_bytes", "pg_mini_shuffle_bytes", "pg_mini_shuffle_bytes_merged", "pg_mini_merge_words", "pg_mini_count_piece", "pg_mini_lookup_begin", "pg_mini_lookup_piece", "pg_mini_count", "pg_mini_half_bytes", "pg_mini_count_half", "pg_mini_gather_entries", "pg_mini_merge_bins", "pg_mini_lookup_half", "pg_mini_count_half_piece", "pg_mini_lookup_half_piece", "pg_mini_merge_form_applies", "pg_mini_records_meta_offset", "pg_mini_wait_first_pass", "pg_mini_abundance_from_emitted",
            "pg_mini_plan_masked", "pg_mini_count_half_masked", "pg_mini_count_half_piece_masked", "pg_mini_merge_bins_masked",
-           "pg_table_query", "pg_table_spectrum",
+           "pg_table_query", "pg_table_spectrum", "pg_table_profile", "pg_table_depth_workspace_bytes", "pg_table_depth",
            "pg_table_dump_units", "pg_table_dump_sizes", "pg_table_dump_text", "pg_dump_parse_workspace_bytes", "pg_dump_parse",
            "pg_table_merge", "pg_table_merge_aligned", "pg_table_merge_aligned_applies",
            "pg_table_combine_aligned", "pg_table_combine_items", "pg_table_compare",

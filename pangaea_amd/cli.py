@@ -9,6 +9,7 @@
     kmer_table merge -k K [-g DUMP]... [-i F]... [-L LOWER] -o OUT     (two inputs or more; `jellyfish merge` + `dump -c -t`)
     kmer_table combine --op {min,max,diff,left,only} -k K {-ga DUMP | -ia F} {-gb DUMP | -ib F} [-L LOWER] [-U UPPER] -o OUT
     kmer_table compare -k K {-ga DUMP | -ia F} {-gb DUMP | -ib F}      (one JSON line on stdout)
+    kmer_table depth {-i F | -1 F -2 F | -g DUMP} -k K -s SEQS.fa[.gz] [-L LOWER] -o OUT.tsv
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -162,11 +163,16 @@ def main_kmer_table(argv=None) -> int:
     -- met by ``--op`` (``KmerTable.combined``: min, max, diff = counts subtracted, left = A's counts of the shared k-mers, only =
     A's k-mers that B lacks), kept where LOWER <= count <= UPPER and written as ``kmer_table dump`` writes a table.  ``kmer_table
     compare``: one JSON line of ``KmerTable.compare`` on the same two inputs.  ``kmer_table dump -U UPPER`` writes only the
-    entries of count <= UPPER (``KmerTable.filtered``); without ``-U`` nothing about ``dump`` changes.  Exit status 0, or 1 with a
-    message on stderr, as ``main_count_kmer``."""
+    entries of count <= UPPER (``KmerTable.filtered``); without ``-U`` nothing about ``dump`` changes.  ``kmer_table depth``: how
+    deep the table covers each sequence of the FASTA file ``-s`` (``ReadStream.from_fasta``, ``KmerTable.depth``; lower-case
+    bases are bases, as to ``jellyfish query -s``), one tab-separated line ``name  length  kmers  present  mean  median  max``
+    per sequence in file order -- its k-mers, those whose count is at least LOWER, and mean (``%.3f`` of sum / kmers, 0.000
+    without k-mers), lower median and maximum of the counts, a count below LOWER taken as 0.  The table comes from exactly one
+    of ``-i``, ``-1``/``-2`` and ``-g``.  A k-mer depth beside the alignment depth of scripts/bin_assembly.sh:43, not that number.
+    Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
     p = _Parser(prog="kmer_table")
     sub = p.add_subparsers(dest="cmd", required=True)
-    for name in ("histo", "query", "dump"):
+    for name in ("histo", "query", "dump", "depth"):
         q = sub.add_parser(name)
         q.add_argument("-1", "--reads1", default="")
         q.add_argument("-2", "--reads2", default="")
@@ -180,6 +186,10 @@ def main_kmer_table(argv=None) -> int:
         elif name == "dump":
             q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
             q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
+            q.add_argument("-o", "--output", required=True)
+        elif name == "depth":
+            q.add_argument("-s", "--sequences", required=True)
+            q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
             q.add_argument("-o", "--output", required=True)
         else:
             q.add_argument("-q", "--queries", default="")
@@ -243,7 +253,22 @@ def main_kmer_table(argv=None) -> int:
             raise ValueError("no input: -i F, -1 F -2 F or -g DUMP is needed")
         if not 1 <= a.kmer <= _lib.WIDE_MAX_K:
             raise ValueError(f"k-mer size {a.kmer} unsupported (1..{_lib.WIDE_MAX_K})")
-        if a.cmd == "histo":
+        if a.cmd == "depth":
+            if sum((bool(a.global_), bool(a.interleaved), bool(a.reads1 or a.reads2))) != 1:
+                raise ValueError("depth takes the table from one source: -i F, -1 F -2 F or -g DUMP")
+            if a.lower < 1:
+                raise ValueError(f"-L must be at least 1 (got {a.lower})")
+            if not os.path.isfile(a.sequences):
+                raise ValueError(f"{a.sequences}: no such sequence file")
+            from .reads import ReadStream
+            table = _table_for(a)
+            seqs = ReadStream.from_fasta(a.sequences, device=table.device)
+            d = table.depth(seqs, lower=a.lower).cpu().numpy()
+            lengths = np.diff(seqs.run_off) - 1              # (every run ends with the one 'N' that from_fasta appends)
+            with open(a.output, "w") as f:
+                f.writelines(f"{name}\t{int(n)}\t{int(r[0])}\t{int(r[1])}\t{(int(r[2]) / int(r[0]) if r[0] else 0.0):.3f}\t{int(r[4])}\t{int(r[3])}\n"
+                             for name, n, r in zip(seqs.run_names, lengths, d))
+        elif a.cmd == "histo":
             if not 1 <= a.high <= _lib.SPECTRUM_MAX_HIGH:
                 raise ValueError(f"--high must lie in [1, {_lib.SPECTRUM_MAX_HIGH}]")
             hist = _table_for(a).spectrum(a.high)

@@ -2549,6 +2549,380 @@ __global__ __launch_bounds__(BLOCK) void features_kernel(const uint64_t *__restr
     }
 }
 
+// -------------------------------------------------------------------------------- depth of sequences in a finished table
+//
+// What `jellyfish query -s FILE` answers (the multiplicity of every k-mer of a sequence; feature.py:87's table) and the per-range
+// numbers that stand beside the reference's contig depth (scripts/bin_assembly.sh:43, cut at scripts/low_abd_reads.sh:10).  The
+// table is only read: plain loads, no atomics on it.
+//
+// One LANE per stream position here, not one lane per word as in the counting kernels: a lane takes the k characters that start
+// at its position straight out of the one or two stream words that hold them (k <= 31), so a range of 150 characters keeps 130
+// lanes busy instead of 5, nothing is pre-rolled, and the answers of a wavefront are 64 consecutive words.  The stream words are
+// read 32 times over, from L1.
+
+// the canonical k-mer that starts at character i; false where one of its characters is not set in `valid`.  The caller has made
+// sure that 0 <= i and i + k <= n_chars: the second word is read only when the k-mer reaches into it.
+__device__ __forceinline__ bool kmer_at(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid, int64_t i, int k, uint64_t kmask,
+                                        uint64_t *canon)
+{
+    const int64_t w = i >> 5;
+    const int s = (int)(i & 31);
+    uint64_t c = codes[w] >> (2 * s), v = valid[w] >> s;
+    if (s + k > 32) {                                      // (then s >= 2: both shifts below are in range)
+        c |= codes[w + 1] << (64 - 2 * s);
+        v |= (uint64_t)valid[w + 1] << (32 - s);
+    }
+    const uint64_t vm = (1ull << k) - 1;
+    if ((v & vm) != vm) return false;
+    c &= kmask;
+    // the stream keeps the OLDEST character lowest, a code the newest: the forward code is the window reversed, the reverse
+    // complement (Roller::rc: complement = ^ 2, order reversed) is the window complemented
+    const uint64_t fw = rev2_64(c) >> (64 - 2 * k), rc = (c ^ 0xAAAAAAAAAAAAAAAAull) & kmask;
+    *canon = fw < rc ? fw : rc;
+    return true;
+}
+
+// one lookup in two halves, so that a lane issues the first probes of a batch before it resolves any (table_query_kernel)
+struct DepthProbe {
+    uint64_t key, hh, cur;
+};
+template <int TK>
+__device__ __forceinline__ void depth_issue(DepthProbe &p, uint64_t canon, int k, const uint32_t *__restrict__ dense, const HashView &t)
+{
+    if (TK == TK_DENSE) {
+        p.cur = dense[(uint32_t)canon];
+        return;
+    }
+    p.key = TK == TK_HASH ? key42(canon) : canon;
+    p.hh = TK == TK_WIDE ? t.home_wide(canon) : (TK == TK_MINI || TK == TK_MINIW) ? t.home_mini(canon, k) : t.home_key(p.key);
+    p.cur = t.slots[p.hh];
+}
+template <int TK> __device__ __forceinline__ uint32_t depth_resolve(const DepthProbe &p, const HashView &t)
+{
+    bool found;
+    if (TK == TK_DENSE) return (uint32_t)p.cur;
+    if (TK == TK_WIDE || TK == TK_MINIW) return wide_probe(t, p.hh, p.cur, p.key, &found);
+    return hash_probe(t, p.hh, p.cur, p.key, &found);
+}
+
+constexpr int DEPTH_BATCH = 8;              // lookups a lane has in flight
+static_assert(PG_DEPTH_SHORT_MAX == 64 * DEPTH_BATCH, "a short range is one batch of one wavefront");
+
+// out[g] = count of the k-mer that starts at character begin + g, PG_PROFILE_NONE where none does (g < n; the launcher has
+// checked 0 <= begin and begin + n <= n_chars)
+template <int TK>
+__device__ __forceinline__ void profile_span(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid, int64_t n_chars,
+                                             int64_t begin, int64_t n, int64_t g_first, int64_t stride, int k, const uint32_t *__restrict__ dense,
+                                             const HashView &t, uint32_t *__restrict__ out)
+{
+    const uint64_t kmask = low_mask<uint64_t>(k);
+    for (int64_t g0 = g_first; g0 < n; g0 += stride * DEPTH_BATCH) {
+        DepthProbe p[DEPTH_BATCH];
+        bool ask[DEPTH_BATCH];
+#pragma unroll
+        for (int u = 0; u < DEPTH_BATCH; ++u) {
+            const int64_t g = g0 + u * stride, i = begin + g;
+            uint64_t canon = 0;
+            p[u].key = p[u].hh = p[u].cur = 0;
+            ask[u] = g < n && i + k <= n_chars && kmer_at(codes, valid, i, k, kmask, &canon);
+            if (ask[u]) depth_issue<TK>(p[u], canon, k, dense, t);
+        }
+#pragma unroll
+        for (int u = 0; u < DEPTH_BATCH; ++u) {
+            const int64_t g = g0 + u * stride;
+            if (g < n) out[g] = ask[u] ? depth_resolve<TK>(p[u], t) : PG_PROFILE_NONE;
+        }
+    }
+}
+
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void table_profile_kernel(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid, int64_t n_chars,
+                                                              int64_t begin, int64_t n, int k, const uint32_t *__restrict__ dense, HashView t,
+                                                              uint32_t *__restrict__ out)
+{
+    profile_span<TK>(codes, valid, n_chars, begin, n, (int64_t)blockIdx.x * BLOCK + threadIdx.x, (int64_t)gridDim.x * BLOCK, k, dense, t, out);
+}
+
+// A LONG range (more than PG_DEPTH_SHORT_MAX characters after clipping) as the workspace lists it: its n = length - k + 1
+// positions keep their counts in words [off, off + n) of the workspace's count area.  The list grows DOWN from the end of the
+// workspace, the counts grow UP from behind the head, and one 64-bit word of the head holds both cursors -- entries in its top
+// DEPTH_LIST_BITS bits, count words below --, so ONE atomic add hands out both and entry e's words lie behind entry e - 1's: the
+// list is sorted by `off`, whatever order the wavefronts arrive in.  (An add, not a compare-and-swap: 12 000 wavefronts that
+// retry on one word took 85 ms to list 12 000 ranges.)  A range whose entry or words would not fit writes neither and sets
+// PG_STATUS_DEPTH_WORKSPACE; the cursors have moved all the same, so the list then has a hole, and the two kernels of the long
+// form do NOTHING once that bit is set.  (Which entry a range becomes depends on the order of arrival; its results do not.)
+struct DepthLong {
+    int64_t range, start, off, n;
+};
+constexpr int DEPTH_LIST_BITS = 24, DEPTH_OFF_BITS = 64 - DEPTH_LIST_BITS;
+constexpr uint64_t DEPTH_OFF_MASK = (1ull << DEPTH_OFF_BITS) - 1;
+constexpr int64_t DEPTH_HEAD_BYTES = 256;
+__device__ __forceinline__ const DepthLong *depth_entry(const void *ws, int64_t ws_bytes, uint64_t e)
+{
+    return reinterpret_cast<const DepthLong *>((const char *)ws + ws_bytes) - 1 - e;
+}
+
+// SHORT form: one wavefront per range, grid-stride.  The lane's up to DEPTH_BATCH values stay in registers; the five results
+// come from ballots and wavefront reductions, the lower median from a search over the bits of the value (how many values lie
+// below the candidate: one ballot per register and bit).  40 bytes leave per range, nothing else.  A long range is only entered
+// in the workspace's list here.
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void depth_short_kernel(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid, int64_t n_chars,
+                                                            const int64_t *__restrict__ range_start, const int64_t *__restrict__ range_end,
+                                                            int64_t n_ranges, int k, uint64_t lower, const uint32_t *__restrict__ dense, HashView t,
+                                                            long long *__restrict__ out, void *ws, int64_t ws_bytes, uint32_t *status)
+{
+    const int lane = threadIdx.x & 63;
+    const uint64_t kmask = low_mask<uint64_t>(k);
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES;
+    for (int64_t r = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); r < n_ranges; r += n_waves) {
+        int64_t a = range_start[r], b = range_end[r];
+        a = a < 0 ? 0 : a > n_chars ? n_chars : a;          // (outside the contract: clipped, so that nothing outside the stream is read)
+        b = b < 0 ? 0 : b > n_chars ? n_chars : b;
+        const int64_t n_pos = b - a >= k ? b - a - k + 1 : 0;
+        long long *o = out + 5 * r;
+        if (b - a > PG_DEPTH_SHORT_MAX) {
+            if (lane == 0) {
+                const unsigned long long old = atomicAdd((unsigned long long *)ws, (1ull << DEPTH_OFF_BITS) | (unsigned long long)n_pos);
+                const uint64_t e = old >> DEPTH_OFF_BITS, off = old & DEPTH_OFF_MASK;
+                // (n_pos <= n_chars < 2^37: the sum below cannot wrap.  Cursors that have run over their fields -- more than
+                // 2^24 entries or 2^40 words asked for -- have failed this test on the way there, and the bit stays set.)
+                if (e + 1 < (1ull << DEPTH_LIST_BITS) && off + (uint64_t)n_pos <= DEPTH_OFF_MASK &&
+                    (uint64_t)DEPTH_HEAD_BYTES + 4 * (off + (uint64_t)n_pos) + sizeof(DepthLong) * (e + 1) <= (uint64_t)ws_bytes) {
+                    DepthLong *d = const_cast<DepthLong *>(depth_entry(ws, ws_bytes, e));
+                    d->range = r; d->start = a; d->off = (int64_t)off; d->n = n_pos;
+                } else {
+                    atomicOr(status, PG_STATUS_DEPTH_WORKSPACE);
+                    o[0] = o[1] = o[2] = o[3] = o[4] = 0;
+                }
+            }
+            continue;
+        }
+        uint32_t val[DEPTH_BATCH];
+        DepthProbe p[DEPTH_BATCH];
+        bool have[DEPTH_BATCH];
+#pragma unroll
+        for (int u = 0; u < DEPTH_BATCH; ++u) {
+            const int64_t g = lane + 64 * u;
+            uint64_t canon = 0;
+            p[u].key = p[u].hh = p[u].cur = 0;
+            have[u] = g < n_pos && kmer_at(codes, valid, a + g, k, kmask, &canon);
+            if (have[u]) depth_issue<TK>(p[u], canon, k, dense, t);
+        }
+        uint32_t n = 0, present = 0, vmax = 0;
+        unsigned long long sum = 0;
+#pragma unroll
+        for (int u = 0; u < DEPTH_BATCH; ++u) {
+            uint32_t c = have[u] ? depth_resolve<TK>(p[u], t) : 0u;
+            if (c < lower) c = 0;
+            val[u] = c;
+            n += (uint32_t)__popcll(__ballot(have[u]));
+            present += (uint32_t)__popcll(__ballot(c > 0));
+            sum += c;
+            vmax = c > vmax ? c : vmax;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            sum += __shfl_xor(sum, d);
+            const uint32_t m = __shfl_xor(vmax, d);
+            vmax = m > vmax ? m : vmax;
+        }
+        // the value at sorted index (n - 1) / 2: the largest x with fewer than (n - 1) / 2 + 1 values below it
+        uint32_t median = 0;
+        if (vmax) {
+            const uint32_t mid = (n - 1) / 2;
+            for (int bit = 31 - __clz((int)vmax); bit >= 0; --bit) {
+                const uint32_t cand = median | (1u << bit);
+                uint32_t below = 0;
+#pragma unroll
+                for (int u = 0; u < DEPTH_BATCH; ++u) below += (uint32_t)__popcll(__ballot(have[u] && val[u] < cand));
+                if (below <= mid) median = cand;
+            }
+        }
+        if (lane == 0) {
+            o[0] = n; o[1] = present; o[2] = (long long)sum; o[3] = vmax; o[4] = median;
+        }
+    }
+}
+
+// LONG form, first half: the counts of every listed range go to the workspace once, 4 bytes per position (PG_PROFILE_NONE where
+// no k-mer starts).  The count words of all ranges are one flat array; a workgroup takes tiles of it, finds the entry its tile
+// begins in (a search over the sorted list, the same for every lane) and walks on from there -- a long range has hundreds of
+// positions, so a tile meets a handful.
+constexpr int64_t DEPTH_TILE = (int64_t)BLOCK * DEPTH_BATCH;
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void depth_fill_kernel(const uint64_t *__restrict__ codes, const uint32_t *__restrict__ valid, int64_t n_chars,
+                                                           const void *ws, int64_t ws_bytes, int k, const uint32_t *__restrict__ dense, HashView t,
+                                                           const uint32_t *status)
+{
+    if (*status & PG_STATUS_DEPTH_WORKSPACE) return;        // (the list has a hole: depth_short_kernel)
+    const unsigned long long head = *(const unsigned long long *)ws;
+    const int64_t n_long = (int64_t)(head >> DEPTH_OFF_BITS), total = (int64_t)(head & DEPTH_OFF_MASK);
+    uint32_t *counts = (uint32_t *)((char *)const_cast<void *>(ws) + DEPTH_HEAD_BYTES);
+    const uint64_t kmask = low_mask<uint64_t>(k);
+    for (int64_t t0 = (int64_t)blockIdx.x * DEPTH_TILE; t0 < total; t0 += (int64_t)gridDim.x * DEPTH_TILE) {
+        int64_t lo = 0, hi = n_long - 1;                    // the last entry whose off <= t0
+        while (lo < hi) {
+            const int64_t mid = (lo + hi + 1) >> 1;
+            if (depth_entry(ws, ws_bytes, (uint64_t)mid)->off <= t0) lo = mid;
+            else hi = mid - 1;
+        }
+        DepthProbe p[DEPTH_BATCH];
+        bool ask[DEPTH_BATCH];
+        int64_t e = lo;
+        DepthLong d = *depth_entry(ws, ws_bytes, (uint64_t)e);
+#pragma unroll
+        for (int u = 0; u < DEPTH_BATCH; ++u) {
+            const int64_t g = t0 + u * BLOCK + threadIdx.x;
+            uint64_t canon = 0;
+            p[u].key = p[u].hh = p[u].cur = 0;
+            ask[u] = false;
+            if (g >= total) continue;
+            while (g >= d.off + d.n) d = *depth_entry(ws, ws_bytes, (uint64_t)++e);
+            const int64_t i = d.start + (g - d.off);
+            ask[u] = i >= 0 && i + k <= n_chars && kmer_at(codes, valid, i, k, kmask, &canon);
+            if (ask[u]) depth_issue<TK>(p[u], canon, k, dense, t);
+        }
+#pragma unroll
+        for (int u = 0; u < DEPTH_BATCH; ++u) {
+            const int64_t g = t0 + u * BLOCK + threadIdx.x;
+            if (g < total) counts[g] = ask[u] ? depth_resolve<TK>(p[u], t) : PG_PROFILE_NONE;
+        }
+    }
+}
+
+// LONG form, second half: one workgroup per listed range reads the range's words -- once for n_kmers, n_present, sum and max,
+// then once per digit of the value for the lower median: a radix select from the top, DEPTH_DIGIT_BITS bits at a time with a
+// histogram in LDS, keeping only the values that agree with the digits already chosen.  Digits above the maximum are all zero
+// and take no pass: packed tables (counts <= PG_HASH_COUNT_SAT = 2^21) need two at most, spectra of real reads one.  64-bit
+// bins (16 KiB of LDS): a range may have more than 2^32 positions.  A lane gathers equal digits that follow each other before
+// it adds to LDS -- most values of a real range are 0 or one small number, and 64 lanes adding to one bin take turns.
+constexpr int DEPTH_DIGIT_BITS = 11, DEPTH_BINS = 1 << DEPTH_DIGIT_BITS;
+static_assert(DEPTH_BINS % 64 == 0, "wavefront 0 scans the bins, a whole number per lane");
+
+__device__ __forceinline__ unsigned long long depth_block_sum(unsigned long long v, unsigned long long *part)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long s = 0;
+#pragma unroll
+    for (int w = 0; w < BIG_BLOCK / 64; ++w) s += part[w];
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ unsigned long long depth_block_max(unsigned long long v, unsigned long long *part)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d);
+        v = o > v ? o : v;
+    }
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long s = 0;
+#pragma unroll
+    for (int w = 0; w < BIG_BLOCK / 64; ++w) s = part[w] > s ? part[w] : s;
+    __syncthreads();
+    return s;
+}
+
+__global__ __launch_bounds__(BIG_BLOCK) void depth_select_kernel(const void *ws, int64_t ws_bytes, uint64_t lower, long long *__restrict__ out,
+                                                                 const uint32_t *status)
+{
+    __shared__ unsigned long long hist[DEPTH_BINS];
+    __shared__ unsigned long long part[BIG_BLOCK / 64];
+    __shared__ unsigned long long chosen[2];                // the digit wavefront 0 chose, and the rank left inside its bin
+    if (*status & PG_STATUS_DEPTH_WORKSPACE) return;        // (the list has a hole: depth_short_kernel)
+    const unsigned long long head = *(const unsigned long long *)ws;
+    const int64_t n_long = (int64_t)(head >> DEPTH_OFF_BITS);
+    const uint32_t *counts = (const uint32_t *)((const char *)ws + DEPTH_HEAD_BYTES);
+    const int lane = threadIdx.x & 63;
+    for (int64_t e = blockIdx.x; e < n_long; e += gridDim.x) {
+        const DepthLong d = *depth_entry(ws, ws_bytes, (uint64_t)e);
+        const uint32_t *v = counts + d.off;
+        unsigned long long n = 0, present = 0, sum = 0, vmax = 0;
+        for (int64_t i0 = threadIdx.x; i0 < d.n; i0 += (int64_t)BIG_BLOCK * DEPTH_BATCH) {
+            uint32_t c[DEPTH_BATCH];                         // (all loads of the batch first: one in flight per lane read 8 GB/s)
+#pragma unroll
+            for (int u = 0; u < DEPTH_BATCH; ++u) c[u] = i0 + u * BIG_BLOCK < d.n ? v[i0 + u * BIG_BLOCK] : PG_PROFILE_NONE;
+#pragma unroll
+            for (int u = 0; u < DEPTH_BATCH; ++u) {
+                if (c[u] == PG_PROFILE_NONE) continue;
+                if (c[u] < lower) c[u] = 0;
+                ++n;
+                present += c[u] > 0;
+                sum += c[u];
+                vmax = c[u] > vmax ? c[u] : vmax;
+            }
+        }
+        n = depth_block_sum(n, part);
+        present = depth_block_sum(present, part);
+        sum = depth_block_sum(sum, part);
+        vmax = depth_block_max(vmax, part);
+        uint32_t prefix = 0, known = 0;                      // the median's digits chosen so far, and the mask of their bits
+        unsigned long long rank = n ? (n - 1) / 2 : 0;
+#pragma unroll 1
+        for (int shift = 2 * DEPTH_DIGIT_BITS; shift >= 0 && vmax; shift -= DEPTH_DIGIT_BITS) {
+            if ((vmax >> shift) == 0) continue;              // (every value has 0 in this digit and above)
+            for (int i = threadIdx.x; i < DEPTH_BINS; i += BIG_BLOCK) hist[i] = 0;
+            __syncthreads();
+            uint32_t run_digit = 0;
+            unsigned long long run = 0;
+            for (int64_t i0 = threadIdx.x; i0 < d.n; i0 += (int64_t)BIG_BLOCK * DEPTH_BATCH) {
+                uint32_t c[DEPTH_BATCH];
+#pragma unroll
+                for (int u = 0; u < DEPTH_BATCH; ++u) c[u] = i0 + u * BIG_BLOCK < d.n ? v[i0 + u * BIG_BLOCK] : PG_PROFILE_NONE;
+#pragma unroll
+                for (int u = 0; u < DEPTH_BATCH; ++u) {
+                    if (c[u] == PG_PROFILE_NONE) continue;
+                    if (c[u] < lower) c[u] = 0;
+                    if ((c[u] & known) != prefix) continue;
+                    const uint32_t digit = (c[u] >> shift) & (DEPTH_BINS - 1);
+                    if (digit != run_digit) {
+                        if (run) atomicAdd(&hist[run_digit], run);
+                        run_digit = digit;
+                        run = 0;
+                    }
+                    ++run;
+                }
+            }
+            if (run) atomicAdd(&hist[run_digit], run);
+            __syncthreads();
+            if (threadIdx.x < 64) {
+                constexpr int PER = DEPTH_BINS / 64;
+                unsigned long long mine = 0;
+#pragma unroll 1
+                for (int j = 0; j < PER; ++j) mine += hist[lane * PER + j];
+                unsigned long long incl = mine;
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1) {
+                    const unsigned long long o = __shfl_up(incl, s);
+                    if (lane >= s) incl += o;
+                }
+                unsigned long long before = incl - mine;
+                if (before <= rank && rank < incl) {         // exactly one lane: rank < the values that take part
+                    int j = 0;
+#pragma unroll 1
+                    for (; j < PER - 1 && before + hist[lane * PER + j] <= rank; ++j) before += hist[lane * PER + j];
+                    chosen[0] = (unsigned long long)(lane * PER + j);
+                    chosen[1] = rank - before;
+                }
+            }
+            __syncthreads();
+            prefix |= (uint32_t)chosen[0] << shift;
+            known |= (uint32_t)(DEPTH_BINS - 1) << shift;
+            rank = chosen[1];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            long long *o = out + 5 * d.range;
+            o[0] = (long long)n; o[1] = (long long)present; o[2] = (long long)sum; o[3] = (long long)vmax; o[4] = (long long)prefix;
+        }
+    }
+}
+
 // -------------------------------------------------------------------------------- launch helpers
 int check_table(const pg_table *t)
 {
@@ -3154,6 +3528,102 @@ extern "C" int pg_table_spectrum(const pg_table *t, int high, uint64_t *hist, vo
 #undef PG_LAUNCH_FORM
 #undef PG_LAUNCH
     return check_launch("pg_table_spectrum");
+}
+
+// ---- depth of sequences in a finished table (kernels: "depth of sequences" above)
+extern "C" int pg_table_profile(const pg_table *t, const uint64_t *codes, const uint32_t *valid, int64_t n_chars, int64_t char_begin,
+                                int64_t char_end, uint32_t *counts, void *stream)
+{
+    if (!t) return pg_fail(PG_EINVAL, "pg_table_profile: t is null");
+    if (!codes || !valid) return pg_fail(PG_EINVAL, "pg_table_profile: the stream is null");
+    if (!counts) return pg_fail(PG_EINVAL, "pg_table_profile: counts is null");
+    if (n_chars < 0) return pg_fail(PG_EINVAL, "pg_table_profile: n_chars is negative (%lld)", (long long)n_chars);
+    if (char_begin < 0 || char_end < char_begin || char_end > n_chars)
+        return pg_fail(PG_EINVAL, "pg_table_profile: range [%lld, %lld) outside the stream's %lld characters", (long long)char_begin,
+                       (long long)char_end, (long long)n_chars);
+    int rc = check_table(t);
+    if (rc) return rc;
+    const int64_t n = char_end - char_begin;
+    if (n == 0) return PG_OK;
+    const int grid = grid_for((n + DEPTH_BATCH - 1) / DEPTH_BATCH);
+    const HashView v = t->kind == PG_TABLE_DENSE ? HashView{nullptr, 0, 0} : view_of(t);
+    const uint32_t *dense = t->kind == PG_TABLE_DENSE ? (const uint32_t *)t->data : nullptr;
+#define PG_LAUNCH(TK)                                                                                                          \
+    hipLaunchKernelGGL((table_profile_kernel<TK>), dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, codes, valid, n_chars, char_begin, n, \
+                       t->k, dense, v, counts)
+    switch (t->kind) {
+    case PG_TABLE_DENSE: PG_LAUNCH(TK_DENSE); break;
+    case PG_TABLE_HASH: PG_LAUNCH(TK_HASH); break;
+    case PG_TABLE_WIDE: PG_LAUNCH(TK_WIDE); break;
+    case PG_TABLE_MINI: PG_LAUNCH(TK_MINI); break;
+    default: PG_LAUNCH(TK_MINIW); break;
+    }
+#undef PG_LAUNCH
+    return check_launch("pg_table_profile");
+}
+
+extern "C" int64_t pg_table_depth_workspace_bytes(int64_t n_long, int64_t long_positions)
+{
+    if (n_long < 0 || long_positions < 0) return pg_fail(PG_EINVAL, "pg_table_depth_workspace_bytes: negative size");
+    if (n_long > PG_DEPTH_MAX_LONG) return pg_fail(PG_EINVAL, "pg_table_depth_workspace_bytes: more than %d long ranges in one call", PG_DEPTH_MAX_LONG);
+    if (long_positions > (int64_t)(DEPTH_OFF_MASK >> 3)) return pg_fail(PG_EINVAL, "pg_table_depth_workspace_bytes: too many positions");
+    const int64_t body = 4 * long_positions + (int64_t)sizeof(DepthLong) * n_long;
+    return DEPTH_HEAD_BYTES + (body + 255) / 256 * 256;
+}
+
+extern "C" int pg_table_depth(const pg_table *t, const uint64_t *codes, const uint32_t *valid, int64_t n_chars, const int64_t *range_start,
+                              const int64_t *range_end, int64_t n_ranges, int64_t lower, int64_t *out, void *workspace,
+                              int64_t workspace_bytes, uint32_t *status, void *stream)
+{
+    if (!t) return pg_fail(PG_EINVAL, "pg_table_depth: t is null");
+    if (!codes || !valid) return pg_fail(PG_EINVAL, "pg_table_depth: the stream is null");
+    if (n_chars < 0) return pg_fail(PG_EINVAL, "pg_table_depth: n_chars is negative (%lld)", (long long)n_chars);
+    if (n_chars > (int64_t)(DEPTH_OFF_MASK >> 3)) return pg_fail(PG_EINVAL, "pg_table_depth: a stream of %lld characters is too long", (long long)n_chars);
+    if (n_ranges < 0) return pg_fail(PG_EINVAL, "pg_table_depth: n_ranges is negative (%lld)", (long long)n_ranges);
+    if (n_ranges > 0 && (!range_start || !range_end)) return pg_fail(PG_EINVAL, "pg_table_depth: the range arrays are null");
+    if (n_ranges > 0 && !out) return pg_fail(PG_EINVAL, "pg_table_depth: out is null");
+    if (lower < 1) return pg_fail(PG_EINVAL, "pg_table_depth: lower must be at least 1 (got %lld)", (long long)lower);
+    if (!workspace) return pg_fail(PG_EINVAL, "pg_table_depth: workspace is null");
+    if ((uintptr_t)workspace & 255) return pg_fail(PG_EINVAL, "pg_table_depth: workspace is not 256-byte aligned");
+    if (workspace_bytes < DEPTH_HEAD_BYTES)
+        return pg_fail(PG_EINVAL, "pg_table_depth: workspace of %lld bytes is smaller than the %lld every call needs", (long long)workspace_bytes,
+                       (long long)DEPTH_HEAD_BYTES);
+    if (!status) return pg_fail(PG_EINVAL, "pg_table_depth: status is null");
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (n_ranges == 0) return PG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t ws_bytes = workspace_bytes & ~(int64_t)255;      // (the list of long ranges hangs from the end: keep it aligned)
+    if (hipMemsetAsync(workspace, 0, (size_t)DEPTH_HEAD_BYTES, s) != hipSuccess) return pg_fail(PG_EHIP, "pg_table_depth: cannot clear the workspace's head");
+    const HashView v = t->kind == PG_TABLE_DENSE ? HashView{nullptr, 0, 0} : view_of(t);
+    const uint32_t *dense = t->kind == PG_TABLE_DENSE ? (const uint32_t *)t->data : nullptr;
+    const int grid = grid_for(n_ranges, WAVES);
+    // room for one long range at least?  (a caller whose ranges are all short gives the head alone: two launches less)
+    const int64_t room = (ws_bytes - DEPTH_HEAD_BYTES) / 4;
+    const bool any_long = ws_bytes - DEPTH_HEAD_BYTES >= (int64_t)sizeof(DepthLong) + 4 * (PG_DEPTH_SHORT_MAX + 2 - PG_WIDE_MAX_K);
+    const int fill_grid = grid_for((room + DEPTH_BATCH - 1) / DEPTH_BATCH);
+    int64_t select_grid = (ws_bytes - DEPTH_HEAD_BYTES) / ((int64_t)sizeof(DepthLong) + 4 * (PG_DEPTH_SHORT_MAX + 2 - PG_WIDE_MAX_K));
+    if (select_grid > 2048) select_grid = 2048;
+#define PG_LAUNCH(TK)                                                                                                          \
+    do {                                                                                                                       \
+        hipLaunchKernelGGL((depth_short_kernel<TK>), dim3(grid), dim3(BLOCK), 0, s, codes, valid, n_chars, range_start, range_end, n_ranges, \
+                           t->k, (uint64_t)lower, dense, v, (long long *)out, workspace, ws_bytes, status);                    \
+        if (any_long)                                                                                                          \
+            hipLaunchKernelGGL((depth_fill_kernel<TK>), dim3(fill_grid), dim3(BLOCK), 0, s, codes, valid, n_chars, (const void *)workspace, \
+                               ws_bytes, t->k, dense, v, (const uint32_t *)status);                                            \
+    } while (0)
+    switch (t->kind) {
+    case PG_TABLE_DENSE: PG_LAUNCH(TK_DENSE); break;
+    case PG_TABLE_HASH: PG_LAUNCH(TK_HASH); break;
+    case PG_TABLE_WIDE: PG_LAUNCH(TK_WIDE); break;
+    case PG_TABLE_MINI: PG_LAUNCH(TK_MINI); break;
+    default: PG_LAUNCH(TK_MINIW); break;
+    }
+#undef PG_LAUNCH
+    if (any_long)
+        hipLaunchKernelGGL(depth_select_kernel, dim3((unsigned)select_grid), dim3(BIG_BLOCK), 0, s, (const void *)workspace, ws_bytes,
+                           (uint64_t)lower, (long long *)out, (const uint32_t *)status);
+    return check_launch("pg_table_depth");
 }
 
 // the table as the dump kernels see it: form, entries, the counts plane of the planes form

@@ -124,6 +124,7 @@ class KmerTable:
         self.merge_form = None           # "aligned" / "general": which kernel built a table that ``merged`` returned
         self.combine_form = None         # "aligned" / "general": which kernel built a table that ``combined`` / ``filtered`` returned
         self.rows_form = None            # "find" / "lookup": how the last ``abundance_of`` built its rows
+        self._depth_ws = None            # the workspace of ``depth``: the counts of its long ranges
 
     # ------------------------------------------------------------------ construction
 
@@ -1083,7 +1084,7 @@ class KmerTable:
         """give the scratch of the counting pipelines back (record buffers, word buffers, plans: tens of GB at BASELINE sizes); the
         table keeps its counts, the next count allocates again"""
         self._workspace = self._shuffle_ws = self._mini_rec_ws = self._mini_spare = None
-        self._merge_ws = self._half_ws = None
+        self._merge_ws = self._half_ws = self._depth_ws = None
         self._mini_plan = self._mini_next = None
         self._mini_sized_for = self._mini_optimistic = None
         self._records = self._emitted = self._half = None
@@ -1398,6 +1399,104 @@ class KmerTable:
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().pg_table_spectrum(self.desc(), high, hist.data_ptr(), _stream_ptr(self.device)))
         return hist.cpu().numpy()
+
+    # ------------------------------------------------------------------ depth of sequences (jellyfish query -s; contig depth)
+
+    def _plane_for(self, stream: ReadStream, plane) -> torch.Tensor:
+        """the validity plane a profile reads the stream with (None: jellyfish's view of a sequence, lower-case bases count)"""
+        self._require_readable()
+        _require_gpu(stream.codes, "the read stream")
+        if stream.device != self.device:
+            raise ValueError("stream and table are on different devices")
+        plane = stream.lenient_valid() if plane is None else plane
+        if plane.dtype != torch.int32 or plane.device != self.device or plane.numel() != stream.n_words:
+            raise ValueError(f"plane must be an int32 tensor of the stream's {stream.n_words} words on {self.device}")
+        return plane.contiguous()
+
+    def profile(self, stream: ReadStream, start: int = 0, end: int | None = None, plane: torch.Tensor | None = None) -> torch.Tensor:
+        """the table's count of the k-mer that starts at each character of ``[start, end)`` of ``stream`` (``jellyfish query -s``
+        on the table of src/feature.py:87): int64 on the table's device, 0 for a k-mer the table lacks, -1 where no k-mer
+        starts -- one of the k characters is not a base under ``plane``, or fewer than k characters are left in the stream.
+        ``plane``: a validity plane of the stream (``stream.valid``: the strict rule); None: ``stream.lenient_valid()``.  The
+        table is only read (pg_table_profile)."""
+        plane = self._plane_for(stream, plane)
+        start, end = int(start), stream.n_chars if end is None else int(end)
+        if not 0 <= start <= end <= stream.n_chars:
+            raise ValueError(f"[{start}, {end}) is no range of the stream's {stream.n_chars} characters")
+        if end == start:
+            return torch.zeros(0, dtype=torch.int64, device=self.device)
+        out = torch.empty(end - start, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().pg_table_profile(self.desc(), stream.codes.data_ptr(), plane.data_ptr(), stream.n_chars, start, end,
+                                                    out.data_ptr(), _stream_ptr(self.device)))
+        return torch.where(out == -1, -1, out.to(torch.int64) & 0xFFFFFFFF)      # (-1 as int32: PG_PROFILE_NONE)
+
+    def depth(self, stream: ReadStream, ranges=None, lower: int = 1, plane: torch.Tensor | None = None) -> torch.Tensor:
+        """how deep the table covers character ranges of ``stream``: int64 [n, 5] on the table's device, per range the columns
+        ``_lib.DEPTH_N_KMERS`` (k-mers that lie inside the range), ``DEPTH_N_PRESENT`` (those with a value above 0), ``DEPTH_SUM``,
+        ``DEPTH_MAX`` and ``DEPTH_MEDIAN`` (the lower median, zeros included) of their values -- a k-mer's value is its count in
+        the table where that is at least ``lower``, else 0; all five are 0 for a range without k-mers.  A k-mer depth of contigs
+        against the reads' table is the kind of number scripts/bin_assembly.sh:43 computes by alignment, not that number.
+
+        ``ranges``: a ``(start, end)`` pair of integer numpy arrays or of int64 tensors on the device (used as they are), a
+        ``Rows``, or None: the stream's own runs.  Ranges are independent -- they may overlap, repeat, be unsorted or empty --
+        but each must lie inside the stream with start <= end, else ValueError before anything is launched (for device tensors
+        that is one reduction and its copy to the host).  ``plane`` as for ``profile``.  The table is only read (pg_table_depth:
+        ranges of at most ``_lib.DEPTH_SHORT_MAX`` characters never leave the registers of a wavefront, longer ones keep 4 bytes
+        per position in a workspace this table holds until ``release_workspaces``)."""
+        plane = self._plane_for(stream, plane)
+        lower = int(lower)
+        if lower < 1:
+            raise ValueError(f"lower must be at least 1 (got {lower})")
+        if ranges is None:
+            ranges = (stream.run_off[:-1], stream.run_off[1:])
+        elif isinstance(ranges, Rows):
+            ranges = (ranges.start, ranges.end)
+        start, end = ranges
+        if isinstance(start, torch.Tensor) or isinstance(end, torch.Tensor):
+            if not (isinstance(start, torch.Tensor) and isinstance(end, torch.Tensor)) or start.dtype != torch.int64 or end.dtype != torch.int64:
+                raise TypeError("range starts and ends must both be int64 tensors (or both numpy arrays)")
+            if start.device != self.device or end.device != self.device:
+                raise ValueError("ranges and table are on different devices")
+            if start.dim() != 1 or start.shape != end.shape:
+                raise ValueError("range starts and ends must be two vectors of one length")
+            start, end = start.contiguous(), end.contiguous()
+            n = int(start.numel())
+            if n:
+                ln = end - start
+                long_ = ln > _lib.DEPTH_SHORT_MAX
+                lo, shortest, hi, n_long, long_pos = torch.stack([start.min(), ln.min(), end.max(), long_.sum(),
+                                                                  torch.where(long_, ln - (self.k - 1), 0).sum()]).tolist()
+        else:
+            a, b = np.asarray(start), np.asarray(end)
+            if a.ndim != 1 or a.shape != b.shape:
+                raise ValueError("range starts and ends must be two vectors of one length")
+            if a.size and (a.dtype.kind not in "iu" or b.dtype.kind not in "iu"):
+                raise TypeError(f"range starts and ends must be integers (got {a.dtype}, {b.dtype})")
+            a, b = a.astype(np.int64), b.astype(np.int64)
+            n = int(a.size)
+            if n:
+                ln = b - a
+                long_ = ln > _lib.DEPTH_SHORT_MAX
+                lo, shortest, hi, n_long, long_pos = int(a.min()), int(ln.min()), int(b.max()), int(long_.sum()), int((ln[long_] - (self.k - 1)).sum())
+                start, end = torch.from_numpy(a).to(self.device), torch.from_numpy(b).to(self.device)
+        if n == 0:
+            return torch.zeros((0, 5), dtype=torch.int64, device=self.device)
+        if lo < 0 or shortest < 0 or hi > stream.n_chars:
+            raise ValueError(f"every range must lie inside the stream's {stream.n_chars} characters with start <= end "
+                             f"(smallest start {lo}, largest end {hi}, shortest length {shortest})")
+        if n_long > _lib.DEPTH_MAX_LONG:
+            raise ValueError(f"{n_long} ranges of more than {_lib.DEPTH_SHORT_MAX} characters: one call takes {_lib.DEPTH_MAX_LONG}")
+        L = _lib.load()
+        ws = self._grown("_depth_ws", _lib.check(L.pg_table_depth_workspace_bytes(n_long, long_pos)), shrink=True)
+        out = torch.empty((n, 5), dtype=torch.int64, device=self.device)
+        status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(L.pg_table_depth(self.desc(), stream.codes.data_ptr(), plane.data_ptr(), stream.n_chars, start.data_ptr(), end.data_ptr(),
+                                        n, lower, out.data_ptr(), ws.data_ptr(), ws.numel(), status.data_ptr(), _stream_ptr(self.device)))
+        if n_long and int(status[0].item()) & _lib.STATUS_DEPTH_WORKSPACE:       # (sized from these very ranges: cannot happen)
+            raise RuntimeError("pg_table_depth: the workspace did not hold the long ranges (PG_STATUS_DEPTH_WORKSPACE)")
+        return out
 
     # ------------------------------------------------------------------ summing finished tables (jellyfish merge)
 

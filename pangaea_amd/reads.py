@@ -327,6 +327,39 @@ class ReadStream:
         return cls(torch.from_numpy(codes), torch.from_numpy(valid), len(text), off, [n for n, _ in runs],
                    valid_lower=torch.from_numpy(lower) if any_lower else None).to(device)
 
+    @staticmethod
+    def parse_fasta(path: str) -> list:
+        """[(name, sequence bytes)] of a FASTA file, gzip or plain: a record starts at a line that begins with ``>``, its name is
+        the first word behind it (none: ""), its sequence the lines up to the next record joined as they are -- case, N and
+        IUPAC letters kept, line ends (LF or CRLF) and blank lines dropped.  A record may be empty; the last line needs no
+        newline.  Text in front of the first ``>`` is no FASTA: ValueError."""
+        import gzip
+        with open(path, "rb") as f:
+            gz = f.read(2) == b"\x1f\x8b"
+        records, name, parts = [], None, []
+        with (gzip.open(path, "rb") if gz else open(path, "rb")) as f:
+            for line in f:
+                line = line.rstrip()
+                if line.startswith(b">"):
+                    if name is not None:
+                        records.append((name, b"".join(parts)))
+                    words = line[1:].split()
+                    name, parts = (words[0].decode(errors="replace") if words else ""), []
+                elif line:
+                    if name is None:
+                        raise ValueError(f"{path}: sequence text in front of the first '>' line")
+                    parts.append(line)
+        if name is not None:
+            records.append((name, b"".join(parts)))
+        return records
+
+    @classmethod
+    def from_fasta(cls, path: str, device: str | torch.device = "cpu") -> "ReadStream":
+        """the sequences of a FASTA file (``parse_fasta``) as a stream: record i is run i, named by the first word of its header --
+        its sequence followed by one 'N', as ``from_runs`` expects, so that no k-mer spans two records.  Lower-case bases go to
+        the lower-case plane (``lenient_valid()`` reads them as bases, as jellyfish does), every other letter is no base."""
+        return cls.from_runs([(name, seq + b"N") for name, seq in cls.parse_fasta(str(path))], device=device)
+
     # ------------------------------------------------------------------ packed-stream cache (SURVEY 8f rank 1)
 
     _MAGIC = b"PGSTRM2\0"
