@@ -2587,9 +2587,7 @@ int check_mini_rows(const pg_rows *rows, const char *who)
     return PG_OK;
 }
 
-// ---- typed dispatch: a runtime value becomes a compile-time tag, and the generic lambda `f` is called with the tag of the one
-// case that applies.  Every helper lists exactly the cases that have kernels: f is instantiated for those and no others.
-template <int N> using int_tag = std::integral_constant<int, N>;
+// ---- typed dispatch (int_tag, with_flag, launch: pg_device.hpp); the helpers below list the cases of this file's kernels
 
 // the first-pass kernels are instantiated per window length (registers of the rolling minimum); k > 21 runs the delayed
 // central window of 8 or 9 M-mers (mini_window).  f(WindowTag<W, DELAY, M>, woff)
@@ -2618,23 +2616,11 @@ template <class F> int with_cap(int cap, F &&f)
     return c == 4 ? f(int_tag<4>{}) : c == 6 ? f(int_tag<6>{}) : c == 8 ? f(int_tag<8>{}) : f(int_tag<9>{});
 }
 
-// the MASKED twin of a kernel or its plain form: f(std::true_type | std::false_type)
-template <class F> int with_flag(bool on, F &&f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
-
 // threads and row-group digits of a lookup workgroup (LookupLds / MergeLds): f(GeomTag<BLK, DIG>) for the three that exist
 template <int BLK_, int DIG_> struct GeomTag { static constexpr int BLK = BLK_, DIG = DIG_; };
 template <class F> auto with_lookup_geom(int blk, int dig, F &&f)
 {
     return dig == 2048 ? f(GeomTag<BIG_BLOCK, 2048>{}) : blk == 512 ? f(GeomTag<512, 1024>{}) : f(GeomTag<BIG_BLOCK, 1024>{});
-}
-
-// raises the kernel's dynamic LDS limit where `lds` needs it, then enqueues it (the arguments convert to the kernel's parameter types)
-template <class... P, class... A>
-int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const char *who, const A &...args)
-{
-    if (int rc = raise_lds_limit((const void *)kernel, lds, who)) return rc;
-    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(args)...);
-    return PG_OK;
 }
 
 // (the kernel's SLOTS, WIDE, MERGE, HALF, MASKED; threads of a workgroup, row-group digits of its lookup tiles; dynamic LDS)

@@ -1,10 +1,12 @@
 // pg_device.hpp -- device helpers and small kernels shared by the translation units of libpangaea_feat.so
-// (kernels.hip: the key-partitioned pipeline; mini.hip: the super-k-mer pipeline).  Everything lives in an anonymous
+// (kernels.hip: the key-partitioned pipeline; table_ops.hip: operations on a finished table; mini.hip: the super-k-mer pipeline).  Everything lives in an anonymous
 // namespace: each translation unit gets its own copy.
 #ifndef PG_DEVICE_HPP
 #define PG_DEVICE_HPP
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
 
 #include "pangaea_feat.h"
 #include "pg_internal.h"
@@ -132,7 +134,7 @@ __device__ __forceinline__ uint32_t div_uniform(uint32_t c, uint32_t d, float rc
 
 // per-digit exclusive scan of table[d][0..n) in place, plus base[d << base_shift]; totals[d] (may be NULL) = row sum.
 // One workgroup per digit.
-__global__ __launch_bounds__(BIG_BLOCK) void digit_scan_kernel(unsigned long long *__restrict__ table, int64_t n,
+__attribute__((unused)) __global__ __launch_bounds__(BIG_BLOCK) void digit_scan_kernel(unsigned long long *__restrict__ table, int64_t n,
                                                                const unsigned long long *__restrict__ base, int base_shift,
                                                                unsigned long long *__restrict__ totals)
 {
@@ -292,6 +294,22 @@ int raise_lds_limit(const void *kernel, size_t bytes, const char *who)
     const int want = bytes <= 144 * 1024 ? 144 * 1024 : (int)bytes;
     if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, want) != hipSuccess)
         return pg_fail(PG_EHIP, "%s: cannot raise the dynamic LDS limit", who);
+    return PG_OK;
+}
+
+// typed dispatch: a runtime value becomes a compile-time tag, and the generic lambda `f` is called with the tag of the one
+// case that applies.  Every helper lists exactly the cases that have kernels: f is instantiated for those and no others.
+template <int N> using int_tag = std::integral_constant<int, N>;
+
+// the MASKED twin of a kernel or its plain form: f(std::true_type | std::false_type)
+template <class F> int with_flag(bool on, F &&f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+
+// raises the kernel's dynamic LDS limit where `lds` needs it, then enqueues it (the arguments convert to the kernel's parameter types)
+template <class... P, class... A>
+int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const char *who, const A &...args)
+{
+    if (int rc = raise_lds_limit((const void *)kernel, lds, who)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, static_cast<P>(args)...);
     return PG_OK;
 }
 

@@ -35,7 +35,10 @@ CASES = [("dense", 4, 0, 0), ("dense", 8, 0, 0),
 _IDS = [f"{c[0]}-k{c[1]}-s{c[2]}-b{c[3]}" for c in CASES]
 ALIGNED = [c for c in CASES if c[0] == "mini" or (c[0] == "hash" and c[3])]
 CROSS = [("hash", "mini", 15), ("mini", "hash", 15), ("hash", "mini", 21), ("mini", "hash", 21), ("dense", "hash", 11), ("hash", "dense", 11),
-         ("wide", "miniw", 25), ("miniw", "wide", 25)]
+         ("wide", "miniw", 25), ("miniw", "wide", 25),
+         # the other ordered pairs of distinct kinds that share a k, each at the smallest k both admit (dense at k = 13: 256 MiB)
+         ("dense", "wide", 11), ("wide", "dense", 11), ("dense", "mini", 13), ("mini", "dense", 13),
+         ("hash", "wide", 15), ("wide", "hash", 15), ("mini", "wide", 15), ("wide", "mini", 15)]
 
 
 def _rc(codes, k):
