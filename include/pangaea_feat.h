@@ -442,6 +442,64 @@ int pg_table_depth(const pg_table *t, const uint64_t *codes, const uint32_t *val
                    void *workspace, int64_t workspace_bytes, uint32_t *status, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Reads of a FASTQ text by their k-mers' counts in a finished table (device; one GPU, any of the five kinds; the table is only
+ * read: plain loads, no atomics on it).  What `kmc_tools filter` and khmer's filter-abund do with a table and a read file; here
+ * the alignment-free counterpart of the reference's low-abundance step, scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp, which
+ * pulls the reads of low-depth contigs into *.low_abd.fq after a bwa + samtools round: the same kind of read set straight from
+ * the table, and its opposite (reads made of error k-mers dropped before assembly).  The kernels work on the FASTQ TEXT in
+ * device memory -- the packed read stream keeps barcode runs, not read boundaries, names or qualities.  All entries are additive
+ * to ABI 9; every argument is checked before anything is enqueued (PG_EINVAL with a pg_last_error text: a null pointer, a k that
+ * is not the table's, lower > upper, negative sizes, a text base that is not 16-byte aligned).
+ *   INPUT    four-line FASTQ.  A line ends at '\n'; a last line without '\n' is a line; '\r' is an ordinary byte of its line
+ *            (no base: a CRLF file works and is copied verbatim).  Record r is lines 4r .. 4r + 3; line 0 must begin with '@'
+ *            and line 2 with '+'.  Multi-line FASTQ and FASTA are outside the contract.
+ *   K-MERS   position i of the sequence line (line 1) holds a k-mer iff i + k <= its length and bytes i .. i + k - 1 are all
+ *            bases: ACGT, and acgt too when lowercase_is_base; with min_qual_char = c != 0 a base whose quality byte (the same
+ *            offset of line 3) is below c is no base, and a quality line shorter than its sequence line is a format error
+ *            (without min_qual_char the quality line is never looked at).  The k-mer is made canonical in the table's code
+ *            (A0 C1 T2 G3, (ch >> 1) & 3).
+ *   HITS     n = the record's k-mers, h = those whose stored count c (0: not in the table; saturated counts as stored) satisfies
+ *            lower <= c <= upper; upper < 0: no upper bound; lower >= 0 (lower = upper = 0 counts the absent k-mers).
+ *   pg_fastq_index      beside scripts/low_abd_reads.sh:10 / extract_unmapped.cpp (its reader's getline): line_start[j] = byte
+ *                       offset of line j's first byte for j < lines, line_start[lines] = n_bytes; *n_lines (device) = lines.
+ *                       Entries at or beyond `cap` (>= 1) are not stored: a caller that finds *n_lines + 1 > cap calls again
+ *                       with room.  workspace: pg_fastq_index_workspace_bytes(n_bytes), 8-byte aligned.  n_bytes == 0: PG_OK,
+ *                       nothing launched, nothing written.
+ *   pg_table_read_hits  beside scripts/low_abd_reads.sh:10 / extract_unmapped.cpp (its decision which read to keep, here from
+ *                       k-mer counts and not from contig depth): hits[r][0] = n and hits[r][1] = h of record r < n_records of a
+ *                       text whose line index holds 4 * n_records + 1 entries.  One wavefront per record, any read length.
+ *                       status (device uint64_t[2], written whole by the call): [0] = PG_STATUS_FASTQ_FORMAT when a record is
+ *                       malformed, else 0; [1] = PG_FASTQ_CLEAN, or ((first_record + r) << 8) | reason of the malformed record
+ *                       with the SMALLEST ordinal (PG_FASTQ_NO_AT, PG_FASTQ_NO_PLUS, PG_FASTQ_SHORT_QUALITY; PG_FASTQ_BAD_INDEX:
+ *                       line_start is no index of this text -- nothing outside the text is read whatever it holds).  A
+ *                       malformed record's hits are 0, 0.  n_records == 0: PG_OK, nothing launched, nothing written.
+ *   pg_fastq_gather     beside scripts/low_abd_reads.sh:10 / extract_unmapped.cpp (its writing of the chosen reads): the bytes
+ *                       of record kept[i], [line_start[4 r], line_start[4 r + 4]), go to out + dst_off[i] for i < n_kept, byte
+ *                       for byte (a final record without its '\n' leaves without one).  dst_off is the caller's exclusive scan
+ *                       of the kept records' lengths.  One wavefront per kept record; nothing outside [0, n_bytes) of the text
+ *                       is read and nothing outside [0, out_bytes) of out written, whatever the device arrays hold.
+ *                       n_kept == 0: PG_OK, nothing launched.
+ * Which records are kept -- the pass rule (n >= 1, min_hits <= h <= max_hits, absolute or as a share of n) and the pair rule
+ * (any / both / single) -- is the caller's: a few element-wise operations on [n_records] arrays (pangaea_amd/kmer.py,
+ * KmerTable.filter_fastq).
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_STATUS_FASTQ_FORMAT 32u /* pg_table_read_hits: a record of the text is malformed; status[1] says which and why */
+#define PG_FASTQ_CLEAN 0xFFFFFFFFFFFFFFFFull
+#define PG_FASTQ_NO_AT 1u
+#define PG_FASTQ_NO_PLUS 2u
+#define PG_FASTQ_SHORT_QUALITY 3u
+#define PG_FASTQ_BAD_INDEX 4u
+int64_t pg_fastq_index_workspace_bytes(int64_t n_bytes);
+int pg_fastq_index(const uint8_t *text, int64_t n_bytes, int64_t *line_start /* device, [cap] */, int64_t cap,
+                   int64_t *n_lines /* device [1] */, void *workspace, int64_t workspace_bytes, void *stream);
+int pg_table_read_hits(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                       int64_t first_record, int64_t lower, int64_t upper /* < 0: none */, int lowercase_is_base,
+                       int min_qual_char /* 0: none */, uint32_t *hits /* device, [n_records][2] */,
+                       uint64_t *status /* device [2] */, void *stream);
+int pg_fastq_gather(const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records, const int64_t *kept,
+                    const int64_t *dst_off, int64_t n_kept, uint8_t *out, int64_t out_bytes, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
  * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
  * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for

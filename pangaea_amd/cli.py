@@ -10,6 +10,8 @@
     kmer_table combine --op {min,max,diff,left,only} -k K {-ga DUMP | -ia F} {-gb DUMP | -ib F} [-L LOWER] [-U UPPER] -o OUT
     kmer_table compare -k K {-ga DUMP | -ia F} {-gb DUMP | -ib F}      (one JSON line on stdout)
     kmer_table depth {-i F | -1 F -2 F | -g DUMP} -k K -s SEQS.fa[.gz] [-L LOWER] -o OUT.tsv
+    kmer_table filter {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} [-L LOWER] [-U UPPER] [--min-hits X] [--max-hits X]
+                      [--pair any|both|single] [--min-qual-char C] -o OUT [-o2 OUT2]      (one JSON line on stdout)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -148,28 +150,80 @@ def _check_window(lower: int, upper) -> None:
         raise ValueError(f"-U ({upper}) is below -L ({lower})")
 
 
-def main_kmer_table(argv=None) -> int:
-    """``kmer_table histo``: the count spectrum, one line ``"<count> <distinct k-mers>"`` for count = 1 .. high + 1 (the last
-    line gathers every count above ``--high``); lines of 0 are left out unless ``--full``.  ``kmer_table query``: one line
-    ``"<k-mer as given> <count>"`` on stdout per k-mer of the arguments and then of ``-q FILE`` (one per line), in that order;
-    either strand may be given, 0 = not in the table.  ``kmer_table dump``: the table as ``jellyfish dump -c -t [-L LOWER]``
-    writes it, one line ``"<k-mer>\t<count>"`` per canonical k-mer of count >= LOWER (``KmerTable.write_dump``; the file
-    ``count_kmer -g`` and ``kmer_table -g`` read).  The two formats of histo and query follow jellyfish's documented ``histo`` and ``query``
-    output; jellyfish is not at hand to compare with, so they are unpinned (like the two rules of DESIGN section 2) -- what the
-    tests pin is the content, against the oracle.  ``kmer_table merge``: the sum of two or more inputs -- every ``-g DUMP`` loaded
-    as ``-g`` elsewhere, every ``-i FASTQ`` counted as ``-i`` elsewhere, both repeatable -- as one table (``KmerTable.merged``: what
-    `jellyfish merge` makes of the tables of feature.py:76-94), written as ``kmer_table dump`` writes it.  ``kmer_table combine``:
-    two inputs -- A from ``-ga DUMP`` or ``-ia FASTQ``, B from ``-gb`` or ``-ib``, loaded or counted as ``-g`` / ``-i`` are elsewhere
-    -- met by ``--op`` (``KmerTable.combined``: min, max, diff = counts subtracted, left = A's counts of the shared k-mers, only =
-    A's k-mers that B lacks), kept where LOWER <= count <= UPPER and written as ``kmer_table dump`` writes a table.  ``kmer_table
-    compare``: one JSON line of ``KmerTable.compare`` on the same two inputs.  ``kmer_table dump -U UPPER`` writes only the
-    entries of count <= UPPER (``KmerTable.filtered``); without ``-U`` nothing about ``dump`` changes.  ``kmer_table depth``: how
-    deep the table covers each sequence of the FASTA file ``-s`` (``ReadStream.from_fasta``, ``KmerTable.depth``; lower-case
-    bases are bases, as to ``jellyfish query -s``), one tab-separated line ``name  length  kmers  present  mean  median  max``
-    per sequence in file order -- its k-mers, those whose count is at least LOWER, and mean (``%.3f`` of sum / kmers, 0.000
-    without k-mers), lower median and maximum of the counts, a count below LOWER taken as 0.  The table comes from exactly one
-    of ``-i``, ``-1``/``-2`` and ``-g``.  A k-mer depth beside the alignment depth of scripts/bin_assembly.sh:43, not that number.
-    Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
+def _hit_bound_arg(text: str, flag: str):
+    """``--min-hits`` / ``--max-hits``: with a '.' a share of the read's k-mers in [0, 1], else a whole number of them"""
+    try:
+        v = float(text) if "." in text else int(text)
+    except ValueError:
+        raise ValueError(f"{flag} takes a whole number or, written with a '.', a share in [0, 1] (got {text!r})")
+    if v < 0 or (isinstance(v, float) and v > 1.0):
+        raise ValueError(f"{flag} {text}: a share lies in [0, 1], a number of k-mers is at least 0")
+    return v
+
+
+def _filter_plan(a) -> tuple:
+    """the checked arguments of ``kmer_table filter``: (table source, reads, keyword arguments of ``KmerTable.filter_fastq``) -- the
+    table source is ("dump", path), ("reads", r1, r2 or None) or None (the table of the reads themselves).  Nothing is opened
+    but the question whether the inputs exist."""
+    from . import _lib
+    if not 1 <= a.kmer <= _lib.WIDE_MAX_K:
+        raise ValueError(f"k-mer size {a.kmer} unsupported (1..{_lib.WIDE_MAX_K})")
+    if bool(a.table1) != bool(a.table2):
+        raise ValueError("-t1 and -t2 go together")
+    if sum((bool(a.global_), bool(a.table_interleaved), bool(a.table1))) > 1:
+        raise ValueError("filter takes the table from one source: -g DUMP, -ti F or -t1 F -t2 F (none: the reads themselves)")
+    if bool(a.reads1) != bool(a.reads2):
+        raise ValueError("-1 and -2 go together")
+    if bool(a.interleaved) == bool(a.reads1):
+        raise ValueError("the reads to filter are -i F or -1 F -2 F (one of the two)")
+    if a.reads1 and not a.output2:
+        raise ValueError("-1 F -2 F writes two files: -o OUT -o2 OUT2")
+    if a.interleaved and a.output2:
+        raise ValueError("-o2 goes with -1 F -2 F")
+    if a.pair not in ("any", "both", "single"):
+        raise ValueError(f"--pair must be any, both or single (got {a.pair!r})")
+    if a.pair == "single" and a.reads1:
+        raise ValueError("--pair single judges the records of one file; -1 F -2 F is paired")
+    if a.lower < 0:
+        raise ValueError(f"-L must be at least 0 (got {a.lower})")
+    if a.upper is not None and a.upper < a.lower:
+        raise ValueError(f"-U ({a.upper}) is below -L ({a.lower})")
+    if a.min_qual_char is not None and len(a.min_qual_char) != 1:
+        raise ValueError(f"--min-qual-char takes one character (got {a.min_qual_char!r})")
+    kw = dict(lower=a.lower, upper=a.upper, min_hits=_hit_bound_arg(a.min_hits, "--min-hits"),
+              max_hits=None if a.max_hits is None else _hit_bound_arg(a.max_hits, "--max-hits"), pair=a.pair, min_qual_char=a.min_qual_char,
+              lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+    reads = (a.interleaved, None, a.output, None) if a.interleaved else (a.reads1, a.reads2, a.output, a.output2)
+    for o in reads[2:]:
+        if o and o.endswith(".gz"):
+            raise ValueError(f"{o}: the kept reads are written as plain text, gzip output is not supported")
+    source = ("dump", a.global_) if a.global_ else ("reads", a.table_interleaved, None) if a.table_interleaved else \
+        ("reads", a.table1, a.table2) if a.table1 else None
+    for f in [x for x in reads[:2] if x] + ([x for x in source[1:] if x] if source else []):
+        if not os.path.isfile(f):
+            raise ValueError(f"{f}: no such file")
+    return source, reads, kw
+
+
+def _kmer_table_filter(a) -> int:
+    import json
+    import torch
+    from .kmer import KmerTable
+    source, (r1, r2, o1, o2), kw = _filter_plan(a)
+    device = torch.device("cuda", torch.cuda.current_device())
+    if source is None:
+        table = _counted(r1, r2, a.kmer, device)
+    elif source[0] == "dump":
+        table = KmerTable.from_dump(source[1], a.kmer, device)
+    else:
+        table = _counted(source[1], source[2], a.kmer, device)
+    res = table.filter_fastq(r1, o1, r2, o2, **kw)
+    sys.stdout.write(json.dumps(res) + "\n")
+    return 0
+
+
+def _kmer_table_parser() -> _Parser:
+    """the argument parser of ``main_kmer_table``: one sub-parser per command"""
     p = _Parser(prog="kmer_table")
     sub = p.add_subparsers(dest="cmd", required=True)
     for name in ("histo", "query", "dump", "depth"):
@@ -212,9 +266,62 @@ def main_kmer_table(argv=None) -> int:
             q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
             q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
             q.add_argument("-o", "--output", required=True)
-    a = p.parse_args(argv)
+    q = sub.add_parser("filter")
+    q.add_argument("-g", "--global", dest="global_", default="")
+    q.add_argument("-ti", "--table-interleaved", dest="table_interleaved", default="")
+    q.add_argument("-t1", "--table-reads1", dest="table1", default="")
+    q.add_argument("-t2", "--table-reads2", dest="table2", default="")
+    q.add_argument("-k", "--kmer", type=int, required=True)
+    q.add_argument("-i", "--interleaved", default="")
+    q.add_argument("-1", "--reads1", default="")
+    q.add_argument("-2", "--reads2", default="")
+    q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
+    q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
+    q.add_argument("--min-hits", dest="min_hits", default="1")
+    q.add_argument("--max-hits", dest="max_hits", default=None)
+    q.add_argument("--pair", default="any")
+    q.add_argument("--min-qual-char", dest="min_qual_char", default=None)
+    q.add_argument("-o", "--output", required=True)
+    q.add_argument("-o2", "--output2", default="")
+    return p
+
+
+def main_kmer_table(argv=None) -> int:
+    """``kmer_table histo``: the count spectrum, one line ``"<count> <distinct k-mers>"`` for count = 1 .. high + 1 (the last
+    line gathers every count above ``--high``); lines of 0 are left out unless ``--full``.  ``kmer_table query``: one line
+    ``"<k-mer as given> <count>"`` on stdout per k-mer of the arguments and then of ``-q FILE`` (one per line), in that order;
+    either strand may be given, 0 = not in the table.  ``kmer_table dump``: the table as ``jellyfish dump -c -t [-L LOWER]``
+    writes it, one line ``"<k-mer>\t<count>"`` per canonical k-mer of count >= LOWER (``KmerTable.write_dump``; the file
+    ``count_kmer -g`` and ``kmer_table -g`` read).  The two formats of histo and query follow jellyfish's documented ``histo`` and ``query``
+    output; jellyfish is not at hand to compare with, so they are unpinned (like the two rules of DESIGN section 2) -- what the
+    tests pin is the content, against the oracle.  ``kmer_table merge``: the sum of two or more inputs -- every ``-g DUMP`` loaded
+    as ``-g`` elsewhere, every ``-i FASTQ`` counted as ``-i`` elsewhere, both repeatable -- as one table (``KmerTable.merged``: what
+    `jellyfish merge` makes of the tables of feature.py:76-94), written as ``kmer_table dump`` writes it.  ``kmer_table combine``:
+    two inputs -- A from ``-ga DUMP`` or ``-ia FASTQ``, B from ``-gb`` or ``-ib``, loaded or counted as ``-g`` / ``-i`` are elsewhere
+    -- met by ``--op`` (``KmerTable.combined``: min, max, diff = counts subtracted, left = A's counts of the shared k-mers, only =
+    A's k-mers that B lacks), kept where LOWER <= count <= UPPER and written as ``kmer_table dump`` writes a table.  ``kmer_table
+    compare``: one JSON line of ``KmerTable.compare`` on the same two inputs.  ``kmer_table dump -U UPPER`` writes only the
+    entries of count <= UPPER (``KmerTable.filtered``); without ``-U`` nothing about ``dump`` changes.  ``kmer_table depth``: how
+    deep the table covers each sequence of the FASTA file ``-s`` (``ReadStream.from_fasta``, ``KmerTable.depth``; lower-case
+    bases are bases, as to ``jellyfish query -s``), one tab-separated line ``name  length  kmers  present  mean  median  max``
+    per sequence in file order -- its k-mers, those whose count is at least LOWER, and mean (``%.3f`` of sum / kmers, 0.000
+    without k-mers), lower median and maximum of the counts, a count below LOWER taken as 0.  The table comes from exactly one
+    of ``-i``, ``-1``/``-2`` and ``-g``.  A k-mer depth beside the alignment depth of scripts/bin_assembly.sh:43, not that number.
+    ``kmer_table filter``: the reads of ``-i F`` (mates, if any, interleaved) or ``-1 F -2 F`` whose k-mers the table counts as
+    asked, written byte for byte and in input order to ``-o`` (and ``-o2``) as plain FASTQ (``KmerTable.filter_fastq``; what
+    `kmc_tools filter` does, beside the read set of scripts/low_abd_reads.sh:10).  The table is loaded from ``-g DUMP``, counted
+    from ``-ti F`` or ``-t1 F -t2 F`` as ``-i`` / ``-1 -2`` are elsewhere, or -- no table source -- counted from the reads
+    themselves (the usual "drop my own error reads" call).  A read passes iff it has a k-mer and the number h of its k-mers with
+    LOWER <= count <= UPPER (``-L`` may be 0: absent k-mers; no ``-U``: no upper bound) satisfies ``--min-hits`` <= h <=
+    ``--max-hits``, each a whole number or, written with a '.', a share of the read's k-mers; ``--pair any`` (the default) keeps
+    both mates if either passes, ``both`` if both do, ``single`` judges every record of ``-i`` on its own; ``--min-qual-char C``:
+    bases of quality below C are no bases.  One JSON line on stdout: records, kept, passed, bases, kmers, hits, seconds, device_ms.
+    Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
+    a = _kmer_table_parser().parse_args(argv)
     from . import _lib
     try:
+        if a.cmd == "filter":
+            return _kmer_table_filter(a)
         if a.cmd in ("combine", "compare"):
             for side, g, i in (("A", a.global_a, a.interleaved_a), ("B", a.global_b, a.interleaved_b)):
                 if bool(g) == bool(i):

@@ -1,5 +1,5 @@
 // table_ops.hip -- gfx950 kernels that work on a FINISHED k-mer table, and their C-ABI launchers: query and spectrum, the text dump
-// and its reload, merge, combine and compare, depth of sequences.  None of them is on the timed path (kernels.hip: counting and
+// and its reload, merge, combine and compare, depth of sequences, reads of a FASTQ text by their k-mers' counts.  None of them is on the timed path (kernels.hip: counting and
 // features; mini.hip: the super-k-mer pipeline); what they share with it is pg_table.hpp.
 //
 // Replaces (reference file:line): jellyfish query / histo / dump / merge over the table of feature.py:76-103 and
@@ -1174,6 +1174,187 @@ __global__ __launch_bounds__(BIG_BLOCK) void depth_select_kernel(const void *ws,
     }
 }
 
+// -------------------------------------------------------------------------------- reads of a FASTQ text by their k-mers' counts
+//
+// What `kmc_tools filter` / khmer's filter-abund answer from a table and a FASTQ file, and the k-mer counterpart of the read set
+// that scripts/low_abd_reads.sh:10 (extract_unmapped.cpp) pulls out by alignment: per record how many k-mers its sequence line
+// holds and how many of them the table counts inside [lower, upper], and the kept records copied byte for byte.  The kernels
+// work on the TEXT (the packed stream keeps barcode runs, no read boundaries, names or qualities); semantics: the header's
+// section of the same name.  The table is only read: plain loads, no atomics on it.
+
+// ---- 1. the line index: line_start[j] = byte offset of line j's first character, line_start[lines] = n.  The tiles and the
+// newline mask are the dump reload's (dump_newlines_kernel counts, scan_kernel numbers the tiles); a lane that owns newlines
+// writes the start of the line behind each.  Nothing is stored at or beyond `cap`.
+__global__ __launch_bounds__(BLOCK) void fastq_lines_kernel(const uint8_t *__restrict__ text, int64_t n, int64_t n_tiles,
+                                                            const unsigned long long *__restrict__ tile_first, long long *__restrict__ line_start,
+                                                            int64_t cap, long long *__restrict__ n_lines)
+{
+    __shared__ uint32_t part[WAVES];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int64_t nl = (int64_t)tile_first[n_tiles], lines = nl + (text[n - 1] != '\n');     // (a last line without newline is a line)
+        *n_lines = lines;
+        if (cap > 0) line_start[0] = 0;
+        if (lines > nl && lines < cap) line_start[lines] = n;
+    }
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t p0 = tile * PARSE_TILE + (int64_t)threadIdx.x * 16;
+        uint32_t nl = p0 < n ? dump_newline_mask(text, p0, n) : 0u;
+        uint32_t total;
+        int64_t at = (int64_t)tile_first[tile] + dump_block_scan((uint32_t)__popc(nl), part, &total) + 1;
+        while (nl) {
+            const int b = __ffs(nl) - 1;
+            nl &= nl - 1;
+            if (at < cap) line_start[at] = p0 + b + 1;
+            ++at;
+        }
+    }
+}
+
+// ---- 2. (k-mers, hits) of every record.  One wavefront per record, grid-stride, as depth_short_kernel takes a range.  A batch is
+// 64 x DEPTH_BATCH positions of the sequence line: the wavefront reads the HITS_CHARS characters those positions reach (the
+// batch's own and the k - 1 <= 30 behind them, in whole words; the next batch reads its overlap again, from L1), one byte per
+// lane and turn, and composes them into the stream's word form in its own corner of LDS -- 2-bit codes (ch >> 1) & 3, oldest
+// character lowest, 32 to a word, and the validity bits beside them -- from three ballots per turn.  From there the k-mers come
+// out exactly as kmer_at takes them from a stream, and the lookups are depth_short_kernel's: all first probes of the batch
+// issued before any is resolved.  No packed copy of the text goes through HBM; 8 bytes leave per record.
+constexpr int HITS_TURNS = DEPTH_BATCH + 1;
+constexpr int HITS_CHARS = 64 * HITS_TURNS, HITS_WORDS = HITS_CHARS / 32;
+static_assert(64 * DEPTH_BATCH + PG_WIDE_MAX_K - 1 <= HITS_CHARS, "a batch's last k-mer ends inside the staged characters");
+
+// the bits of x at the even positions of a 64-bit word
+__device__ __forceinline__ uint64_t spread_bits(uint32_t x)
+{
+    uint64_t v = x;
+    v = (v | (v << 16)) & 0x0000FFFF0000FFFFull;
+    v = (v | (v << 8)) & 0x00FF00FF00FF00FFull;
+    v = (v | (v << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    v = (v | (v << 2)) & 0x3333333333333333ull;
+    v = (v | (v << 1)) & 0x5555555555555555ull;
+    return v;
+}
+
+// (what one lane of a wavefront wrote to LDS, the others may read behind this, and the other way round)
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void read_hits_kernel(const uint8_t *__restrict__ text, int64_t n_bytes, const long long *__restrict__ line_start,
+                                                          int64_t n_records, int64_t first_record, int k, uint64_t lower, uint64_t upper, int lenient,
+                                                          uint32_t min_qual, const uint32_t *__restrict__ dense, HashView t, uint32_t *__restrict__ out,
+                                                          unsigned long long *status)
+{
+    __shared__ uint64_t s_codes[WAVES][HITS_WORDS];
+    __shared__ uint32_t s_valid[WAVES][HITS_WORDS];
+    const int lane = threadIdx.x & 63;
+    uint64_t *wc = s_codes[threadIdx.x >> 6];
+    uint32_t *wv = s_valid[threadIdx.x >> 6];
+    const uint64_t kmask = low_mask<uint64_t>(k);
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES;
+    for (int64_t r = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); r < n_records; r += n_waves) {
+        const int64_t s0 = line_start[4 * r], s1 = line_start[4 * r + 1], s2 = line_start[4 * r + 2], s3 = line_start[4 * r + 3], s4 = line_start[4 * r + 4];
+        uint32_t bad = 0;
+        int64_t len = 0;
+        // (an index that is none -- outside the contract -- is a bad record too: nothing outside the text is read)
+        if (!(s0 >= 0 && s0 < s1 && s1 < s2 && s2 < s3 && s3 <= s4 && s4 <= n_bytes)) bad = PG_FASTQ_BAD_INDEX;
+        else if (text[s0] != '@') bad = PG_FASTQ_NO_AT;
+        else if (text[s2] != '+') bad = PG_FASTQ_NO_PLUS;
+        else {
+            len = s2 - 1 - s1;                               // (the sequence line ends with the newline in front of the '+' line)
+            if (min_qual) {
+                const int64_t qlen = s4 - s3 - (s4 > s3 && text[s4 - 1] == '\n');
+                if (qlen < len) bad = PG_FASTQ_SHORT_QUALITY;
+            }
+        }
+        if (bad) {                                           // (the same for the whole wavefront)
+            if (lane == 0) {
+                atomicMin(&status[1], ((unsigned long long)(first_record + r) << 8) | bad);
+                atomicOr(&status[0], (unsigned long long)PG_STATUS_FASTQ_FORMAT);
+                out[2 * r] = out[2 * r + 1] = 0;
+            }
+            continue;
+        }
+        const int64_t n_pos = len >= k ? len - k + 1 : 0;
+        uint32_t n = 0, h = 0;
+        for (int64_t base = 0; base < n_pos; base += 64 * DEPTH_BATCH) {
+#pragma unroll
+            for (int u = 0; u < HITS_TURNS; ++u) {
+                if (base + 64 * u >= len) break;             // (the same for the whole wavefront; no k-mer of the line reaches these words)
+                const int64_t j = base + 64 * u + lane;
+                uint32_t ch = 0;
+                bool ok = false;
+                if (j < len) {
+                    ch = text[s1 + j];
+                    const uint32_t up = lenient ? ch & 0xDFu : ch;
+                    ok = up == 'A' || up == 'C' || up == 'G' || up == 'T';
+                    if (ok && min_qual) ok = text[s3 + j] >= min_qual;       // (j < len <= the quality line's length)
+                }
+                const uint64_t v = __ballot(ok), b0 = __ballot((ch >> 1) & 1u), b1 = __ballot((ch >> 2) & 1u);
+                if (lane < 2) {
+                    wc[2 * u + lane] = spread_bits((uint32_t)(b0 >> (32 * lane))) | (spread_bits((uint32_t)(b1 >> (32 * lane))) << 1);
+                    wv[2 * u + lane] = (uint32_t)(v >> (32 * lane));
+                }
+            }
+            wave_lds_sync();
+            Lookup<TK> p[DEPTH_BATCH];
+            bool have[DEPTH_BATCH];
+#pragma unroll
+            for (int u = 0; u < DEPTH_BATCH; ++u) {
+                const int g = lane + 64 * u;
+                uint64_t canon = 0;
+                p[u].key = p[u].hh = p[u].cur = 0;
+                have[u] = base + g < n_pos && kmer_at(wc, wv, g, k, kmask, &canon);
+                if (have[u]) p[u].issue(canon, k, dense, t);
+            }
+#pragma unroll
+            for (int u = 0; u < DEPTH_BATCH; ++u) {
+                const uint32_t c = have[u] ? p[u].resolve(t) : 0u;
+                n += (uint32_t)__popcll(__ballot(have[u]));
+                h += (uint32_t)__popcll(__ballot(have[u] && c >= lower && c <= upper));
+            }
+            wave_lds_sync();                                 // (the next batch stages over these words)
+        }
+        if (lane == 0) { out[2 * r] = n; out[2 * r + 1] = h; }
+    }
+}
+
+// ---- 3. the kept records to their places: record kept[i]'s bytes [line_start[4 r], line_start[4 r + 4]) to out + dst_off[i].  One
+// wavefront per kept record.  Source and destination are unaligned with respect to each other: the destination side goes in
+// whole 16-byte pieces (each read from wherever it lies in the source), the fewer than 16 bytes in front of the first aligned
+// piece and behind the last byte-wise, as table_dump_text_kernel places its units.  No byte outside [0, n_bytes) of the text is
+// read and none outside [0, out_bytes) of `out` written, whatever the device arrays say.
+__global__ __launch_bounds__(BLOCK) void fastq_gather_kernel(const uint8_t *__restrict__ text, int64_t n_bytes, const long long *__restrict__ line_start,
+                                                             int64_t n_records, const long long *__restrict__ kept, const long long *__restrict__ dst_off,
+                                                             int64_t n_kept, uint8_t *__restrict__ out, int64_t out_bytes)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES;
+    for (int64_t i = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); i < n_kept; i += n_waves) {
+        const int64_t r = kept[i];
+        if (r < 0 || r >= n_records) continue;
+        const int64_t a = line_start[4 * r], b = line_start[4 * r + 4], d = dst_off[i];
+        if (a < 0 || b < a || b > n_bytes || d < 0 || d > out_bytes - (b - a)) continue;
+        const int64_t len = b - a;
+        const uint8_t *src = text + a;
+        uint8_t *dst = out + d;
+        int64_t head = (int64_t)((16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u);
+        if (head > len) head = len;
+        const int64_t n16 = (len - head) >> 4, tail = len - head - (n16 << 4);
+        for (int64_t q = lane; q < n16; q += 64) {
+            uint4 v;
+            __builtin_memcpy(&v, src + head + (q << 4), 16);                  // (no alignment is promised for the source)
+            *(uint4 *)(dst + head + (q << 4)) = v;
+        }
+        if (lane < head + tail) {
+            const int64_t o = lane < head ? lane : len - tail + (lane - head);
+            dst[o] = src[o];
+        }
+    }
+}
+
 }  // namespace
 
 // the table as the streaming kernels see it (spectrum, dump, merge, combine): layout, entries, the counts plane of the planes form
@@ -1619,4 +1800,89 @@ extern "C" int pg_dump_parse(const uint8_t *text, int64_t n_bytes, int k, int64_
     hipLaunchKernelGGL(dump_parse_kernel, dim3(grid), dim3(BLOCK), 0, s, text, n_bytes, n_tiles, (const unsigned long long *)first, k, first_ordinal,
                        codes, counts, (long long *)ordinals, cap, (unsigned long long *)n_out, (unsigned long long *)status);
     return check_launch("pg_dump_parse");
+}
+
+// ---- reads of a FASTQ text by their k-mers' counts (kernels: the section of the same name above); beside the read set of
+// scripts/low_abd_reads.sh:10 / extract_unmapped.cpp, replacing nothing
+extern "C" int64_t pg_fastq_index_workspace_bytes(int64_t n_bytes)
+{
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "pg_fastq_index_workspace_bytes: n_bytes is negative (%lld)", (long long)n_bytes);
+    return pg_dump_parse_workspace_bytes(n_bytes);                         // (the same tiles: newlines per tile and their scan)
+}
+
+extern "C" int pg_fastq_index(const uint8_t *text, int64_t n_bytes, int64_t *line_start, int64_t cap, int64_t *n_lines, void *workspace,
+                              int64_t workspace_bytes, void *stream)
+{
+    if (!text) return pg_fail(PG_EINVAL, "pg_fastq_index: text is null");
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "pg_fastq_index: n_bytes is negative (%lld)", (long long)n_bytes);
+    if (!line_start) return pg_fail(PG_EINVAL, "pg_fastq_index: line_start is null");
+    if (cap < 1) return pg_fail(PG_EINVAL, "pg_fastq_index: cap is below 1 (%lld)", (long long)cap);
+    if (!n_lines) return pg_fail(PG_EINVAL, "pg_fastq_index: n_lines is null");
+    if ((uintptr_t)text & 15) return pg_fail(PG_EINVAL, "pg_fastq_index: text is not 16-byte aligned");
+    if (n_bytes == 0) return PG_OK;
+    const int64_t need = pg_fastq_index_workspace_bytes(n_bytes);
+    if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < need)
+        return pg_fail(PG_EINVAL, "pg_fastq_index: workspace of %lld bytes, %lld needed (8-byte aligned)", (long long)workspace_bytes, (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_tiles = (n_bytes + PARSE_TILE - 1) / PARSE_TILE;
+    unsigned long long *hist = (unsigned long long *)workspace, *first = hist + n_tiles + 1;
+    const int grid = grid_for(n_tiles, 1);
+    hipLaunchKernelGGL(dump_newlines_kernel, dim3(grid), dim3(BLOCK), 0, s, text, n_bytes, n_tiles, hist);
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(BIG_BLOCK), 0, s, (const unsigned long long *)hist, n_tiles, first);
+    hipLaunchKernelGGL(fastq_lines_kernel, dim3(grid), dim3(BLOCK), 0, s, text, n_bytes, n_tiles, (const unsigned long long *)first,
+                       (long long *)line_start, cap, (long long *)n_lines);
+    return check_launch("pg_fastq_index");
+}
+
+extern "C" int pg_table_read_hits(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                                  int64_t first_record, int64_t lower, int64_t upper, int lowercase_is_base, int min_qual_char, uint32_t *hits,
+                                  uint64_t *status, void *stream)
+{
+    const char *who = "pg_table_read_hits";
+    if (!t) return pg_fail(PG_EINVAL, "%s: t is null", who);
+    if (!text) return pg_fail(PG_EINVAL, "%s: text is null", who);
+    if (!line_start) return pg_fail(PG_EINVAL, "%s: line_start is null", who);
+    if (!hits) return pg_fail(PG_EINVAL, "%s: hits is null", who);
+    if (!status) return pg_fail(PG_EINVAL, "%s: status is null", who);
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "%s: n_bytes is negative (%lld)", who, (long long)n_bytes);
+    if (n_records < 0) return pg_fail(PG_EINVAL, "%s: n_records is negative (%lld)", who, (long long)n_records);
+    if (first_record < 0) return pg_fail(PG_EINVAL, "%s: first_record is negative (%lld)", who, (long long)first_record);
+    if (lower < 0) return pg_fail(PG_EINVAL, "%s: lower is negative (%lld)", who, (long long)lower);
+    if (upper >= 0 && upper < lower) return pg_fail(PG_EINVAL, "%s: upper %lld is below lower %lld", who, (long long)upper, (long long)lower);
+    if (min_qual_char < 0 || min_qual_char > 255) return pg_fail(PG_EINVAL, "%s: min_qual_char %d is no byte (0: none)", who, min_qual_char);
+    if ((uintptr_t)text & 15) return pg_fail(PG_EINVAL, "%s: text is not 16-byte aligned", who);
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (t->k != k) return pg_fail(PG_EINVAL, "%s: k differs (table %d, asked %d)", who, t->k, k);
+    if (n_records == 0) return PG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(status, 0, sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(status + 1, 0xff, sizeof(uint64_t), s) != hipSuccess)
+        return pg_fail(PG_EHIP, "%s: cannot clear the status", who);
+    const ProbeArgs pa = probe_args(t);
+    const int grid = grid_for(n_records, WAVES);
+    const uint64_t up = upper < 0 ? ~0ull : (uint64_t)upper;
+    rc = with_kind(t->kind, [&](auto tk) {
+        return launch(read_hits_kernel<decltype(tk)::value>, dim3(grid), dim3(BLOCK), 0, s, who, text, n_bytes, (const long long *)line_start, n_records,
+                      first_record, k, (uint64_t)lower, up, lowercase_is_base ? 1 : 0, (uint32_t)min_qual_char, pa.dense, pa.view, hits,
+                      (unsigned long long *)status);
+    });
+    return rc ? rc : check_launch(who);
+}
+
+extern "C" int pg_fastq_gather(const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records, const int64_t *kept,
+                               const int64_t *dst_off, int64_t n_kept, uint8_t *out, int64_t out_bytes, void *stream)
+{
+    const char *who = "pg_fastq_gather";
+    if (!text) return pg_fail(PG_EINVAL, "%s: text is null", who);
+    if (!line_start) return pg_fail(PG_EINVAL, "%s: line_start is null", who);
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "%s: n_bytes is negative (%lld)", who, (long long)n_bytes);
+    if (n_records < 0) return pg_fail(PG_EINVAL, "%s: n_records is negative (%lld)", who, (long long)n_records);
+    if (n_kept < 0 || n_kept > n_records) return pg_fail(PG_EINVAL, "%s: n_kept %lld outside [0, %lld]", who, (long long)n_kept, (long long)n_records);
+    if (out_bytes < 0) return pg_fail(PG_EINVAL, "%s: out_bytes is negative (%lld)", who, (long long)out_bytes);
+    if (n_kept > 0 && (!kept || !dst_off)) return pg_fail(PG_EINVAL, "%s: kept or dst_off is null", who);
+    if (n_kept > 0 && !out) return pg_fail(PG_EINVAL, "%s: out is null", who);
+    if (n_kept == 0) return PG_OK;
+    hipLaunchKernelGGL(fastq_gather_kernel, dim3(grid_for(n_kept, WAVES)), dim3(BLOCK), 0, (hipStream_t)stream, text, n_bytes, (const long long *)line_start,
+                       n_records, (const long long *)kept, (const long long *)dst_off, n_kept, out, out_bytes);
+    return check_launch(who);
 }

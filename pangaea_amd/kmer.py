@@ -1498,6 +1498,258 @@ class KmerTable:
             raise RuntimeError("pg_table_depth: the workspace did not hold the long ranges (PG_STATUS_DEPTH_WORKSPACE)")
         return out
 
+    # ------------------------------------------------------------------ reads by their k-mers' counts (kmc_tools filter)
+
+    FILTER_PIECE_BYTES = 256 << 20         # FASTQ text per piece and input of ``filter_fastq`` (device buffer + pinned host buffer)
+
+    @staticmethod
+    def _filter_piece_bytes() -> int:
+        """PG_FILTER_PIECE_BYTES overrides the piece size (tests: records across every boundary, a record larger than a piece)"""
+        want = os.environ.get("PG_FILTER_PIECE_BYTES")
+        return max(64, int(want)) if want else KmerTable.FILTER_PIECE_BYTES
+
+    def _hits_window(self, lower, upper, min_qual_char) -> tuple:
+        """(lower, upper or -1, quality threshold byte or 0) as pg_table_read_hits takes them"""
+        lower = int(lower)
+        if lower < 0:
+            raise ValueError(f"lower must be at least 0 (got {lower})")
+        if upper is not None and int(upper) < lower:
+            raise ValueError(f"upper ({upper}) is below lower ({lower})")
+        if min_qual_char is None:
+            mq = 0
+        else:
+            c = min_qual_char.encode("latin-1") if isinstance(min_qual_char, str) else bytes([min_qual_char]) if isinstance(min_qual_char, int) else bytes(min_qual_char)
+            if len(c) != 1 or c[0] == 0:
+                raise ValueError(f"min_qual_char must be one character (got {min_qual_char!r})")
+            mq = c[0]
+        return lower, -1 if upper is None else int(upper), mq
+
+    def _line_index(self, text: torch.Tensor, n_bytes: int, hold: dict) -> tuple:
+        """(line starts: int64 on the device, entries 0 .. n_lines valid; n_lines) of text[:n_bytes] (pg_fastq_index).  ``hold``
+        keeps the index buffer and the workspace for the next piece.  A host wait."""
+        L = _lib.load()
+        dev = self.device
+        need = _lib.check(L.pg_fastq_index_workspace_bytes(n_bytes))
+        if hold.get("ws") is None or hold["ws"].numel() < need:
+            hold["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        word = torch.zeros(1, dtype=torch.int64, device=dev)
+        cap = n_bytes // 16 + 1024               # (reads have lines of 50 bytes and more; a text of shorter ones asks twice)
+        while True:
+            if hold.get("idx") is None or hold["idx"].numel() < cap:
+                hold["idx"] = torch.empty(cap, dtype=torch.int64, device=dev)
+            idx = hold["idx"]
+            _lib.check(L.pg_fastq_index(text.data_ptr(), n_bytes, idx.data_ptr(), idx.numel(), word.data_ptr(), hold["ws"].data_ptr(),
+                                        hold["ws"].numel(), _stream_ptr(dev)))
+            n_lines = int(word.item())
+            if n_lines + 1 <= idx.numel():
+                return idx, n_lines
+            cap = n_lines + 1
+
+    def _hits_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, window: tuple,
+                 lowercase_is_base: bool, status: torch.Tensor | None = None, events: tuple | None = None) -> tuple:
+        """(hits: int32 [n_records, 2] holding the 32-bit counts, status: int64 [2]) of pg_table_read_hits, both on the device.
+        ``status``: a tensor to use (the entry writes it whole); ``events``: two device events recorded right around the entry"""
+        dev = self.device
+        hits = torch.empty((n_records, 2), dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(2, dtype=torch.int64, device=dev)
+        lower, upper, mq = window
+        L = _lib.load()
+        if events:
+            events[0].record()
+        rc = L.pg_table_read_hits(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, upper,
+                                  1 if lowercase_is_base else 0, mq, hits.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+        if events:
+            events[1].record()
+        _lib.check(rc)
+        return hits, status
+
+    def read_hits(self, text: torch.Tensor, lower: int = 1, upper: int | None = None, lowercase_is_base: bool = True,
+                  min_qual_char=None) -> torch.Tensor:
+        """(n, h) of every record of a four-line FASTQ text: int64 [n_records, 2] on the table's device -- n = the k-mers of the
+        record's sequence line, h = those whose count c in this table (0: absent; saturated counts as stored) satisfies
+        ``lower <= c <= upper`` (``upper`` None: no upper bound; ``lower`` 0 is allowed, ``lower = upper = 0`` counts the absent
+        k-mers).  The alignment-free counterpart of the read choice of scripts/low_abd_reads.sh:10 (extract_unmapped.cpp).
+
+        ``text``: a uint8 tensor ON THE DEVICE that holds whole records.  A line ends at ``\\n``, a last line without one is a
+        line, ``\\r`` is an ordinary byte of its line (no base).  Record r is lines 4r .. 4r + 3; line 0 must begin with ``@``,
+        line 2 with ``+``.  Position i of the sequence line holds a k-mer iff i + k <= its length and bytes i .. i + k - 1 are all
+        bases: ACGT, and acgt too when ``lowercase_is_base`` (the rule the tables are counted with); with ``min_qual_char`` a
+        base whose quality byte at the same offset is below it is no base (what ``--min-qual-char`` does to -1/-2 tables), and
+        a quality line shorter than its sequence line is malformed -- otherwise the quality line is never looked at.  Malformed
+        text (a line count that is no multiple of 4 included) raises ValueError naming the first offending record; a CPU tensor
+        RuntimeError.  The table is only read (pg_fastq_index, pg_table_read_hits)."""
+        if not isinstance(text, torch.Tensor) or text.dtype != torch.uint8 or text.dim() != 1:
+            raise TypeError("text must be a one-dimensional uint8 tensor")
+        _require_gpu(text, "the FASTQ text")
+        self._require_readable()
+        if text.device != self.device:
+            raise ValueError("text and table are on different devices")
+        window = self._hits_window(lower, upper, min_qual_char)
+        n = int(text.numel())
+        if n == 0:
+            return torch.zeros((0, 2), dtype=torch.int64, device=self.device)
+        text = text.contiguous()
+        if text.data_ptr() & 15:                 # (a view into a larger text: the kernels read 16-byte pieces)
+            text = text.clone()
+        with torch.cuda.device(self.device):
+            idx, n_lines = self._line_index(text, n, {})
+            hits, bad = torch.zeros((0, 2), dtype=torch.int32, device=self.device), -1
+            if n_lines >= 4:
+                hits, status = self._hits_of(text, n, idx, n_lines // 4, 0, window, bool(lowercase_is_base))
+                bad = int(status[1].item())
+        if bad != -1:
+            raise ValueError(_fastq_error("the text", bad & ((1 << 64) - 1)))
+        if n_lines % 4:
+            raise ValueError(f"the text: record {n_lines // 4}: the text ends inside it ({n_lines} lines, no multiple of 4) (PG_EFORMAT)")
+        return hits.to(torch.int64) & 0xFFFFFFFF
+
+    def filter_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
+                     min_hits=1, max_hits=None, pair: str = "any", lowercase_is_base: bool = True, min_qual_char=None) -> dict:
+        """keep or drop the reads of a FASTQ file by the counts of their k-mers in this table (`kmc_tools filter`, khmer's
+        filter-abund; the alignment-free counterpart of scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp) and write the kept
+        records, byte for byte and in input order, to ``out1`` (and ``out2``).
+
+        Input: four-line FASTQ, plain or gzip -- one file (``src1``; mates, if any, interleaved) or an R1/R2 pair (``src1``,
+        ``src2`` with ``out1``, ``out2``).  Records, k-mers and the hit count h of a read among its n k-mers: ``read_hits``
+        (``lower``, ``upper``, ``lowercase_is_base``, ``min_qual_char`` as there).  A read PASSES iff n >= 1, h >= ``min_hits`` and
+        h <= ``max_hits``; each bound is an int (absolute) or a float in [0, 1] (a share of n, compared as ``h >= f * n`` /
+        ``h <= f * n`` in IEEE double); ``max_hits`` None: no bound.  A read without k-mers never passes.  ``pair``: "any" keeps
+        both mates if either passes, "both" if both pass, "single" judges every record on its own (one input file only).  Mates
+        are records 2i and 2i + 1 of one file, or record i of R1 and of R2; names are not compared.  ValueError (PG_EFORMAT) with
+        the record's ordinal: a first line without ``@``, a third without ``+``, a file that ends inside a record, a short quality
+        line under ``min_qual_char``, an odd record count under any / both, R1 / R2 of different record counts.
+
+        Output is plain text (a path ending in ``.gz`` is refused), written under a temporary name of its own beside the output
+        and moved into place at the end: after any error no output file is left and no other file has been touched.  The
+        outputs must differ from each other and from the inputs.  The files go through the device in pieces of ``FILTER_PIECE_BYTES``
+        (PG_FILTER_PIECE_BYTES, read at call time): a piece starts at a record start, what lies behind its last complete record
+        (and, for R1 / R2, behind the records both pieces hold) is carried into the next, a record larger than a piece grows the
+        buffer.  The device holds one piece per input, its line index, the hits and one output piece.
+
+        Returns ``records``, ``kept``, ``passed`` (records that passed on their own), ``bases`` (bytes of the sequence lines),
+        ``kmers``, ``hits`` -- totals over all inputs, exact -- and ``seconds`` (wall), ``device_ms`` (the pg_table_read_hits and
+        pg_fastq_gather entries of every piece, each between two device events of its own)."""
+        import time
+        t0 = time.perf_counter()
+        if pair not in ("any", "both", "single"):
+            raise ValueError(f"pair must be any, both or single (got {pair!r})")
+        if (src2 is None) != (out2 is None):
+            raise ValueError("src2 and out2 go together: two inputs give two outputs")
+        if pair == "single" and src2 is not None:
+            raise ValueError("pair='single' judges the records of ONE file; R1/R2 input is paired")
+        srcs = [os.fspath(src1)] + ([os.fspath(src2)] if src2 is not None else [])
+        outs = [os.fspath(out1)] + ([os.fspath(out2)] if out2 is not None else [])
+        for o in outs:
+            if o.endswith(".gz"):
+                raise ValueError(f"{o}: the kept reads are written as plain text, gzip output is not supported")
+        real_outs = [os.path.realpath(x) for x in outs]
+        if len(set(real_outs)) != len(outs) or set(real_outs) & {os.path.realpath(x) for x in srcs}:
+            raise ValueError("the outputs must differ from each other and from the inputs (got " + ", ".join(outs + srcs) + ")")
+        window = self._hits_window(lower, upper, min_qual_char)
+        lo_bound, hi_bound = _hit_bound(min_hits, "min_hits"), None if max_hits is None else _hit_bound(max_hits, "max_hits")
+        lenient = bool(lowercase_is_base)
+        self._require_readable()
+        dev = self.device
+        L = _lib.load()
+        piece = self._filter_piece_bytes()
+        mates = pair != "single"
+        tot = torch.zeros(6, dtype=torch.int64, device=dev)              # records, kept, passed, bases, kmers, hits
+        timed = []                                                       # (event, event) around every timed entry; read at the end
+        ins, files, tmps = [], [], []
+        try:
+            with torch.cuda.device(dev):
+                for path in srcs:
+                    ins.append(_FastqPieces(path, piece))
+                for o in outs:
+                    f, tmp = _temp_beside(o)
+                    files.append(f)
+                    tmps.append(tmp)
+                status = torch.empty((len(ins), 2), dtype=torch.int64, device=dev)
+                out_dev = out_host = None
+                done = False
+                while not done:
+                    for s in ins:
+                        s.fill()
+                        s.index(self)
+                    n, pending, all_eof = _filter_round(ins, mates, pair)
+                    if n == 0 and pending is None and not all_eof:       # a buffer that is full and holds no record (pair): a longer one
+                        for s in ins:
+                            if not s.eof and s.n_rec < (2 if len(ins) == 1 and mates else 1):
+                                s.grow()
+                        continue
+                    done = all_eof or pending is not None
+                    if n:
+                        got = []
+                        for i, s in enumerate(ins):
+                            timed.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                            got.append(self._hits_of(s.text, s.have, s.idx, n, s.done, window, lenient, status[i], timed[-1])[0])
+                        for s, b in zip(ins, status[:, 1].cpu().tolist()):       # (the malformed record in front comes before what is pending)
+                            if b != -1:
+                                raise ValueError(_fastq_error(s.path, b & ((1 << 64) - 1)))
+                    if pending is not None:
+                        raise ValueError(pending)
+                    if n == 0:
+                        break
+                    passed = []
+                    for s, hits in zip(ins, got):
+                        nk, hh = (hits[:, 0].to(torch.int64) & 0xFFFFFFFF), (hits[:, 1].to(torch.int64) & 0xFFFFFFFF)
+                        ok = (nk >= 1) & _bound_holds(hh, nk, lo_bound, True)
+                        if hi_bound is not None:
+                            ok &= _bound_holds(hh, nk, hi_bound, False)
+                        passed.append(ok)
+                        tot[0] += n
+                        tot[2] += ok.sum()
+                        tot[3] += (s.idx[2:4 * n:4] - s.idx[1:4 * n:4] - 1).sum()
+                        tot[4] += nk.sum()
+                        tot[5] += hh.sum()
+                    if len(ins) == 2:
+                        keep = passed[0] | passed[1] if pair == "any" else passed[0] & passed[1]
+                        keeps = [keep, keep]
+                    elif mates:
+                        p2 = passed[0].view(-1, 2)
+                        keeps = [(p2.any(1) if pair == "any" else p2.all(1)).repeat_interleave(2)]
+                    else:
+                        keeps = passed
+                    for s, keep, f in zip(ins, keeps, files):
+                        kept = keep.nonzero().flatten()
+                        lens = s.idx[4 * kept + 4] - s.idx[4 * kept]
+                        dst = torch.cumsum(lens, 0) - lens
+                        n_kept = int(kept.numel())
+                        total, used = (int(v) for v in torch.stack([lens.sum(), s.idx[4 * n]]).tolist())
+                        tot[1] += n_kept
+                        if total:
+                            if out_dev is None or out_dev.numel() < total:
+                                out_dev = out_host = None
+                                out_dev = torch.empty(total + total // 8, dtype=torch.uint8, device=dev)
+                                out_host = torch.empty(out_dev.numel(), dtype=torch.uint8, pin_memory=True)
+                            timed.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+                            timed[-1][0].record()
+                            rc = L.pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept,
+                                                   out_dev.data_ptr(), out_dev.numel(), _stream_ptr(dev))
+                            timed[-1][1].record()
+                            _lib.check(rc)
+                            out_host[:total].copy_(out_dev[:total], non_blocking=True)
+                            torch.cuda.current_stream(dev).synchronize()
+                            f.write(memoryview(out_host.numpy())[:total])
+                        s.consume(used, n)
+                totals = tot.cpu().tolist()                              # (a host wait: every timed event has happened)
+                device_ms = sum(a.elapsed_time(b) for a, b in timed)
+            for f in files:
+                f.close()
+            for tmp, o in zip(tmps, outs):
+                os.replace(tmp, o)
+        finally:
+            for s in ins:
+                s.close()
+            for f in files:
+                f.close()
+            for tmp in tmps:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "bases": totals[3], "kmers": totals[4], "hits": totals[5],
+                "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
+
     # ------------------------------------------------------------------ summing finished tables (jellyfish merge)
 
     @staticmethod
@@ -1715,6 +1967,148 @@ class KmerTable:
         return {"n_a": n_a, "n_b": n_b, "n_shared": n_shared, "sum_a": sum_a, "sum_b": sum_b, "sum_min": sum_min,
                 "jaccard": ratio(n_shared, n_a + n_b - n_shared), "containment_a": ratio(n_shared, n_a), "containment_b": ratio(n_shared, n_b),
                 "bray_curtis": 1.0 - 2.0 * sum_min / (sum_a + sum_b) if sum_a + sum_b else 0.0}
+
+
+def _fastq_error(what: str, status: int) -> str:
+    """the message for status[1] of pg_table_read_hits: the malformed record with the smallest ordinal, and why"""
+    record, reason = status >> 8, status & 0xFF
+    why = {_lib.FASTQ_NO_AT: "its first line does not begin with '@'", _lib.FASTQ_NO_PLUS: "its third line does not begin with '+'",
+           _lib.FASTQ_SHORT_QUALITY: "its quality line is shorter than its sequence line",
+           _lib.FASTQ_BAD_INDEX: "the line index does not describe the text"}.get(reason, f"reason {reason}")
+    return f"{what}: record {record}: {why} (PG_EFORMAT)"
+
+
+def _hit_bound(v, name: str) -> tuple:
+    """a hit bound of ``KmerTable.filter_fastq`` as (is a share, value): an int is absolute, a float in [0, 1] a share of n"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"{name} must be an int (absolute) or a float in [0, 1] (a share of the read's k-mers), got {v!r}")
+    if isinstance(v, (int, np.integer)):
+        if v < 0:
+            raise ValueError(f"{name} must be at least 0 (got {v})")
+        return False, int(v)
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"{name} as a share must lie in [0, 1] (got {v})")
+    return True, float(v)
+
+
+def _bound_holds(h: torch.Tensor, n: torch.Tensor, bound: tuple, at_least: bool) -> torch.Tensor:
+    """h >= bound (``at_least``) or h <= bound, element-wise; a share is compared as h against f * n in IEEE double (h, n < 2^32:
+    both sides exact before the product is rounded once, as numpy rounds it)"""
+    share, v = bound
+    ref = n.to(torch.float64) * v if share else v
+    left = h.to(torch.float64) if share else h
+    return left >= ref if at_least else left <= ref
+
+
+def _temp_beside(path: str) -> tuple:
+    """(file open for writing, its name): a new file of a name nobody else has, in the directory of ``path`` (so that it can be
+    moved into place), with the mode a plain ``open`` would have given it"""
+    import tempfile
+    fd, tmp = tempfile.mkstemp(dir=os.path.dirname(os.path.abspath(path)), prefix=os.path.basename(path) + ".", suffix=".tmp")
+    mask = os.umask(0)
+    os.umask(mask)
+    os.chmod(tmp, 0o666 & ~mask)
+    return os.fdopen(fd, "wb"), tmp
+
+
+def _filter_round(ins: list, mates: bool, pair: str) -> tuple:
+    """what one round of ``KmerTable.filter_fastq`` takes of its indexed pieces: (records per input, the error that ends the call
+    once those records are found well-formed or None, every input has ended).  The records are the whole ones every piece
+    holds -- an even number of them for interleaved mates while the file goes on.  Pending errors: an input that ends inside a
+    record, R1 / R2 of which one ends (at a record boundary) while the other holds more, an odd record count under any / both."""
+    n = min(s.n_rec for s in ins)
+    all_eof = all(s.eof for s in ins)
+    pending = None
+    if len(ins) == 2:
+        for s, o in ((ins[0], ins[1]), (ins[1], ins[0])):
+            if pending is None and s.eof and s.n_rec == n and not s.n_lines % 4 and (o.n_rec > n or (o.eof and o.n_lines > 4 * n)):
+                pending = f"{s.path} ends after {s.done + n} records, {o.path} holds more: R1 and R2 must have the same number of records (PG_EFORMAT)"
+    for s in ins:
+        if pending is None and s.eof and s.n_rec == n and s.n_lines % 4:
+            pending = f"{s.path}: record {s.done + n}: the file ends inside it ({s.n_lines % 4} of its 4 lines) (PG_EFORMAT)"
+    if len(ins) == 1 and mates and n & 1:
+        if all_eof:
+            pending = pending or (f"{ins[0].path}: record {ins[0].done + n - 1} has no mate: {ins[0].done + n} records are an odd number "
+                                  f"(pair={pair!r} takes records 2i and 2i + 1 as mates; PG_EFORMAT)")
+        else:
+            n -= 1
+    return n, pending, all_eof
+
+
+class _FastqPieces:
+    """one input of ``KmerTable.filter_fastq``: the file (plain or gzip, told by its first two bytes), the pinned buffer its pieces
+    are read into, the piece on the device and its line index.  The buffers are no larger than the input asks: a plain file's
+    size is known, a gzip file's buffer starts at ``START`` bytes and doubles up to the piece while the file goes on"""
+    START = 1 << 20
+
+    def __init__(self, path: str, piece: int):
+        self.path = path
+        self.f = None
+        with open(path, "rb") as probe:
+            packed = probe.read(2) == b"\x1f\x8b"
+        if packed:
+            import gzip
+            self.f = gzip.open(path, "rb")
+            self.limit, piece = piece, min(piece, self.START)
+        else:
+            self.f = open(path, "rb", buffering=0)
+            piece = max(64, min(piece, os.path.getsize(path) + 1))       # (a small file: one piece of its own size, and the end seen at once)
+            self.limit = piece
+        self.cap = piece
+        self.host = torch.empty(piece, dtype=torch.uint8, pin_memory=True)
+        self.buf = self.host.numpy()
+        self.text = None
+        self.have, self.eof, self.done = 0, False, 0     # bytes in the buffer, the file has ended, records of earlier pieces
+        self.hold = {}
+        self.idx, self.n_lines, self.n_rec = None, 0, 0
+
+    def fill(self) -> None:
+        while not self.eof:
+            if self.have == self.cap:
+                if self.cap >= self.limit:
+                    break
+                self._resize(min(2 * self.cap, self.limit))          # (a buffer that began small: up to the piece)
+            got = self.f.readinto(memoryview(self.buf)[self.have:self.cap])
+            if not got:
+                self.eof = True
+            else:
+                self.have += got
+
+    def _resize(self, cap: int) -> None:
+        host = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
+        host[:self.have] = self.host[:self.have]
+        self.cap, self.host, self.buf = cap, host, host.numpy()
+
+    def grow(self) -> None:
+        """twice the piece: a record (a pair of them) that no piece holds"""
+        self.limit = 2 * self.cap
+        self._resize(self.limit)
+
+    def index(self, table: "KmerTable") -> None:
+        """the piece to the device, its lines counted and indexed; n_rec = the records that are whole (before the end of the file
+        a line without its newline is not yet a line)"""
+        if self.have == 0:
+            self.n_lines = self.n_rec = 0
+            return
+        if self.text is None or self.text.numel() < self.cap + 16:
+            self.text = None
+            self.text = torch.empty(self.cap + 16, dtype=torch.uint8, device=table.device)
+        self.text[:self.have].copy_(self.host[:self.have], non_blocking=True)
+        self.idx, self.n_lines = table._line_index(self.text, self.have, self.hold)
+        whole = self.n_lines if self.eof else self.n_lines - int(self.buf[self.have - 1] != 10)
+        self.n_rec = whole // 4
+
+    def consume(self, used: int, n_records: int) -> None:
+        """the first ``used`` bytes (``n_records`` records) are dealt with: what lies behind them moves to the front"""
+        rest = self.have - used
+        if rest:
+            self.buf[:rest] = self.buf[used:self.have].copy()
+        self.have, self.done = rest, self.done + n_records
+
+    def close(self) -> None:
+        if self.f is not None:
+            self.f.close()
+            self.f = None
 
 
 def encode_kmers(strings, k: int) -> np.ndarray:
