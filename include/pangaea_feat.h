@@ -500,6 +500,58 @@ int pg_fastq_gather(const uint8_t *text, int64_t n_bytes, const int64_t *line_st
                     const int64_t *dst_off, int64_t n_kept, uint8_t *out, int64_t out_bytes, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Reads of a FASTQ text trimmed to their solid span (device; one GPU, any of the five kinds; the table is only read).  The second
+ * mode of the tools the section above is modelled on -- `kmc_tools filter -t`, khmer's filter-abund / trim-low-abund: a read
+ * is cut down to the part the table vouches for and not dropped, so that a read with one sequencing error keeps its good
+ * bases.  Beside the same step of the reference, scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp.  INPUT, K-MERS, the count
+ * window lower <= c <= upper, lowercase_is_base and min_qual_char are exactly those of pg_table_read_hits.  Both entries are
+ * additive to ABI 9; every argument is checked before the first HIP call (PG_EINVAL with a pg_last_error text: a null pointer
+ * by name, a k that is not the table's, lower > upper, negative sizes, a mode that is none, a text base that is not 16-byte
+ * aligned, n_kept outside [0, n_records]).
+ *   SOLID    position i of a sequence line is solid iff it holds a k-mer and that k-mer's stored count is inside the window.  A
+ *            position that holds no k-mer -- an 'N', a '\r', a masked base among its k bytes, or i + k > length -- is not solid.
+ *   RUN      a maximal interval [a, b) of solid positions; its SPAN is the bases [a, b + k - 1): start a, length b - a + k - 1.
+ *   MODE     PG_SPAN_FIRST: the run that begins at position 0 (`kmc_tools filter -t` / khmer: cut at the first k-mer outside
+ *            the window); the empty span (0, 0) if position 0 is not solid.  PG_SPAN_LONGEST: the longest run, among equals
+ *            the leftmost; (0, 0) if the record has no solid position.
+ *   N, H     those of pg_table_read_hits, over the whole line in both modes (FIRST takes no early exit: one pass gives hits and
+ *            span, and the totals stay exact).
+ *   CR       cr_s = 1 iff the sequence line is non-empty and its last byte is '\r'; cr_q the same for the quality line's
+ *            content (the line without its '\n').
+ *   TRIMMED  the record cut to its span (start, length): line 0 verbatim with its newline; seq[start : start + length], '\r'
+ *            if cr_s, '\n'; line 2 verbatim; qual[start : start + length], '\r' if cr_q, '\n' iff the record ended in one.
+ *            Quality bytes beyond the sequence's length are dropped: the output is always a well-formed record.
+ *   SHORT    qual_len - cr_q < seq_len - cr_s is malformed (PG_FASTQ_SHORT_QUALITY) ALWAYS here, not only under min_qual_char:
+ *            the quality line is cut too.  (Under min_qual_char the rule of pg_table_read_hits holds as well.)
+ *   pg_table_read_spans      beside scripts/low_abd_reads.sh:10 / extract_unmapped.cpp (its decision which read to keep; here which
+ *                            part of it): spans[r] = n, h, start, length of record r < n_records and trimmed_bytes[r] = the bytes
+ *                            of its trimmed record, (s1 - s0) + length + cr_s + 1 + (s3 - s2) + length + cr_q + nl with s0 .. s3
+ *                            its four line starts and nl = 1 iff it ends in '\n'.  One wavefront per record, any read length;
+ *                            status as pg_table_read_hits writes it (the same two words, the same reasons).  A malformed
+ *                            record's row is 0, 0, 0, 0 and its trimmed_bytes 0.  n_records == 0: PG_OK, nothing launched,
+ *                            nothing written.
+ *   pg_fastq_gather_trimmed  beside scripts/low_abd_reads.sh:10 / extract_unmapped.cpp (its writing of the chosen reads): the
+ *                            trimmed record of r = kept[i], span spans[r][2], spans[r][3], goes to out + dst_off[i] for
+ *                            i < n_kept; dst_off is the caller's exclusive scan of trimmed_bytes over the kept records.  One
+ *                            wavefront per kept record.  cr_s, cr_q, nl are read from the text again and everything handed in
+ *                            is checked: a record is skipped when r is out of range, its index is not monotone inside the
+ *                            text, start + length exceeds the sequence's or the quality's bases, or its bytes do not fit
+ *                            [dst_off[i], out_bytes).  Nothing outside [0, n_bytes) of the text is read and nothing outside
+ *                            [0, out_bytes) of out written.  n_kept == 0: PG_OK, nothing launched.
+ * Which records are written -- span length >= min_len, the pair rule -- is the caller's (KmerTable.trim_fastq).
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_SPAN_FIRST 0
+#define PG_SPAN_LONGEST 1
+int pg_table_read_spans(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                        int64_t first_record, int64_t lower, int64_t upper /* < 0: none */, int lowercase_is_base,
+                        int min_qual_char /* 0: none */, int mode,
+                        uint32_t *spans /* device, [n_records][4]: n, h, start, length */,
+                        int64_t *trimmed_bytes /* device, [n_records] */, uint64_t *status /* device [2] */, void *stream);
+int pg_fastq_gather_trimmed(const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                            const int64_t *kept, const uint32_t *spans /* [n_records][4] */, const int64_t *dst_off,
+                            int64_t n_kept, uint8_t *out, int64_t out_bytes, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
  * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
  * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for

@@ -12,6 +12,8 @@
     kmer_table depth {-i F | -1 F -2 F | -g DUMP} -k K -s SEQS.fa[.gz] [-L LOWER] -o OUT.tsv
     kmer_table filter {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} [-L LOWER] [-U UPPER] [--min-hits X] [--max-hits X]
                       [--pair any|both|single] [--min-qual-char C] -o OUT [-o2 OUT2]      (one JSON line on stdout)
+    kmer_table trim {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} [-L LOWER] [-U UPPER] [--mode first|longest] [--min-len N]
+                    [--pair any|both|single] [--min-qual-char C] -o OUT [-o2 OUT2]        (one JSON line on stdout)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -161,21 +163,20 @@ def _hit_bound_arg(text: str, flag: str):
     return v
 
 
-def _filter_plan(a) -> tuple:
-    """the checked arguments of ``kmer_table filter``: (table source, reads, keyword arguments of ``KmerTable.filter_fastq``) -- the
-    table source is ("dump", path), ("reads", r1, r2 or None) or None (the table of the reads themselves).  Nothing is opened
-    but the question whether the inputs exist."""
+def _reads_checks(a, verb: str) -> None:
+    """what ``kmer_table filter`` and ``kmer_table trim`` refuse alike about k, the table's source, the reads, the outputs, the pair
+    rule, the count window and the quality threshold"""
     from . import _lib
     if not 1 <= a.kmer <= _lib.WIDE_MAX_K:
         raise ValueError(f"k-mer size {a.kmer} unsupported (1..{_lib.WIDE_MAX_K})")
     if bool(a.table1) != bool(a.table2):
         raise ValueError("-t1 and -t2 go together")
     if sum((bool(a.global_), bool(a.table_interleaved), bool(a.table1))) > 1:
-        raise ValueError("filter takes the table from one source: -g DUMP, -ti F or -t1 F -t2 F (none: the reads themselves)")
+        raise ValueError(f"{verb} takes the table from one source: -g DUMP, -ti F or -t1 F -t2 F (none: the reads themselves)")
     if bool(a.reads1) != bool(a.reads2):
         raise ValueError("-1 and -2 go together")
     if bool(a.interleaved) == bool(a.reads1):
-        raise ValueError("the reads to filter are -i F or -1 F -2 F (one of the two)")
+        raise ValueError(f"the reads to {verb} are -i F or -1 F -2 F (one of the two)")
     if a.reads1 and not a.output2:
         raise ValueError("-1 F -2 F writes two files: -o OUT -o2 OUT2")
     if a.interleaved and a.output2:
@@ -190,9 +191,12 @@ def _filter_plan(a) -> tuple:
         raise ValueError(f"-U ({a.upper}) is below -L ({a.lower})")
     if a.min_qual_char is not None and len(a.min_qual_char) != 1:
         raise ValueError(f"--min-qual-char takes one character (got {a.min_qual_char!r})")
-    kw = dict(lower=a.lower, upper=a.upper, min_hits=_hit_bound_arg(a.min_hits, "--min-hits"),
-              max_hits=None if a.max_hits is None else _hit_bound_arg(a.max_hits, "--max-hits"), pair=a.pair, min_qual_char=a.min_qual_char,
-              lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+
+
+def _reads_sources(a) -> tuple:
+    """(table source, reads) of ``kmer_table filter`` / ``trim`` once ``_reads_checks`` has passed: the table source is ("dump",
+    path), ("reads", r1, r2 or None) or None (the table of the reads themselves), the reads (r1, r2 or None, out1, out2 or None).
+    Nothing is opened but the question whether the inputs exist."""
     reads = (a.interleaved, None, a.output, None) if a.interleaved else (a.reads1, a.reads2, a.output, a.output2)
     for o in reads[2:]:
         if o and o.endswith(".gz"):
@@ -202,14 +206,41 @@ def _filter_plan(a) -> tuple:
     for f in [x for x in reads[:2] if x] + ([x for x in source[1:] if x] if source else []):
         if not os.path.isfile(f):
             raise ValueError(f"{f}: no such file")
+    return source, reads
+
+
+def _filter_plan(a) -> tuple:
+    """the checked arguments of ``kmer_table filter``: (table source, reads, keyword arguments of ``KmerTable.filter_fastq``) -- the
+    table source is ("dump", path), ("reads", r1, r2 or None) or None (the table of the reads themselves).  Nothing is opened
+    but the question whether the inputs exist."""
+    _reads_checks(a, "filter")
+    kw = dict(lower=a.lower, upper=a.upper, min_hits=_hit_bound_arg(a.min_hits, "--min-hits"),
+              max_hits=None if a.max_hits is None else _hit_bound_arg(a.max_hits, "--max-hits"), pair=a.pair, min_qual_char=a.min_qual_char,
+              lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+    source, reads = _reads_sources(a)
+    return source, reads, kw
+
+
+def _trim_plan(a) -> tuple:
+    """the checked arguments of ``kmer_table trim``: (table source, reads, keyword arguments of ``KmerTable.trim_fastq``), as
+    ``_filter_plan`` gives them.  Nothing is opened but the question whether the inputs exist."""
+    _reads_checks(a, "trim")
+    if a.mode not in ("first", "longest"):
+        raise ValueError(f"--mode must be first or longest (got {a.mode!r})")
+    if a.min_len is not None and a.min_len < 1:
+        raise ValueError(f"--min-len must be at least 1 (got {a.min_len})")
+    kw = dict(lower=a.lower, upper=a.upper, mode=a.mode, min_len=a.min_len, pair=a.pair, min_qual_char=a.min_qual_char,
+              lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+    source, reads = _reads_sources(a)
     return source, reads, kw
 
 
 def _kmer_table_filter(a) -> int:
+    """``kmer_table filter`` and ``kmer_table trim``: the table from its source, the call, one JSON line"""
     import json
     import torch
     from .kmer import KmerTable
-    source, (r1, r2, o1, o2), kw = _filter_plan(a)
+    source, (r1, r2, o1, o2), kw = _trim_plan(a) if a.cmd == "trim" else _filter_plan(a)
     device = torch.device("cuda", torch.cuda.current_device())
     if source is None:
         table = _counted(r1, r2, a.kmer, device)
@@ -217,7 +248,7 @@ def _kmer_table_filter(a) -> int:
         table = KmerTable.from_dump(source[1], a.kmer, device)
     else:
         table = _counted(source[1], source[2], a.kmer, device)
-    res = table.filter_fastq(r1, o1, r2, o2, **kw)
+    res = table.trim_fastq(r1, o1, r2, o2, **kw) if a.cmd == "trim" else table.filter_fastq(r1, o1, r2, o2, **kw)
     sys.stdout.write(json.dumps(res) + "\n")
     return 0
 
@@ -266,23 +297,29 @@ def _kmer_table_parser() -> _Parser:
             q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
             q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
             q.add_argument("-o", "--output", required=True)
-    q = sub.add_parser("filter")
-    q.add_argument("-g", "--global", dest="global_", default="")
-    q.add_argument("-ti", "--table-interleaved", dest="table_interleaved", default="")
-    q.add_argument("-t1", "--table-reads1", dest="table1", default="")
-    q.add_argument("-t2", "--table-reads2", dest="table2", default="")
-    q.add_argument("-k", "--kmer", type=int, required=True)
-    q.add_argument("-i", "--interleaved", default="")
-    q.add_argument("-1", "--reads1", default="")
-    q.add_argument("-2", "--reads2", default="")
-    q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
-    q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
-    q.add_argument("--min-hits", dest="min_hits", default="1")
-    q.add_argument("--max-hits", dest="max_hits", default=None)
-    q.add_argument("--pair", default="any")
-    q.add_argument("--min-qual-char", dest="min_qual_char", default=None)
-    q.add_argument("-o", "--output", required=True)
-    q.add_argument("-o2", "--output2", default="")
+    for name in ("filter", "trim"):
+        q = sub.add_parser(name)
+        q.add_argument("-g", "--global", dest="global_", default="")
+        q.add_argument("-ti", "--table-interleaved", dest="table_interleaved", default="")
+        q.add_argument("-t1", "--table-reads1", dest="table1", default="")
+        q.add_argument("-t2", "--table-reads2", dest="table2", default="")
+        q.add_argument("-k", "--kmer", type=int, required=True)
+        q.add_argument("-i", "--interleaved", default="")
+        q.add_argument("-1", "--reads1", default="")
+        q.add_argument("-2", "--reads2", default="")
+        q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
+        q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
+        if name == "filter":
+            q.add_argument("--min-hits", dest="min_hits", default="1")
+            q.add_argument("--max-hits", dest="max_hits", default=None)
+            q.add_argument("--pair", default="any")
+        else:
+            q.add_argument("--mode", default="longest")
+            q.add_argument("--min-len", dest="min_len", type=int, default=None)
+            q.add_argument("--pair", default="both")
+        q.add_argument("--min-qual-char", dest="min_qual_char", default=None)
+        q.add_argument("-o", "--output", required=True)
+        q.add_argument("-o2", "--output2", default="")
     return p
 
 
@@ -316,11 +353,18 @@ def main_kmer_table(argv=None) -> int:
     ``--max-hits``, each a whole number or, written with a '.', a share of the read's k-mers; ``--pair any`` (the default) keeps
     both mates if either passes, ``both`` if both do, ``single`` judges every record of ``-i`` on its own; ``--min-qual-char C``:
     bases of quality below C are no bases.  One JSON line on stdout: records, kept, passed, bases, kmers, hits, seconds, device_ms.
+    ``kmer_table trim``: the same reads, table sources and count window, but every written read is CUT to its solid span and not
+    copied whole (``KmerTable.trim_fastq``; what `kmc_tools filter -t` and khmer's filter-abund do): a position is solid iff its
+    k-mer's count lies in [LOWER, UPPER], ``--mode longest`` (the default) keeps the bases of the longest run of solid positions,
+    ``first`` those in front of the first k-mer outside the window; name and ``+`` line stay, sequence and quality are cut alike
+    and keep their line ends.  A read passes iff its span has at least ``--min-len`` bases (default K); ``--pair both`` (the
+    default here: a mate kept under ``any`` that did not pass is written too, possibly empty), ``any``, ``single`` as for filter.
+    One JSON line on stdout: records, kept, passed, trimmed, bases, bases_out, kmers, hits, seconds, device_ms.
     Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
     a = _kmer_table_parser().parse_args(argv)
     from . import _lib
     try:
-        if a.cmd == "filter":
+        if a.cmd in ("filter", "trim"):
             return _kmer_table_filter(a)
         if a.cmd in ("combine", "compare"):
             for side, g, i in (("A", a.global_a, a.interleaved_a), ("B", a.global_b, a.interleaved_b)):

@@ -1241,6 +1241,75 @@ __device__ __forceinline__ void wave_lds_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// the record's malformation, or 0, from its five line starts (an index that is none -- outside the contract -- is a bad record
+// too: nothing outside the text is read).  *len = the sequence line's bytes.  read_spans_kernel asks the same questions, and
+// more, in one round trip of its own
+__device__ __forceinline__ uint32_t fastq_record_check(const uint8_t *__restrict__ text, int64_t n_bytes, int64_t s0, int64_t s1, int64_t s2, int64_t s3,
+                                                       int64_t s4, uint32_t min_qual, int64_t *len)
+{
+    *len = 0;
+    if (!(s0 >= 0 && s0 < s1 && s1 < s2 && s2 < s3 && s3 <= s4 && s4 <= n_bytes)) return PG_FASTQ_BAD_INDEX;
+    if (text[s0] != '@') return PG_FASTQ_NO_AT;
+    if (text[s2] != '+') return PG_FASTQ_NO_PLUS;
+    *len = s2 - 1 - s1;                                      // (the sequence line ends with the newline in front of the '+' line)
+    if (min_qual) {
+        const int64_t qlen = s4 - s3 - (s4 > s3 && text[s4 - 1] == '\n');
+        if (qlen < *len) return PG_FASTQ_SHORT_QUALITY;
+    }
+    return 0;
+}
+
+// a malformed record to the two status words (one lane calls this)
+__device__ __forceinline__ void fastq_record_bad(unsigned long long *status, int64_t ordinal, uint32_t bad)
+{
+    atomicMin(&status[1], ((unsigned long long)ordinal << 8) | bad);
+    atomicOr(&status[0], (unsigned long long)PG_STATUS_FASTQ_FORMAT);
+}
+
+// the batch that begins at position `base` of a sequence line of `len` bytes, staged into the wavefront's stream words
+__device__ __forceinline__ void hits_stage(const uint8_t *__restrict__ text, int64_t s1, int64_t s3, int64_t len, int64_t base, int lane, int lenient,
+                                           uint32_t min_qual, uint64_t *wc, uint32_t *wv)
+{
+#pragma unroll
+    for (int u = 0; u < HITS_TURNS; ++u) {
+        if (base + 64 * u >= len) break;                     // (the same for the whole wavefront; no k-mer of the line reaches these words)
+        const int64_t j = base + 64 * u + lane;
+        uint32_t ch = 0;
+        bool ok = false;
+        if (j < len) {
+            ch = text[s1 + j];
+            const uint32_t up = lenient ? ch & 0xDFu : ch;
+            ok = up == 'A' || up == 'C' || up == 'G' || up == 'T';
+            if (ok && min_qual) ok = text[s3 + j] >= min_qual;               // (a base: j is below the quality line's length)
+        }
+        const uint64_t v = __ballot(ok), b0 = __ballot((ch >> 1) & 1u), b1 = __ballot((ch >> 2) & 1u);
+        if (lane < 2) {
+            wc[2 * u + lane] = spread_bits((uint32_t)(b0 >> (32 * lane))) | (spread_bits((uint32_t)(b1 >> (32 * lane))) << 1);
+            wv[2 * u + lane] = (uint32_t)(v >> (32 * lane));
+        }
+    }
+    wave_lds_sync();
+}
+
+// the staged batch looked up: have[u] = position base + 64 u + lane holds a k-mer, c[u] = its stored count (0 without one).  All
+// first probes are issued before any is resolved
+template <int TK>
+__device__ __forceinline__ void hits_lookup(const uint64_t *wc, const uint32_t *wv, int64_t base, int64_t n_pos, int lane, int k, uint64_t kmask,
+                                            const uint32_t *__restrict__ dense, const HashView &t, bool (&have)[DEPTH_BATCH], uint32_t (&c)[DEPTH_BATCH])
+{
+    Lookup<TK> p[DEPTH_BATCH];
+#pragma unroll
+    for (int u = 0; u < DEPTH_BATCH; ++u) {
+        const int g = lane + 64 * u;
+        uint64_t canon = 0;
+        p[u].key = p[u].hh = p[u].cur = 0;
+        have[u] = base + g < n_pos && kmer_at(wc, wv, g, k, kmask, &canon);
+        if (have[u]) p[u].issue(canon, k, dense, t);
+    }
+#pragma unroll
+    for (int u = 0; u < DEPTH_BATCH; ++u) c[u] = have[u] ? p[u].resolve(t) : 0u;
+}
+
 template <int TK>
 __global__ __launch_bounds__(BLOCK) void read_hits_kernel(const uint8_t *__restrict__ text, int64_t n_bytes, const long long *__restrict__ line_start,
                                                           int64_t n_records, int64_t first_record, int k, uint64_t lower, uint64_t upper, int lenient,
@@ -1256,23 +1325,11 @@ __global__ __launch_bounds__(BLOCK) void read_hits_kernel(const uint8_t *__restr
     const int64_t n_waves = (int64_t)gridDim.x * WAVES;
     for (int64_t r = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6); r < n_records; r += n_waves) {
         const int64_t s0 = line_start[4 * r], s1 = line_start[4 * r + 1], s2 = line_start[4 * r + 2], s3 = line_start[4 * r + 3], s4 = line_start[4 * r + 4];
-        uint32_t bad = 0;
-        int64_t len = 0;
-        // (an index that is none -- outside the contract -- is a bad record too: nothing outside the text is read)
-        if (!(s0 >= 0 && s0 < s1 && s1 < s2 && s2 < s3 && s3 <= s4 && s4 <= n_bytes)) bad = PG_FASTQ_BAD_INDEX;
-        else if (text[s0] != '@') bad = PG_FASTQ_NO_AT;
-        else if (text[s2] != '+') bad = PG_FASTQ_NO_PLUS;
-        else {
-            len = s2 - 1 - s1;                               // (the sequence line ends with the newline in front of the '+' line)
-            if (min_qual) {
-                const int64_t qlen = s4 - s3 - (s4 > s3 && text[s4 - 1] == '\n');
-                if (qlen < len) bad = PG_FASTQ_SHORT_QUALITY;
-            }
-        }
+        int64_t len;
+        const uint32_t bad = fastq_record_check(text, n_bytes, s0, s1, s2, s3, s4, min_qual, &len);
         if (bad) {                                           // (the same for the whole wavefront)
             if (lane == 0) {
-                atomicMin(&status[1], ((unsigned long long)(first_record + r) << 8) | bad);
-                atomicOr(&status[0], (unsigned long long)PG_STATUS_FASTQ_FORMAT);
+                fastq_record_bad(status, first_record + r, bad);
                 out[2 * r] = out[2 * r + 1] = 0;
             }
             continue;
@@ -1280,40 +1337,14 @@ __global__ __launch_bounds__(BLOCK) void read_hits_kernel(const uint8_t *__restr
         const int64_t n_pos = len >= k ? len - k + 1 : 0;
         uint32_t n = 0, h = 0;
         for (int64_t base = 0; base < n_pos; base += 64 * DEPTH_BATCH) {
-#pragma unroll
-            for (int u = 0; u < HITS_TURNS; ++u) {
-                if (base + 64 * u >= len) break;             // (the same for the whole wavefront; no k-mer of the line reaches these words)
-                const int64_t j = base + 64 * u + lane;
-                uint32_t ch = 0;
-                bool ok = false;
-                if (j < len) {
-                    ch = text[s1 + j];
-                    const uint32_t up = lenient ? ch & 0xDFu : ch;
-                    ok = up == 'A' || up == 'C' || up == 'G' || up == 'T';
-                    if (ok && min_qual) ok = text[s3 + j] >= min_qual;       // (j < len <= the quality line's length)
-                }
-                const uint64_t v = __ballot(ok), b0 = __ballot((ch >> 1) & 1u), b1 = __ballot((ch >> 2) & 1u);
-                if (lane < 2) {
-                    wc[2 * u + lane] = spread_bits((uint32_t)(b0 >> (32 * lane))) | (spread_bits((uint32_t)(b1 >> (32 * lane))) << 1);
-                    wv[2 * u + lane] = (uint32_t)(v >> (32 * lane));
-                }
-            }
-            wave_lds_sync();
-            Lookup<TK> p[DEPTH_BATCH];
+            hits_stage(text, s1, s3, len, base, lane, lenient, min_qual, wc, wv);
             bool have[DEPTH_BATCH];
+            uint32_t c[DEPTH_BATCH];
+            hits_lookup<TK>(wc, wv, base, n_pos, lane, k, kmask, dense, t, have, c);
 #pragma unroll
             for (int u = 0; u < DEPTH_BATCH; ++u) {
-                const int g = lane + 64 * u;
-                uint64_t canon = 0;
-                p[u].key = p[u].hh = p[u].cur = 0;
-                have[u] = base + g < n_pos && kmer_at(wc, wv, g, k, kmask, &canon);
-                if (have[u]) p[u].issue(canon, k, dense, t);
-            }
-#pragma unroll
-            for (int u = 0; u < DEPTH_BATCH; ++u) {
-                const uint32_t c = have[u] ? p[u].resolve(t) : 0u;
                 n += (uint32_t)__popcll(__ballot(have[u]));
-                h += (uint32_t)__popcll(__ballot(have[u] && c >= lower && c <= upper));
+                h += (uint32_t)__popcll(__ballot(have[u] && c[u] >= lower && c[u] <= upper));
             }
             wave_lds_sync();                                 // (the next batch stages over these words)
         }
@@ -1326,6 +1357,24 @@ __global__ __launch_bounds__(BLOCK) void read_hits_kernel(const uint8_t *__restr
 // whole 16-byte pieces (each read from wherever it lies in the source), the fewer than 16 bytes in front of the first aligned
 // piece and behind the last byte-wise, as table_dump_text_kernel places its units.  No byte outside [0, n_bytes) of the text is
 // read and none outside [0, out_bytes) of `out` written, whatever the device arrays say.
+
+// len bytes from src to dst by one wavefront (the caller has checked both ranges)
+__device__ __forceinline__ void wave_copy(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, int64_t len, int lane)
+{
+    int64_t head = (int64_t)((16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u);
+    if (head > len) head = len;
+    const int64_t n16 = (len - head) >> 4, tail = len - head - (n16 << 4);
+    for (int64_t q = lane; q < n16; q += 64) {
+        uint4 v;
+        __builtin_memcpy(&v, src + head + (q << 4), 16);                      // (no alignment is promised for the source)
+        *(uint4 *)(dst + head + (q << 4)) = v;
+    }
+    if (lane < head + tail) {
+        const int64_t o = lane < head ? lane : len - tail + (lane - head);
+        dst[o] = src[o];
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void fastq_gather_kernel(const uint8_t *__restrict__ text, int64_t n_bytes, const long long *__restrict__ line_start,
                                                              int64_t n_records, const long long *__restrict__ kept, const long long *__restrict__ dst_off,
                                                              int64_t n_kept, uint8_t *__restrict__ out, int64_t out_bytes)
@@ -1337,21 +1386,155 @@ __global__ __launch_bounds__(BLOCK) void fastq_gather_kernel(const uint8_t *__re
         if (r < 0 || r >= n_records) continue;
         const int64_t a = line_start[4 * r], b = line_start[4 * r + 4], d = dst_off[i];
         if (a < 0 || b < a || b > n_bytes || d < 0 || d > out_bytes - (b - a)) continue;
-        const int64_t len = b - a;
-        const uint8_t *src = text + a;
-        uint8_t *dst = out + d;
-        int64_t head = (int64_t)((16u - (uint32_t)((uintptr_t)dst & 15u)) & 15u);
-        if (head > len) head = len;
-        const int64_t n16 = (len - head) >> 4, tail = len - head - (n16 << 4);
-        for (int64_t q = lane; q < n16; q += 64) {
-            uint4 v;
-            __builtin_memcpy(&v, src + head + (q << 4), 16);                  // (no alignment is promised for the source)
-            *(uint4 *)(dst + head + (q << 4)) = v;
+        wave_copy(out + d, text + a, b - a, lane);
+    }
+}
+
+// ---- 4. the solid span of every record: read_hits_kernel's staging and lookups, and per turn of a batch the ballot of
+// have && in-window -- 64 solid flags in position order, the same in every lane -- walked for its runs.  The walk keeps (start,
+// length) of the run that is open at the word's first position and of the best run closed so far in wave-uniform registers, so
+// a run may begin in one word and end any number of words or batches later; ctz of the word and of its complement jump from
+// one run boundary to the next.  The flags never touch LDS and no lane loops over positions.  A closed run replaces the best
+// only when it is LONGER (ties keep the earlier one) and, in PG_SPAN_FIRST mode, only when it began at position 0.  There is no
+// early exit in FIRST mode: n and h are those of read_hits_kernel over the whole line.  Semantics: the header's section "Reads
+// of a FASTQ text trimmed to their solid span".
+struct SpanRuns {
+    uint32_t cur_start, cur_len, best_start, best_len;       // (32 bits, as n and h: a line of 2^32 positions is outside the contract)
+
+    __device__ __forceinline__ void close(int mode)
+    {
+        if (cur_len > best_len && (mode == PG_SPAN_LONGEST || cur_start == 0)) { best_start = cur_start; best_len = cur_len; }
+        cur_len = 0;
+    }
+    // the flags of positions at .. at + 63, lowest bit first (positions without a flag: 0)
+    __device__ __forceinline__ void take(uint64_t w, uint32_t at, int mode)
+    {
+        int pos = 0;
+        while (pos < 64) {
+            const uint64_t gaps = ~(w >> pos);               // (the shift fills with 0: there is a gap at or before bit 64 - pos)
+            const int ones = pos ? __builtin_ctzll(gaps) : gaps ? __builtin_ctzll(gaps) : 64;
+            if (ones) {
+                if (!cur_len) cur_start = at + pos;
+                cur_len += ones;
+                pos += ones;
+                if (pos == 64) break;                        // (the run is open at the word's end)
+            }
+            close(mode);
+            const uint64_t rest = w >> pos;
+            if (!rest) break;
+            pos += __builtin_ctzll(rest);
         }
-        if (lane < head + tail) {
-            const int64_t o = lane < head ? lane : len - tail + (lane - head);
-            dst[o] = src[o];
+    }
+};
+
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void read_spans_kernel(const uint8_t *__restrict__ text, int64_t n_bytes, const long long *__restrict__ line_start,
+                                                           int64_t n_records, int64_t first_record, int k, uint64_t lower, uint64_t upper, int lenient,
+                                                           uint32_t min_qual, int mode, const uint32_t *__restrict__ dense, HashView t,
+                                                           uint32_t *__restrict__ out, long long *__restrict__ trimmed_bytes, unsigned long long *status)
+{
+    __shared__ uint64_t s_codes[WAVES][HITS_WORDS];
+    __shared__ uint32_t s_valid[WAVES][HITS_WORDS];
+    const int lane = threadIdx.x & 63;
+    // (the wavefront's number, in a form the compiler knows to be the same in every lane: the record's index words and everything
+    // derived from them then go through scalar loads and registers, not through 64 lanes that all ask for the same address)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint64_t *wc = s_codes[wave];
+    uint32_t *wv = s_valid[wave];
+    const uint64_t kmask = low_mask<uint64_t>(k);
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES;
+    for (int64_t r = (int64_t)blockIdx.x * WAVES + wave; r < n_records; r += n_waves) {
+        const int64_t s0 = line_start[4 * r], s1 = line_start[4 * r + 1], s2 = line_start[4 * r + 2], s3 = line_start[4 * r + 3], s4 = line_start[4 * r + 4];
+        // the record's check, as fastq_record_check makes it, and its line ends.  Every byte looked at -- '@', '+', the last of the
+        // sequence line, the last two of the record -- has its address from the index alone, so all five loads leave together:
+        // one round trip in front of the characters, not one per question
+        uint32_t bad = 0;
+        int64_t len = 0;
+        int cr_s = 0, cr_q = 0, nl = 0;
+        if (!(s0 >= 0 && s0 < s1 && s1 < s2 && s2 < s3 && s3 <= s4 && s4 <= n_bytes)) bad = PG_FASTQ_BAD_INDEX;
+        else {
+            len = s2 - 1 - s1;
+            // (s0 <= s1 - 1 <= s2 - 2 and s1 <= s2 - 1 <= s4 - 2: all five lie inside the text, whether or not a line is empty)
+            const uint32_t c0 = text[s0], c2 = text[s2], e_s = text[s2 - 2], e1 = text[s4 - 1], e2 = text[s4 - 2];
+            nl = (s4 > s3) & (e1 == '\n');                    // (& and not &&: no load waits behind a branch on another)
+            const int64_t qlen = s4 - s3 - nl;
+            cr_s = (len > 0) & (e_s == '\r');
+            cr_q = (qlen > 0) & ((nl ? e2 : e1) == '\r');
+            if (c0 != '@') bad = PG_FASTQ_NO_AT;
+            else if (c2 != '+') bad = PG_FASTQ_NO_PLUS;
+            else if ((min_qual && qlen < len) || qlen - cr_q < len - cr_s) bad = PG_FASTQ_SHORT_QUALITY;      // (the quality line is cut too)
+            if (bad) len = 0;
         }
+        if (bad) {                                           // (the same for the whole wavefront)
+            if (lane == 0) {
+                fastq_record_bad(status, first_record + r, bad);
+                trimmed_bytes[r] = 0;
+            }
+            if (lane < 4) out[4 * r + lane] = 0;
+            continue;
+        }
+        const int64_t n_pos = len >= k ? len - k + 1 : 0;
+        uint32_t n = 0, h = 0;
+        SpanRuns runs = {0, 0, 0, 0};
+        for (int64_t base = 0; base < n_pos; base += 64 * DEPTH_BATCH) {
+            hits_stage(text, s1, s3, len, base, lane, lenient, min_qual, wc, wv);
+            bool have[DEPTH_BATCH];
+            uint32_t c[DEPTH_BATCH];
+            hits_lookup<TK>(wc, wv, base, n_pos, lane, k, kmask, dense, t, have, c);
+#pragma unroll
+            for (int u = 0; u < DEPTH_BATCH; ++u) {
+                const uint64_t solid = __ballot(have[u] && c[u] >= lower && c[u] <= upper);
+                n += (uint32_t)__popcll(__ballot(have[u]));
+                h += (uint32_t)__popcll(solid);
+                if (solid | runs.cur_len) runs.take(solid, (uint32_t)(base + 64 * u), mode);
+            }
+            wave_lds_sync();                                 // (the next batch stages over these words)
+        }
+        runs.close(mode);
+        const int64_t length = runs.best_len ? (int64_t)runs.best_len + k - 1 : 0;
+        if (lane < 4) out[4 * r + lane] = lane == 0 ? n : lane == 1 ? h : lane == 2 ? runs.best_start : (uint32_t)length;
+        if (lane == 0) trimmed_bytes[r] = (s1 - s0) + length + cr_s + 1 + (s3 - s2) + length + cr_q + nl;
+    }
+}
+
+// ---- 5. the kept records to their places, each cut to its span (start, length) = spans[r][2], spans[r][3]: line 0 as it is,
+// seq[start : start + length] and its line end, line 2 as it is, qual[start : start + length] and its line end ('\r' where the
+// line had one, the last '\n' iff the record ended in one).  One wavefront per kept record, four wave_copy calls; the line ends
+// are single bytes of their own.  cr_s, cr_q and the final newline are read from the text again, and everything handed in is
+// checked: a record whose r, index, span or destination is not what read_spans_kernel would have given is skipped.  No byte
+// outside [0, n_bytes) of the text is read and none outside [0, out_bytes) of `out` written.
+__global__ __launch_bounds__(BLOCK) void fastq_gather_trimmed_kernel(const uint8_t *__restrict__ text, int64_t n_bytes,
+                                                                     const long long *__restrict__ line_start, int64_t n_records,
+                                                                     const long long *__restrict__ kept, const uint32_t *__restrict__ spans,
+                                                                     const long long *__restrict__ dst_off, int64_t n_kept, uint8_t *__restrict__ out,
+                                                                     int64_t out_bytes)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // (as in read_spans_kernel: scalar loads of what is per record)
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES;
+    for (int64_t i = (int64_t)blockIdx.x * WAVES + wave; i < n_kept; i += n_waves) {
+        const int64_t r = kept[i];
+        if (r < 0 || r >= n_records) continue;
+        const int64_t s0 = line_start[4 * r], s1 = line_start[4 * r + 1], s2 = line_start[4 * r + 2], s3 = line_start[4 * r + 3], s4 = line_start[4 * r + 4];
+        if (!(s0 >= 0 && s0 < s1 && s1 < s2 && s2 < s3 && s3 <= s4 && s4 <= n_bytes)) continue;
+        const int64_t start = spans[4 * r + 2], length = spans[4 * r + 3], d = dst_off[i];
+        const int64_t len = s2 - 1 - s1;
+        // (the three bytes that say how the lines end have their addresses from the index and lie inside the text whether or not a
+        // line is empty -- s0 <= s2 - 2, s1 <= s4 - 2 --: they are loaded together)
+        const uint32_t e_s = text[s2 - 2], e1 = text[s4 - 1], e2 = text[s4 - 2];
+        const int nl = (s4 > s3) & (e1 == '\n');            // (& and not &&: no load waits behind a branch on another)
+        const int64_t qlen = s4 - s3 - nl;
+        const int cr_s = (len > 0) & (e_s == '\r'), cr_q = (qlen > 0) & ((nl ? e2 : e1) == '\r');
+        if (start + length > len - cr_s || start + length > qlen - cr_q) continue;
+        const int64_t size = (s1 - s0) + length + cr_s + 1 + (s3 - s2) + length + cr_q + nl;
+        if (d < 0 || d > out_bytes - size) continue;
+        uint8_t *const seq = out + d + (s1 - s0), *const plus = seq + length + cr_s + 1, *const qual = plus + (s3 - s2);
+        wave_copy(out + d, text + s0, s1 - s0, lane);
+        wave_copy(seq, text + s1 + start, length, lane);
+        wave_copy(plus, text + s2, s3 - s2, lane);
+        wave_copy(qual, text + s3 + start, length, lane);
+        if (lane < cr_s + 1) seq[length + lane] = lane < cr_s ? '\r' : '\n';
+        if (lane < cr_q + nl) qual[length + lane] = lane < cr_q ? '\r' : '\n';
     }
 }
 
@@ -1884,5 +2067,65 @@ extern "C" int pg_fastq_gather(const uint8_t *text, int64_t n_bytes, const int64
     if (n_kept == 0) return PG_OK;
     hipLaunchKernelGGL(fastq_gather_kernel, dim3(grid_for(n_kept, WAVES)), dim3(BLOCK), 0, (hipStream_t)stream, text, n_bytes, (const long long *)line_start,
                        n_records, (const long long *)kept, (const long long *)dst_off, n_kept, out, out_bytes);
+    return check_launch(who);
+}
+
+// ---- reads of a FASTQ text trimmed to their solid span (kernels: 4. and 5. of the section above); beside the read set of
+// scripts/low_abd_reads.sh:10 / extract_unmapped.cpp, replacing nothing
+extern "C" int pg_table_read_spans(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                                   int64_t first_record, int64_t lower, int64_t upper, int lowercase_is_base, int min_qual_char, int mode,
+                                   uint32_t *spans, int64_t *trimmed_bytes, uint64_t *status, void *stream)
+{
+    const char *who = "pg_table_read_spans";
+    if (!t) return pg_fail(PG_EINVAL, "%s: t is null", who);
+    if (!text) return pg_fail(PG_EINVAL, "%s: text is null", who);
+    if (!line_start) return pg_fail(PG_EINVAL, "%s: line_start is null", who);
+    if (!spans) return pg_fail(PG_EINVAL, "%s: spans is null", who);
+    if (!trimmed_bytes) return pg_fail(PG_EINVAL, "%s: trimmed_bytes is null", who);
+    if (!status) return pg_fail(PG_EINVAL, "%s: status is null", who);
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "%s: n_bytes is negative (%lld)", who, (long long)n_bytes);
+    if (n_records < 0) return pg_fail(PG_EINVAL, "%s: n_records is negative (%lld)", who, (long long)n_records);
+    if (first_record < 0) return pg_fail(PG_EINVAL, "%s: first_record is negative (%lld)", who, (long long)first_record);
+    if (lower < 0) return pg_fail(PG_EINVAL, "%s: lower is negative (%lld)", who, (long long)lower);
+    if (upper >= 0 && upper < lower) return pg_fail(PG_EINVAL, "%s: upper %lld is below lower %lld", who, (long long)upper, (long long)lower);
+    if (min_qual_char < 0 || min_qual_char > 255) return pg_fail(PG_EINVAL, "%s: min_qual_char %d is no byte (0: none)", who, min_qual_char);
+    if (mode != PG_SPAN_FIRST && mode != PG_SPAN_LONGEST)
+        return pg_fail(PG_EINVAL, "%s: mode %d is neither PG_SPAN_FIRST nor PG_SPAN_LONGEST", who, mode);
+    if ((uintptr_t)text & 15) return pg_fail(PG_EINVAL, "%s: text is not 16-byte aligned", who);
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (t->k != k) return pg_fail(PG_EINVAL, "%s: k differs (table %d, asked %d)", who, t->k, k);
+    if (n_records == 0) return PG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(status, 0, sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(status + 1, 0xff, sizeof(uint64_t), s) != hipSuccess)
+        return pg_fail(PG_EHIP, "%s: cannot clear the status", who);
+    const ProbeArgs pa = probe_args(t);
+    const int grid = grid_for(n_records, WAVES);
+    const uint64_t up = upper < 0 ? ~0ull : (uint64_t)upper;
+    rc = with_kind(t->kind, [&](auto tk) {
+        return launch(read_spans_kernel<decltype(tk)::value>, dim3(grid), dim3(BLOCK), 0, s, who, text, n_bytes, (const long long *)line_start, n_records,
+                      first_record, k, (uint64_t)lower, up, lowercase_is_base ? 1 : 0, (uint32_t)min_qual_char, mode, pa.dense, pa.view, spans,
+                      (long long *)trimmed_bytes, (unsigned long long *)status);
+    });
+    return rc ? rc : check_launch(who);
+}
+
+extern "C" int pg_fastq_gather_trimmed(const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records, const int64_t *kept,
+                                       const uint32_t *spans, const int64_t *dst_off, int64_t n_kept, uint8_t *out, int64_t out_bytes, void *stream)
+{
+    const char *who = "pg_fastq_gather_trimmed";
+    if (!text) return pg_fail(PG_EINVAL, "%s: text is null", who);
+    if (!line_start) return pg_fail(PG_EINVAL, "%s: line_start is null", who);
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "%s: n_bytes is negative (%lld)", who, (long long)n_bytes);
+    if (n_records < 0) return pg_fail(PG_EINVAL, "%s: n_records is negative (%lld)", who, (long long)n_records);
+    if (n_kept < 0 || n_kept > n_records) return pg_fail(PG_EINVAL, "%s: n_kept %lld outside [0, %lld]", who, (long long)n_kept, (long long)n_records);
+    if (out_bytes < 0) return pg_fail(PG_EINVAL, "%s: out_bytes is negative (%lld)", who, (long long)out_bytes);
+    if (n_kept > 0 && !kept) return pg_fail(PG_EINVAL, "%s: kept is null", who);
+    if (n_kept > 0 && !spans) return pg_fail(PG_EINVAL, "%s: spans is null", who);
+    if (n_kept > 0 && !dst_off) return pg_fail(PG_EINVAL, "%s: dst_off is null", who);
+    if (n_kept > 0 && !out) return pg_fail(PG_EINVAL, "%s: out is null", who);
+    if (n_kept == 0) return PG_OK;
+    hipLaunchKernelGGL(fastq_gather_trimmed_kernel, dim3(grid_for(n_kept, WAVES)), dim3(BLOCK), 0, (hipStream_t)stream, text, n_bytes,
+                       (const long long *)line_start, n_records, (const long long *)kept, spans, (const long long *)dst_off, n_kept, out, out_bytes);
     return check_launch(who);
 }

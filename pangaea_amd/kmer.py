@@ -1579,30 +1579,77 @@ class KmerTable:
         a quality line shorter than its sequence line is malformed -- otherwise the quality line is never looked at.  Malformed
         text (a line count that is no multiple of 4 included) raises ValueError naming the first offending record; a CPU tensor
         RuntimeError.  The table is only read (pg_fastq_index, pg_table_read_hits)."""
+        return self._rows_of_text(text, 2, lambda: self._hits_window(lower, upper, min_qual_char),
+                                  lambda t, n, idx, n_rec, window: self._hits_of(t, n, idx, n_rec, 0, window, bool(lowercase_is_base)))
+
+    def _rows_of_text(self, text: torch.Tensor, width: int, checked, rows_of) -> torch.Tensor:
+        """what ``read_hits`` and ``read_spans`` do with a text on the device: its checks, its line index, the rows
+        ``rows_of(text, n_bytes, idx, n_records, checked())`` -> (int32 [n_records, width], status) widened to int64, and the
+        ValueError for malformed text"""
         if not isinstance(text, torch.Tensor) or text.dtype != torch.uint8 or text.dim() != 1:
             raise TypeError("text must be a one-dimensional uint8 tensor")
         _require_gpu(text, "the FASTQ text")
         self._require_readable()
         if text.device != self.device:
             raise ValueError("text and table are on different devices")
-        window = self._hits_window(lower, upper, min_qual_char)
+        args = checked()
         n = int(text.numel())
         if n == 0:
-            return torch.zeros((0, 2), dtype=torch.int64, device=self.device)
+            return torch.zeros((0, width), dtype=torch.int64, device=self.device)
         text = text.contiguous()
         if text.data_ptr() & 15:                 # (a view into a larger text: the kernels read 16-byte pieces)
             text = text.clone()
         with torch.cuda.device(self.device):
             idx, n_lines = self._line_index(text, n, {})
-            hits, bad = torch.zeros((0, 2), dtype=torch.int32, device=self.device), -1
+            rows, bad = torch.zeros((0, width), dtype=torch.int32, device=self.device), -1
             if n_lines >= 4:
-                hits, status = self._hits_of(text, n, idx, n_lines // 4, 0, window, bool(lowercase_is_base))
+                rows, status = rows_of(text, n, idx, n_lines // 4, args)
                 bad = int(status[1].item())
         if bad != -1:
             raise ValueError(_fastq_error("the text", bad & ((1 << 64) - 1)))
         if n_lines % 4:
             raise ValueError(f"the text: record {n_lines // 4}: the text ends inside it ({n_lines} lines, no multiple of 4) (PG_EFORMAT)")
-        return hits.to(torch.int64) & 0xFFFFFFFF
+        return rows.to(torch.int64) & 0xFFFFFFFF
+
+    @staticmethod
+    def _span_mode(mode) -> int:
+        if mode not in _lib.SPAN_MODES:
+            raise ValueError(f"mode must be first or longest (got {mode!r})")
+        return _lib.SPAN_MODES[mode]
+
+    def _spans_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, window: tuple,
+                  lowercase_is_base: bool, mode: int, status: torch.Tensor | None = None, events: tuple | None = None) -> tuple:
+        """(spans: int32 [n_records, 4] holding the 32-bit n, h, start, length; status: int64 [2]; trimmed bytes: int64
+        [n_records]) of pg_table_read_spans, all on the device; ``status`` and ``events`` as for ``_hits_of``"""
+        dev = self.device
+        spans = torch.empty((n_records, 4), dtype=torch.int32, device=dev)
+        sizes = torch.empty(n_records, dtype=torch.int64, device=dev)
+        if status is None:
+            status = torch.empty(2, dtype=torch.int64, device=dev)
+        lower, upper, mq = window
+        L = _lib.load()
+        if events:
+            events[0].record()
+        rc = L.pg_table_read_spans(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, upper,
+                                   1 if lowercase_is_base else 0, mq, mode, spans.data_ptr(), sizes.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+        if events:
+            events[1].record()
+        _lib.check(rc)
+        return spans, status, sizes
+
+    def read_spans(self, text: torch.Tensor, lower: int = 1, upper: int | None = None, mode: str = "longest", lowercase_is_base: bool = True,
+                   min_qual_char=None) -> torch.Tensor:
+        """(n, h, start, length) of every record of a four-line FASTQ text: int64 [n_records, 4] on the table's device -- n, h as
+        ``read_hits`` gives them, and the record's solid span: position i of the sequence line is SOLID iff it holds a k-mer whose
+        count c in this table satisfies ``lower <= c <= upper``; a run is a maximal interval [a, b) of solid positions and covers
+        the bases [a, b + k - 1).  ``mode`` "longest": the longest run's (start, length) = (a, b - a + k - 1), among equals the
+        leftmost; "first": the run that begins at position 0, i.e. the read up to its first k-mer outside the window
+        (`kmc_tools filter -t`, khmer's filter-abund).  (0, 0) where there is no such run.  ``text``, the k-mer rules and the
+        errors are those of ``read_hits``; in addition a quality line that does not reach as far as its sequence line (line
+        ends aside) is malformed whatever ``min_qual_char`` says, since a trimmed record cuts it too.  The table is only read
+        (pg_fastq_index, pg_table_read_spans)."""
+        return self._rows_of_text(text, 4, lambda: (self._hits_window(lower, upper, min_qual_char), self._span_mode(mode)),
+                                  lambda t, n, idx, n_rec, a: self._spans_of(t, n, idx, n_rec, 0, a[0], bool(lowercase_is_base), a[1])[:2])
 
     def filter_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
                      min_hits=1, max_hits=None, pair: str = "any", lowercase_is_base: bool = True, min_qual_char=None) -> dict:
@@ -1632,29 +1679,59 @@ class KmerTable:
         pg_fastq_gather entries of every piece, each between two device events of its own)."""
         import time
         t0 = time.perf_counter()
-        if pair not in ("any", "both", "single"):
-            raise ValueError(f"pair must be any, both or single (got {pair!r})")
-        if (src2 is None) != (out2 is None):
-            raise ValueError("src2 and out2 go together: two inputs give two outputs")
-        if pair == "single" and src2 is not None:
-            raise ValueError("pair='single' judges the records of ONE file; R1/R2 input is paired")
-        srcs = [os.fspath(src1)] + ([os.fspath(src2)] if src2 is not None else [])
-        outs = [os.fspath(out1)] + ([os.fspath(out2)] if out2 is not None else [])
-        for o in outs:
-            if o.endswith(".gz"):
-                raise ValueError(f"{o}: the kept reads are written as plain text, gzip output is not supported")
-        real_outs = [os.path.realpath(x) for x in outs]
-        if len(set(real_outs)) != len(outs) or set(real_outs) & {os.path.realpath(x) for x in srcs}:
-            raise ValueError("the outputs must differ from each other and from the inputs (got " + ", ".join(outs + srcs) + ")")
+        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
         window = self._hits_window(lower, upper, min_qual_char)
         lo_bound, hi_bound = _hit_bound(min_hits, "min_hits"), None if max_hits is None else _hit_bound(max_hits, "max_hits")
-        lenient = bool(lowercase_is_base)
+        totals, device_ms = self._fastq_pieces(srcs, outs, pair, _HitsStep(self, window, bool(lowercase_is_base), lo_bound, hi_bound))
+        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "bases": totals[3], "kmers": totals[4], "hits": totals[5],
+                "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
+
+    def trim_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
+                   mode: str = "longest", min_len: int | None = None, pair: str = "both", lowercase_is_base: bool = True,
+                   min_qual_char=None) -> dict:
+        """cut the reads of a FASTQ file down to the part this table vouches for (`kmc_tools filter -t`, khmer's filter-abund /
+        trim-low-abund; beside the read set of scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp) and write them, in input
+        order, to ``out1`` (and ``out2``): a read with one sequencing error keeps its good bases where ``filter_fastq`` could only
+        keep the error or drop the read.
+
+        The span of a record -- ``read_spans``: ``mode`` "longest" (the longest run of solid k-mers) or "first" (the read up to its
+        first k-mer outside ``[lower, upper]``) -- is (start, length).  A record PASSES iff length >= ``min_len`` (None: k; at
+        least 1).  ``pair``: "both" (the default) keeps a pair when both mates pass, "any" when either does, "single" judges every
+        record of one file on its own.  EVERY written record is written trimmed to its span: line 0 and line 2 as they are,
+        ``seq[start : start + length]`` and ``qual[start : start + length]`` with the line ends they had (``\\r\\n`` stays
+        ``\\r\\n``, a final record without ``\\n`` leaves without one); quality bytes beyond the sequence are dropped.  That includes a
+        mate kept under "any" that did not pass, possibly with empty sequence and quality lines -- which is why "both" is the
+        default here.  A quality line that does not reach as far as its sequence line is malformed, with or without
+        ``min_qual_char``.  Input forms, pieces, the plain-text output under a temporary name, "after any error no output file is
+        left" and the ValueErrors naming the record's ordinal are those of ``filter_fastq``.
+
+        Returns ``records``, ``kept``, ``passed`` (records that passed on their own), ``trimmed`` (kept records that came out
+        shorter than they went in), ``bases`` (bytes of the sequence lines), ``bases_out`` (bases written), ``kmers``, ``hits`` --
+        totals over all inputs, exact -- and ``seconds`` (wall), ``device_ms`` (the pg_table_read_spans and
+        pg_fastq_gather_trimmed entries of every piece, each between two device events of its own)."""
+        import time
+        t0 = time.perf_counter()
+        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
+        window = self._hits_window(lower, upper, min_qual_char)
+        mode = self._span_mode(mode)
+        if min_len is None:
+            min_len = self.k
+        if isinstance(min_len, bool) or not isinstance(min_len, (int, np.integer)) or min_len < 1:
+            raise ValueError(f"min_len must be a whole number of bases, at least 1 (got {min_len!r})")
+        totals, device_ms = self._fastq_pieces(srcs, outs, pair, _SpansStep(self, window, bool(lowercase_is_base), mode, int(min_len)))
+        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "trimmed": totals[6], "bases": totals[3], "bases_out": totals[7],
+                "kmers": totals[4], "hits": totals[5], "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
+
+    def _fastq_pieces(self, srcs: list, outs: list, pair: str, step) -> tuple:
+        """the piece loop of ``filter_fastq`` and ``trim_fastq``: (totals: records, kept, passed, bases, kmers, hits, trimmed, bases
+        written -- exact ints --, device milliseconds of the timed entries).  ``step`` is what differs between the two: its
+        ``launch`` enqueues the per-record kernel of a piece, its ``judge`` turns the kernel's rows into pass flags and totals, its
+        ``sizes`` gives the bytes each kept record leaves with and its ``gather`` writes them to their places."""
         self._require_readable()
         dev = self.device
-        L = _lib.load()
         piece = self._filter_piece_bytes()
         mates = pair != "single"
-        tot = torch.zeros(6, dtype=torch.int64, device=dev)              # records, kept, passed, bases, kmers, hits
+        tot = torch.zeros(8, dtype=torch.int64, device=dev)
         timed = []                                                       # (event, event) around every timed entry; read at the end
         ins, files, tmps = [], [], []
         try:
@@ -1683,7 +1760,7 @@ class KmerTable:
                         got = []
                         for i, s in enumerate(ins):
                             timed.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                            got.append(self._hits_of(s.text, s.have, s.idx, n, s.done, window, lenient, status[i], timed[-1])[0])
+                            got.append(step.launch(s, n, status[i], timed[-1]))
                         for s, b in zip(ins, status[:, 1].cpu().tolist()):       # (the malformed record in front comes before what is pending)
                             if b != -1:
                                 raise ValueError(_fastq_error(s.path, b & ((1 << 64) - 1)))
@@ -1692,17 +1769,10 @@ class KmerTable:
                     if n == 0:
                         break
                     passed = []
-                    for s, hits in zip(ins, got):
-                        nk, hh = (hits[:, 0].to(torch.int64) & 0xFFFFFFFF), (hits[:, 1].to(torch.int64) & 0xFFFFFFFF)
-                        ok = (nk >= 1) & _bound_holds(hh, nk, lo_bound, True)
-                        if hi_bound is not None:
-                            ok &= _bound_holds(hh, nk, hi_bound, False)
-                        passed.append(ok)
+                    for s, rows in zip(ins, got):
+                        passed.append(step.judge(rows, tot))
                         tot[0] += n
-                        tot[2] += ok.sum()
                         tot[3] += (s.idx[2:4 * n:4] - s.idx[1:4 * n:4] - 1).sum()
-                        tot[4] += nk.sum()
-                        tot[5] += hh.sum()
                     if len(ins) == 2:
                         keep = passed[0] | passed[1] if pair == "any" else passed[0] & passed[1]
                         keeps = [keep, keep]
@@ -1711,9 +1781,9 @@ class KmerTable:
                         keeps = [(p2.any(1) if pair == "any" else p2.all(1)).repeat_interleave(2)]
                     else:
                         keeps = passed
-                    for s, keep, f in zip(ins, keeps, files):
+                    for s, keep, f, rows in zip(ins, keeps, files, got):
                         kept = keep.nonzero().flatten()
-                        lens = s.idx[4 * kept + 4] - s.idx[4 * kept]
+                        lens = step.sizes(s, rows, kept, tot)
                         dst = torch.cumsum(lens, 0) - lens
                         n_kept = int(kept.numel())
                         total, used = (int(v) for v in torch.stack([lens.sum(), s.idx[4 * n]]).tolist())
@@ -1725,8 +1795,7 @@ class KmerTable:
                                 out_host = torch.empty(out_dev.numel(), dtype=torch.uint8, pin_memory=True)
                             timed.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
                             timed[-1][0].record()
-                            rc = L.pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept,
-                                                   out_dev.data_ptr(), out_dev.numel(), _stream_ptr(dev))
+                            rc = step.gather(s, n, rows, kept, dst, n_kept, out_dev)
                             timed[-1][1].record()
                             _lib.check(rc)
                             out_host[:total].copy_(out_dev[:total], non_blocking=True)
@@ -1747,8 +1816,7 @@ class KmerTable:
             for tmp in tmps:
                 if os.path.exists(tmp):
                     os.remove(tmp)
-        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "bases": totals[3], "kmers": totals[4], "hits": totals[5],
-                "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
+        return totals, device_ms
 
     # ------------------------------------------------------------------ summing finished tables (jellyfish merge)
 
@@ -1998,6 +2066,84 @@ def _bound_holds(h: torch.Tensor, n: torch.Tensor, bound: tuple, at_least: bool)
     ref = n.to(torch.float64) * v if share else v
     left = h.to(torch.float64) if share else h
     return left >= ref if at_least else left <= ref
+
+
+def _fastq_files(src1, out1, src2, out2, pair: str) -> tuple:
+    """(input paths, output paths) of ``KmerTable.filter_fastq`` / ``trim_fastq``, refused before anything is opened where they make
+    no sense"""
+    if pair not in ("any", "both", "single"):
+        raise ValueError(f"pair must be any, both or single (got {pair!r})")
+    if (src2 is None) != (out2 is None):
+        raise ValueError("src2 and out2 go together: two inputs give two outputs")
+    if pair == "single" and src2 is not None:
+        raise ValueError("pair='single' judges the records of ONE file; R1/R2 input is paired")
+    srcs = [os.fspath(src1)] + ([os.fspath(src2)] if src2 is not None else [])
+    outs = [os.fspath(out1)] + ([os.fspath(out2)] if out2 is not None else [])
+    for o in outs:
+        if o.endswith(".gz"):
+            raise ValueError(f"{o}: the kept reads are written as plain text, gzip output is not supported")
+    real_outs = [os.path.realpath(x) for x in outs]
+    if len(set(real_outs)) != len(outs) or set(real_outs) & {os.path.realpath(x) for x in srcs}:
+        raise ValueError("the outputs must differ from each other and from the inputs (got " + ", ".join(outs + srcs) + ")")
+    return srcs, outs
+
+
+class _HitsStep:
+    """what ``KmerTable.filter_fastq`` does with a piece (``KmerTable._fastq_pieces``): pg_table_read_hits, the hit bounds, the
+    records byte for byte (pg_fastq_gather)"""
+
+    def __init__(self, table, window, lenient, lo_bound, hi_bound):
+        self.table, self.window, self.lenient, self.lo_bound, self.hi_bound = table, window, lenient, lo_bound, hi_bound
+
+    def launch(self, s, n, status, events):
+        return self.table._hits_of(s.text, s.have, s.idx, n, s.done, self.window, self.lenient, status, events)[0]
+
+    def judge(self, hits, tot):
+        nk, hh = (hits[:, 0].to(torch.int64) & 0xFFFFFFFF), (hits[:, 1].to(torch.int64) & 0xFFFFFFFF)
+        ok = (nk >= 1) & _bound_holds(hh, nk, self.lo_bound, True)
+        if self.hi_bound is not None:
+            ok &= _bound_holds(hh, nk, self.hi_bound, False)
+        tot[2] += ok.sum()
+        tot[4] += nk.sum()
+        tot[5] += hh.sum()
+        return ok
+
+    def sizes(self, s, hits, kept, tot):
+        return s.idx[4 * kept + 4] - s.idx[4 * kept]
+
+    def gather(self, s, n, hits, kept, dst, n_kept, out):
+        return _lib.load().pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept, out.data_ptr(),
+                                           out.numel(), _stream_ptr(self.table.device))
+
+
+class _SpansStep:
+    """what ``KmerTable.trim_fastq`` does with a piece: pg_table_read_spans, span length >= min_len, the records cut to their spans
+    (pg_fastq_gather_trimmed)"""
+
+    def __init__(self, table, window, lenient, mode, min_len):
+        self.table, self.window, self.lenient, self.mode, self.min_len = table, window, lenient, mode, min_len
+
+    def launch(self, s, n, status, events):
+        spans, _, sizes = self.table._spans_of(s.text, s.have, s.idx, n, s.done, self.window, self.lenient, self.mode, status, events)
+        return spans, sizes
+
+    def judge(self, rows, tot):
+        wide = rows[0].to(torch.int64) & 0xFFFFFFFF
+        ok = wide[:, 3] >= self.min_len
+        tot[2] += ok.sum()
+        tot[4] += wide[:, 0].sum()
+        tot[5] += wide[:, 1].sum()
+        return ok
+
+    def sizes(self, s, rows, kept, tot):
+        lens = rows[1][kept]
+        tot[6] += (lens < s.idx[4 * kept + 4] - s.idx[4 * kept]).sum()
+        tot[7] += (rows[0][kept, 3].to(torch.int64) & 0xFFFFFFFF).sum()
+        return lens
+
+    def gather(self, s, n, rows, kept, dst, n_kept, out):
+        return _lib.load().pg_fastq_gather_trimmed(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), rows[0].data_ptr(), dst.data_ptr(),
+                                                   n_kept, out.data_ptr(), out.numel(), _stream_ptr(self.table.device))
 
 
 def _temp_beside(path: str) -> tuple:
