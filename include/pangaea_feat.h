@@ -552,6 +552,53 @@ int pg_fastq_gather_trimmed(const uint8_t *text, int64_t n_bytes, const int64_t 
                             int64_t n_kept, uint8_t *out, int64_t out_bytes, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Single substitutions in the reads of a FASTQ text put right (device; one GPU, any of the five kinds; the table is only read).
+ * The third mode of the tools the two sections above are modelled on -- khmer, Lighter, BFC, Musket, beside `kmc_tools filter`:
+ * a read is neither dropped nor cut, the wrong base is replaced.  Beside the same step of the reference,
+ * scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp.  INPUT, K-MERS, the count window lower <= c <= upper, lowercase_is_base
+ * and min_qual_char are exactly those of pg_table_read_hits, SHORT is the rule of pg_table_read_spans (a quality line that does
+ * not reach as far as its sequence line is malformed always).  The entry is additive to ABI 9; every argument is checked
+ * before the first HIP call (PG_EINVAL with a pg_last_error text: a null pointer by name, a k that is not the table's,
+ * lower > upper, negative sizes, a min_qual_char that is no byte, a text base that is not 16-byte aligned).
+ *   BASES      of a sequence line: its bytes without a final '\r' (cr_s of the section above).  len is their number and
+ *              n_pos = max(0, len - k + 1).  The '\r' is beyond the end here, not a position without a k-mer, so that the
+ *              right-end errors of CRLF files are corrected too.
+ *   CLASS      of position i < n_pos: S (solid) -- it holds a k-mer whose stored count is inside the window; W (weak) -- it
+ *              holds a k-mer whose count is outside the window (absent: 0); V (void) -- it holds no k-mer: an 'N', a masked or
+ *              a low-quality base is among its k bytes.  Positions -1 and n_pos are E (the end).
+ *   CANDIDATE  a maximal run [a, b) of W positions whose neighbours a - 1 and b are both in {S, E} and not both E, of one of
+ *              these shapes, with the base p in question:
+ *                  left S, right S, b - a == k:   p = b - 1  (= a + k - 1)
+ *                  left E, right S, b - a <= k:   p = b - 1
+ *                  left S, right E, b - a <= k:   p = a + k - 1
+ *              This is what one substitution at base p does to the flags when no erroneous k-mer is solid by chance: every
+ *              k-mer at a position of [a, b) contains base p and no other k-mer does.  No candidates: a run with a V
+ *              neighbour, an interior run of any other length (two errors d < k apart give k + d), an all-weak read.
+ *   REPAIR     for each of the three bases x of A, C, G, T other than the base at p (compared without regard to case under
+ *              lowercase_is_base): x is VALID iff all b - a k-mers at [a, b), read with x at p, have a stored count inside
+ *              the same window.  The candidate is CORRECTED iff exactly one x is valid: byte p of the sequence line becomes
+ *              that x in the letter case of the byte it replaces.  With no valid x, or two or three, the byte stays.  The
+ *              quality line is never changed.
+ *   ONE PASS   all candidates of a record are judged on the record as it came; they do not interact (a k-mer contains at most
+ *              one p).  After the pass h has grown by exactly the sum of b - a over the corrected runs, and a second pass over
+ *              the output finds candidates - corrected candidates and corrects none.
+ *   ROW        n, h, candidates, corrected of record r < n_records; n and h are those of pg_table_read_hits on the input.  A
+ *              malformed record gives 0, 0, 0, 0 and the status words as pg_table_read_hits writes them.
+ *   pg_table_correct_reads   beside scripts/low_abd_reads.sh:10 / extract_unmapped.cpp (its decision about a read; here the
+ *                            repair of one).  One wavefront per record, any read length, any number of candidates.  out:
+ *                            NULL -- rows only; a device buffer of n_bytes into which the caller has copied text; or text
+ *                            itself -- in place.  The kernel stores nothing but the corrected bytes out[s1 + p] (s1: the
+ *                            start of the record's sequence line) and the rows: no byte outside [0, n_bytes) of the text is
+ *                            read and none outside the record's sequence line written, whatever the index says.
+ *                            n_records == 0: PG_OK, nothing launched, nothing written.
+ * ---------------------------------------------------------------------------------------------- */
+int pg_table_correct_reads(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                           int64_t first_record, int64_t lower, int64_t upper /* < 0: none */, int lowercase_is_base,
+                           int min_qual_char /* 0: none */, uint8_t *out /* device: NULL, a copy of text, or text */,
+                           uint32_t *rows /* device, [n_records][4]: n, h, candidates, corrected */, uint64_t *status /* device [2] */,
+                           void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
  * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
  * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for

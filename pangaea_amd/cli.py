@@ -14,6 +14,8 @@
                       [--pair any|both|single] [--min-qual-char C] -o OUT [-o2 OUT2]      (one JSON line on stdout)
     kmer_table trim {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} [-L LOWER] [-U UPPER] [--mode first|longest] [--min-len N]
                     [--pair any|both|single] [--min-qual-char C] -o OUT [-o2 OUT2]        (one JSON line on stdout)
+    kmer_table correct {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} [-L LOWER] [-U UPPER] [--min-qual-char C]
+                       -o OUT [-o2 OUT2]                                                   (one JSON line on stdout)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -164,7 +166,7 @@ def _hit_bound_arg(text: str, flag: str):
 
 
 def _reads_checks(a, verb: str) -> None:
-    """what ``kmer_table filter`` and ``kmer_table trim`` refuse alike about k, the table's source, the reads, the outputs, the pair
+    """what ``kmer_table filter``, ``kmer_table trim`` and ``kmer_table correct`` refuse alike about k, the table's source, the reads, the outputs, the pair
     rule, the count window and the quality threshold"""
     from . import _lib
     if not 1 <= a.kmer <= _lib.WIDE_MAX_K:
@@ -235,12 +237,23 @@ def _trim_plan(a) -> tuple:
     return source, reads, kw
 
 
+def _correct_plan(a) -> tuple:
+    """the checked arguments of ``kmer_table correct``: (table source, reads, keyword arguments of ``KmerTable.correct_fastq``), as
+    ``_trim_plan`` gives them (there is no pair rule: every record is written).  Nothing is opened but the question whether the
+    inputs exist."""
+    _reads_checks(a, "correct")
+    kw = dict(lower=a.lower, upper=a.upper, min_qual_char=a.min_qual_char,
+              lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+    source, reads = _reads_sources(a)
+    return source, reads, kw
+
+
 def _kmer_table_filter(a) -> int:
-    """``kmer_table filter`` and ``kmer_table trim``: the table from its source, the call, one JSON line"""
+    """``kmer_table filter``, ``kmer_table trim`` and ``kmer_table correct``: the table from its source, the call, one JSON line"""
     import json
     import torch
     from .kmer import KmerTable
-    source, (r1, r2, o1, o2), kw = _trim_plan(a) if a.cmd == "trim" else _filter_plan(a)
+    source, (r1, r2, o1, o2), kw = _trim_plan(a) if a.cmd == "trim" else _correct_plan(a) if a.cmd == "correct" else _filter_plan(a)
     device = torch.device("cuda", torch.cuda.current_device())
     if source is None:
         table = _counted(r1, r2, a.kmer, device)
@@ -248,9 +261,16 @@ def _kmer_table_filter(a) -> int:
         table = KmerTable.from_dump(source[1], a.kmer, device)
     else:
         table = _counted(source[1], source[2], a.kmer, device)
-    res = table.trim_fastq(r1, o1, r2, o2, **kw) if a.cmd == "trim" else table.filter_fastq(r1, o1, r2, o2, **kw)
+    call = {"trim": table.trim_fastq, "correct": table.correct_fastq}.get(a.cmd, table.filter_fastq)
+    res = call(r1, o1, r2, o2, **kw)
     sys.stdout.write(json.dumps(res) + "\n")
     return 0
+
+
+_CORRECT_HELP = ("put single-base substitutions in the reads right from a k-mer table and write every read, at the length it came "
+                 "with.  The table is loaded from -g DUMP, counted from -ti F or -t1 F -t2 F, or -- no table source -- counted from "
+                 "the reads themselves; every k-mer of the reads is then in the table at least once, so that -L 2 or more is what "
+                 "makes sense there.")
 
 
 def _kmer_table_parser() -> _Parser:
@@ -297,8 +317,8 @@ def _kmer_table_parser() -> _Parser:
             q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
             q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
             q.add_argument("-o", "--output", required=True)
-    for name in ("filter", "trim"):
-        q = sub.add_parser(name)
+    for name in ("filter", "trim", "correct"):
+        q = sub.add_parser(name, description=_CORRECT_HELP if name == "correct" else None)
         q.add_argument("-g", "--global", dest="global_", default="")
         q.add_argument("-ti", "--table-interleaved", dest="table_interleaved", default="")
         q.add_argument("-t1", "--table-reads1", dest="table1", default="")
@@ -313,10 +333,12 @@ def _kmer_table_parser() -> _Parser:
             q.add_argument("--min-hits", dest="min_hits", default="1")
             q.add_argument("--max-hits", dest="max_hits", default=None)
             q.add_argument("--pair", default="any")
-        else:
+        elif name == "trim":
             q.add_argument("--mode", default="longest")
             q.add_argument("--min-len", dest="min_len", type=int, default=None)
             q.add_argument("--pair", default="both")
+        else:
+            q.set_defaults(pair="both")                      # (no pair rule: every record is written; what the shared checks read)
         q.add_argument("--min-qual-char", dest="min_qual_char", default=None)
         q.add_argument("-o", "--output", required=True)
         q.add_argument("-o2", "--output2", default="")
@@ -360,11 +382,18 @@ def main_kmer_table(argv=None) -> int:
     and keep their line ends.  A read passes iff its span has at least ``--min-len`` bases (default K); ``--pair both`` (the
     default here: a mate kept under ``any`` that did not pass is written too, possibly empty), ``any``, ``single`` as for filter.
     One JSON line on stdout: records, kept, passed, trimmed, bases, bases_out, kmers, hits, seconds, device_ms.
+    ``kmer_table correct``: the same reads, table sources and count window, but no read is dropped or cut: a base whose k-mers are
+    all outside the window, between solid k-mers or between one and an end of the read, is REPLACED when exactly one other base
+    makes all of them solid (``KmerTable.correct_fastq``; what khmer, Lighter, BFC and Musket do for single substitutions).
+    Every record is written, byte for byte except the corrected bases, so ``-o`` (and ``-o2``) have their inputs' sizes; there is
+    no ``--pair``.  Without a table source the table is the reads' own, where every k-mer has count 1 at least: ``-L 2`` or more is
+    then what makes sense.  One JSON line on stdout: records, bases, kmers, hits, candidates, corrected, reads_corrected, seconds,
+    device_ms.
     Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
     a = _kmer_table_parser().parse_args(argv)
     from . import _lib
     try:
-        if a.cmd in ("filter", "trim"):
+        if a.cmd in ("filter", "trim", "correct"):
             return _kmer_table_filter(a)
         if a.cmd in ("combine", "compare"):
             for side, g, i in (("A", a.global_a, a.interleaved_a), ("B", a.global_b, a.interleaved_b)):

@@ -1538,6 +1538,206 @@ __global__ __launch_bounds__(BLOCK) void fastq_gather_trimmed_kernel(const uint8
     }
 }
 
+// ---- 6. single substitutions put right: read_spans_kernel's staging, lookups and record header, and per turn of a batch TWO
+// ballots, have and solid.  have & ~solid are the WEAK positions (a k-mer outside the window), solid the S positions, ~have the
+// V positions (no k-mer); -1 and n_pos are E.  The walker below keeps the open run of weak positions and the class of the
+// position in front of it in wave-uniform registers across ballot words and batches, and jumps from run boundary to run
+// boundary with ctz, as SpanRuns does.  A run that closes is judged at once by the same wavefront -- no list of candidates,
+// so no cap per record -- against the header's table of shapes, and a candidate is verified (correct_candidate).  Semantics: the
+// header's section "Single substitutions in the reads of a FASTQ text put right".
+enum { CLS_V = 0, CLS_S = 1, CLS_E = 2 };
+
+struct WeakRuns {
+    uint32_t start, len, left;                               // the open run [start, start + len) and the class of position start - 1
+    uint32_t carry;                                          // the last position of the word before was solid
+
+    // the next run that closes inside the word of positions at .. at + cnt - 1 (weak has no bit at or above cnt), from bit *pos
+    // on: true with (a, n, lf, rt) = its start, its length and the classes of its two neighbours, *pos where to go on
+    __device__ __forceinline__ bool next(uint64_t weak, uint64_t solid, uint32_t at, int cnt, int *pos, uint32_t *a, uint32_t *n, uint32_t *lf,
+                                         uint32_t *rt)
+    {
+        int at_bit = *pos;
+        while (at_bit < cnt) {
+            const uint64_t gaps = ~(weak >> at_bit);         // (the shift fills with 0: there is a gap at or before bit 64 - at_bit)
+            const int ones = at_bit ? __builtin_ctzll(gaps) : gaps ? __builtin_ctzll(gaps) : 64;
+            if (ones) {
+                if (!len) {
+                    start = at + at_bit;
+                    left = start == 0 ? (uint32_t)CLS_E : at_bit ? (uint32_t)((solid >> (at_bit - 1)) & 1u) : carry;
+                }
+                len += ones;
+                at_bit += ones;
+                if (at_bit >= cnt) break;                    // (the run is open at the word's end, or at the line's)
+            }
+            const bool closed = len != 0;
+            if (closed) {
+                *a = start;
+                *n = len;
+                *lf = left;
+                *rt = (uint32_t)((solid >> at_bit) & 1u);
+                len = 0;
+            }
+            const uint64_t rest = weak >> at_bit;
+            at_bit = rest ? at_bit + __builtin_ctzll(rest) : cnt;
+            if (closed) {
+                *pos = at_bit;
+                return true;
+            }
+        }
+        *pos = at_bit;
+        return false;
+    }
+};
+
+// what a closed run needs beside its own numbers (the same for the whole kernel, or for the record)
+struct CorrectArgs {
+    const uint8_t *text;
+    uint8_t *out;
+    int64_t s1, len;
+    int k;
+    uint64_t kmask, lower, upper;
+    const uint32_t *dense;
+    HashView t;
+};
+
+// the closed run [a, a + n) between neighbours of classes lf and rt: 0 = no candidate, 1 = a candidate that stays, 2 = corrected.
+// The shapes: S .. S with n == k, E .. S and S .. E with n <= k; the base in question is p = a + n - 1 where the right neighbour
+// is solid, a + k - 1 at the line's end.  Every k-mer of the run holds base p and no other k-mer does, so the 2k - 1 characters
+// seq[a .. a + 2k - 2], clipped to the line, are all the verification needs: one per lane, straight from the text (a may lie in
+// the batch before the staged one), their 2-bit codes as two ballots.  All of them are bases, since every position of the run
+// holds a k-mer.  Lane j < n shifts the ballots by j, which is the window of the k-mer at a + j in the stream's form, puts each of
+// the three other codes at base p, and issues all three lookups before it resolves any; three ballots say which alternatives
+// every k-mer of the run accepts.  Exactly one: lane 0 stores that base, in the letter case of the byte it replaces -- the only
+// store of the kernel beside its row.  The ballots stay in registers: a window of at most 61 characters needs no LDS.
+// Inlined into every turn of the unrolled batch: as one function that the kernel calls it measured 2 % slower.
+template <int TK>
+__device__ __forceinline__ uint32_t correct_candidate(const CorrectArgs &g, uint32_t a, uint32_t n, uint32_t lf, uint32_t rt, int lane)
+{
+    const int k = g.k;
+    if (lf == CLS_V || rt == CLS_V || (lf == CLS_E && rt == CLS_E)) return 0;
+    if (lf == CLS_S && rt == CLS_S ? n != (uint32_t)k : n > (uint32_t)k) return 0;
+    const uint32_t p = rt == CLS_S ? a + n - 1 : a + (uint32_t)k - 1;
+    const int64_t j = (int64_t)a + lane;
+    uint32_t ch = 0;
+    if (lane < 2 * k - 1 && j < g.len) ch = g.text[g.s1 + j];
+    const uint64_t b0 = __ballot((ch >> 1) & 1u), b1 = __ballot((ch >> 2) & 1u);
+    const uint32_t was = (uint32_t)__shfl((int)ch, (int)(p - a));        // (p - a < 2k - 1 <= 61, and p < len: that lane has read)
+    const uint32_t code = (was >> 1) & 3u;
+    const bool mine = (uint32_t)lane < n;
+    const int at = 2 * ((int)(p - a) - lane);                // (where base p lies in the window of the k-mer at a + lane: 0 <= at < 2k for mine)
+    const uint64_t w = (spread_bits((uint32_t)(b0 >> lane)) | (spread_bits((uint32_t)(b1 >> lane)) << 1)) & g.kmask;
+    Lookup<TK> q[3];
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        q[x].key = q[x].hh = q[x].cur = 0;
+        if (mine) {
+            const uint64_t c = (w & ~(3ull << at)) | ((uint64_t)((code + 1 + x) & 3u) << at);
+            // (as kmer_at: the forward code is the window reversed, the reverse complement the window complemented)
+            const uint64_t fw = rev2_64(c) >> (64 - 2 * k), rc = (c ^ 0xAAAAAAAAAAAAAAAAull) & g.kmask;
+            q[x].issue(fw < rc ? fw : rc, k, g.dense, g.t);
+        }
+    }
+    uint32_t valid = 0;
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        const uint32_t c = mine ? q[x].resolve(g.t) : 0u;
+        if (__ballot(mine && !(c >= g.lower && c <= g.upper)) == 0) valid |= 1u << x;
+    }
+    if (__popc(valid) != 1) return 1;
+    const uint32_t put = (code + (uint32_t)__ffs(valid)) & 3u;          // (the codes: A 0, C 1, T 2, G 3)
+    if (g.out && lane == 0) g.out[g.s1 + p] = (uint8_t)(((0x47544341u >> (8 * put)) & 0xFFu) | (was & 0x20u));
+    return 2;
+}
+
+// text and out carry no __restrict__: out may be the text itself.  That is sound because a record belongs to one wavefront, and
+// inside a record every store follows every load of its byte: base p of a run lies in front of the first character of any later
+// run of the record (the later run begins behind this one's solid right neighbour, b > p), so no later verification reads it,
+// and in front of the first character of the batch staged after the run has closed (that batch begins behind b).  The record's
+// header bytes are read before its first store.
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void read_correct_kernel(const uint8_t *text, int64_t n_bytes, const long long *__restrict__ line_start,
+                                                             int64_t n_records, int64_t first_record, int k, uint64_t lower, uint64_t upper, int lenient,
+                                                             uint32_t min_qual, const uint32_t *__restrict__ dense, HashView t, uint8_t *out,
+                                                             uint32_t *__restrict__ rows, unsigned long long *status)
+{
+    __shared__ uint64_t s_codes[WAVES][HITS_WORDS];
+    __shared__ uint32_t s_valid[WAVES][HITS_WORDS];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // (as in read_spans_kernel: what is per record stays scalar)
+    uint64_t *wc = s_codes[wave];
+    uint32_t *wv = s_valid[wave];
+    CorrectArgs g;
+    g.text = text;
+    g.out = out;
+    g.k = k;
+    g.kmask = low_mask<uint64_t>(k);
+    g.lower = lower;
+    g.upper = upper;
+    g.dense = dense;
+    g.t = t;
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES;
+    for (int64_t r = (int64_t)blockIdx.x * WAVES + wave; r < n_records; r += n_waves) {
+        const int64_t s0 = line_start[4 * r], s1 = line_start[4 * r + 1], s2 = line_start[4 * r + 2], s3 = line_start[4 * r + 3], s4 = line_start[4 * r + 4];
+        // (the record's check and its line ends exactly as read_spans_kernel makes them: five loads that leave together)
+        uint32_t bad = 0;
+        int64_t len = 0;
+        if (!(s0 >= 0 && s0 < s1 && s1 < s2 && s2 < s3 && s3 <= s4 && s4 <= n_bytes)) bad = PG_FASTQ_BAD_INDEX;
+        else {
+            len = s2 - 1 - s1;
+            const uint32_t c0 = text[s0], c2 = text[s2], e_s = text[s2 - 2], e1 = text[s4 - 1], e2 = text[s4 - 2];
+            const int nl = (s4 > s3) & (e1 == '\n');
+            const int64_t qlen = s4 - s3 - nl;
+            const int cr_s = (len > 0) & (e_s == '\r'), cr_q = (qlen > 0) & ((nl ? e2 : e1) == '\r');
+            if (c0 != '@') bad = PG_FASTQ_NO_AT;
+            else if (c2 != '+') bad = PG_FASTQ_NO_PLUS;
+            else if ((min_qual && qlen < len) || qlen - cr_q < len - cr_s) bad = PG_FASTQ_SHORT_QUALITY;
+            len -= cr_s;                                     // (the bases of the line: a final '\r' is beyond its end, not a position without a k-mer)
+        }
+        if (bad) {                                           // (the same for the whole wavefront)
+            if (lane == 0) fastq_record_bad(status, first_record + r, bad);
+            if (lane < 4) rows[4 * r + lane] = 0;
+            continue;
+        }
+        g.s1 = s1;
+        g.len = len;
+        const int64_t n_pos = len >= k ? len - k + 1 : 0;
+        uint32_t n = 0, h = 0, candidates = 0, corrected = 0;
+        WeakRuns runs = {0, 0, CLS_E, 0};
+        for (int64_t base = 0; base < n_pos; base += 64 * DEPTH_BATCH) {
+            hits_stage(text, s1, s3, len, base, lane, lenient, min_qual, wc, wv);
+            bool have[DEPTH_BATCH];
+            uint32_t c[DEPTH_BATCH];
+            hits_lookup<TK>(wc, wv, base, n_pos, lane, k, g.kmask, dense, t, have, c);
+#pragma unroll
+            for (int u = 0; u < DEPTH_BATCH; ++u) {
+                const uint64_t held = __ballot(have[u]), solid = __ballot(have[u] && c[u] >= lower && c[u] <= upper);
+                const uint64_t weak = held & ~solid;
+                const int64_t rest = n_pos - (base + 64 * u);
+                const int cnt = rest >= 64 ? 64 : rest > 0 ? (int)rest : 0;
+                n += (uint32_t)__popcll(held);
+                h += (uint32_t)__popcll(solid);
+                if (cnt && (weak | runs.len)) {
+                    int pos = 0;
+                    uint32_t a, m, lf, rt;
+                    while (runs.next(weak, solid, (uint32_t)(base + 64 * u), cnt, &pos, &a, &m, &lf, &rt)) {
+                        const uint32_t did = correct_candidate<TK>(g, a, m, lf, rt, lane);
+                        candidates += did != 0;
+                        corrected += did == 2;
+                    }
+                }
+                if (cnt) runs.carry = (uint32_t)(solid >> 63);
+            }
+            wave_lds_sync();                                 // (the next batch stages over these words)
+        }
+        if (runs.len) {                                      // (open at the line's end: its right neighbour is E)
+            const uint32_t did = correct_candidate<TK>(g, runs.start, runs.len, runs.left, CLS_E, lane);
+            candidates += did != 0;
+            corrected += did == 2;
+        }
+        if (lane < 4) rows[4 * r + lane] = lane == 0 ? n : lane == 1 ? h : lane == 2 ? candidates : corrected;
+    }
+}
+
 }  // namespace
 
 // the table as the streaming kernels see it (spectrum, dump, merge, combine): layout, entries, the counts plane of the planes form
@@ -2128,4 +2328,41 @@ extern "C" int pg_fastq_gather_trimmed(const uint8_t *text, int64_t n_bytes, con
     hipLaunchKernelGGL(fastq_gather_trimmed_kernel, dim3(grid_for(n_kept, WAVES)), dim3(BLOCK), 0, (hipStream_t)stream, text, n_bytes,
                        (const long long *)line_start, n_records, (const long long *)kept, spans, (const long long *)dst_off, n_kept, out, out_bytes);
     return check_launch(who);
+}
+
+// ---- single substitutions in the reads of a FASTQ text put right (kernel: 6. of the section above); beside the read set of
+// scripts/low_abd_reads.sh:10 / extract_unmapped.cpp, replacing nothing
+extern "C" int pg_table_correct_reads(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                                      int64_t first_record, int64_t lower, int64_t upper, int lowercase_is_base, int min_qual_char, uint8_t *out,
+                                      uint32_t *rows, uint64_t *status, void *stream)
+{
+    const char *who = "pg_table_correct_reads";
+    if (!t) return pg_fail(PG_EINVAL, "%s: t is null", who);
+    if (!text) return pg_fail(PG_EINVAL, "%s: text is null", who);
+    if (!line_start) return pg_fail(PG_EINVAL, "%s: line_start is null", who);
+    if (!rows) return pg_fail(PG_EINVAL, "%s: rows is null", who);
+    if (!status) return pg_fail(PG_EINVAL, "%s: status is null", who);
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "%s: n_bytes is negative (%lld)", who, (long long)n_bytes);
+    if (n_records < 0) return pg_fail(PG_EINVAL, "%s: n_records is negative (%lld)", who, (long long)n_records);
+    if (first_record < 0) return pg_fail(PG_EINVAL, "%s: first_record is negative (%lld)", who, (long long)first_record);
+    if (lower < 0) return pg_fail(PG_EINVAL, "%s: lower is negative (%lld)", who, (long long)lower);
+    if (upper >= 0 && upper < lower) return pg_fail(PG_EINVAL, "%s: upper %lld is below lower %lld", who, (long long)upper, (long long)lower);
+    if (min_qual_char < 0 || min_qual_char > 255) return pg_fail(PG_EINVAL, "%s: min_qual_char %d is no byte (0: none)", who, min_qual_char);
+    if ((uintptr_t)text & 15) return pg_fail(PG_EINVAL, "%s: text is not 16-byte aligned", who);
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (t->k != k) return pg_fail(PG_EINVAL, "%s: k differs (table %d, asked %d)", who, t->k, k);
+    if (n_records == 0) return PG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(status, 0, sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(status + 1, 0xff, sizeof(uint64_t), s) != hipSuccess)
+        return pg_fail(PG_EHIP, "%s: cannot clear the status", who);
+    const ProbeArgs pa = probe_args(t);
+    const int grid = grid_for(n_records, WAVES);
+    const uint64_t up = upper < 0 ? ~0ull : (uint64_t)upper;
+    rc = with_kind(t->kind, [&](auto tk) {
+        return launch(read_correct_kernel<decltype(tk)::value>, dim3(grid), dim3(BLOCK), 0, s, who, text, n_bytes, (const long long *)line_start, n_records,
+                      first_record, k, (uint64_t)lower, up, lowercase_is_base ? 1 : 0, (uint32_t)min_qual_char, pa.dense, pa.view, out, rows,
+                      (unsigned long long *)status);
+    });
+    return rc ? rc : check_launch(who);
 }

@@ -1651,6 +1651,75 @@ class KmerTable:
         return self._rows_of_text(text, 4, lambda: (self._hits_window(lower, upper, min_qual_char), self._span_mode(mode)),
                                   lambda t, n, idx, n_rec, a: self._spans_of(t, n, idx, n_rec, 0, a[0], bool(lowercase_is_base), a[1])[:2])
 
+    def _corrections_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, window: tuple,
+                        lowercase_is_base: bool, out: torch.Tensor | None, status: torch.Tensor | None = None,
+                        events: tuple | None = None) -> tuple:
+        """(rows: int32 [n_records, 4] holding the 32-bit n, h, candidates, corrected; status: int64 [2]) of
+        pg_table_correct_reads, both on the device.  ``out``: None (rows only), a copy of ``text`` or ``text`` itself (in place);
+        ``status`` and ``events`` as for ``_hits_of``"""
+        dev = self.device
+        rows = torch.empty((n_records, 4), dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(2, dtype=torch.int64, device=dev)
+        lower, upper, mq = window
+        L = _lib.load()
+        if events:
+            events[0].record()
+        rc = L.pg_table_correct_reads(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, upper,
+                                      1 if lowercase_is_base else 0, mq, None if out is None else out.data_ptr(), rows.data_ptr(),
+                                      status.data_ptr(), _stream_ptr(dev))
+        if events:
+            events[1].record()
+        _lib.check(rc)
+        return rows, status
+
+    def read_corrections(self, text: torch.Tensor, lower: int = 1, upper: int | None = None, lowercase_is_base: bool = True,
+                         min_qual_char=None) -> tuple:
+        """single-base substitutions of a four-line FASTQ text put right from this table (what khmer, Lighter, BFC and Musket do):
+        (rows: int64 [n_records, 4] -- n, h, candidates, corrected --, the corrected text: uint8, a new tensor of the text's size;
+        the argument is not modified), both on the table's device.  n and h are those of ``read_hits`` on the text as it came.
+
+        A position of a sequence line (its bytes without a final ``\\r``) is SOLID iff it holds a k-mer whose count c in this
+        table satisfies ``lower <= c <= upper``, WEAK iff it holds a k-mer whose count does not, VOID iff it holds none.  A
+        CANDIDATE is a maximal run [a, b) of weak positions between two solid ones with b - a == k, or between a solid one and
+        an end of the line with b - a <= k: the signature of ONE wrong base p (b - 1, or a + k - 1 at the right end) whose
+        k-mers are all weak.  It is CORRECTED iff exactly one other base at p makes all b - a k-mers solid; that base goes into
+        byte p in the letter case it had.  Runs beside a void position, runs of any other length (two errors closer than k) and
+        reads that are weak throughout are left alone, as are candidates with no or several fitting bases; the quality line
+        never changes.  All candidates of a record are judged on the record as it came: a second call corrects nothing more.
+        ``text``, the k-mer rules and the errors are those of ``read_spans``.  The table is only read (pg_fastq_index,
+        pg_table_correct_reads)."""
+        fixed = []
+
+        def rows_of(t, n, idx, n_rec, window):
+            fixed.append(t.clone())
+            return self._corrections_of(t, n, idx, n_rec, 0, window, bool(lowercase_is_base), fixed[0])
+
+        rows = self._rows_of_text(text, 4, lambda: self._hits_window(lower, upper, min_qual_char), rows_of)
+        return rows, fixed[0] if fixed else text.clone()
+
+    def correct_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
+                      lowercase_is_base: bool = True, min_qual_char=None) -> dict:
+        """put the single-base substitutions of a FASTQ file's reads right from this table (``read_corrections``) and write EVERY
+        record, in input order and with the length it came with, to ``out1`` (and ``out2``): the output is byte for byte the
+        input except the corrected bases, so each output has its input's size.  One file (interleaved or not: records are judged
+        on their own, an odd number of them is fine) or R1 / R2 (the same number of records).  Input forms, pieces, the plain-text
+        output under a temporary name, "after any error no output file is left" and the ValueErrors naming the record's ordinal
+        are those of ``trim_fastq``; a quality line that does not reach as far as its sequence line is malformed.
+
+        Returns ``records``, ``bases`` (bytes of the sequence lines), ``kmers``, ``hits`` (of the input), ``candidates``,
+        ``corrected``, ``reads_corrected`` (records with at least one corrected base) -- totals over all inputs, exact -- and
+        ``seconds`` (wall), ``device_ms`` (the pg_table_correct_reads and pg_fastq_gather entries of every piece, each between
+        two device events of its own)."""
+        import time
+        t0 = time.perf_counter()
+        pair = "single" if src2 is None else "both"
+        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
+        window = self._hits_window(lower, upper, min_qual_char)
+        totals, device_ms = self._fastq_pieces(srcs, outs, pair, _CorrectStep(self, window, bool(lowercase_is_base)))
+        return {"records": totals[0], "bases": totals[3], "kmers": totals[4], "hits": totals[5], "candidates": totals[8], "corrected": totals[9],
+                "reads_corrected": totals[10], "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
+
     def filter_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
                      min_hits=1, max_hits=None, pair: str = "any", lowercase_is_base: bool = True, min_qual_char=None) -> dict:
         """keep or drop the reads of a FASTQ file by the counts of their k-mers in this table (`kmc_tools filter`, khmer's
@@ -1723,15 +1792,16 @@ class KmerTable:
                 "kmers": totals[4], "hits": totals[5], "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
 
     def _fastq_pieces(self, srcs: list, outs: list, pair: str, step) -> tuple:
-        """the piece loop of ``filter_fastq`` and ``trim_fastq``: (totals: records, kept, passed, bases, kmers, hits, trimmed, bases
-        written -- exact ints --, device milliseconds of the timed entries).  ``step`` is what differs between the two: its
+        """the piece loop of ``filter_fastq``, ``trim_fastq`` and ``correct_fastq``: (totals: records, kept, passed, bases, kmers, hits,
+        trimmed, bases written, candidates, corrected, reads corrected -- exact ints --, device milliseconds of the timed entries).
+        ``step`` is what differs between them: its
         ``launch`` enqueues the per-record kernel of a piece, its ``judge`` turns the kernel's rows into pass flags and totals, its
         ``sizes`` gives the bytes each kept record leaves with and its ``gather`` writes them to their places."""
         self._require_readable()
         dev = self.device
         piece = self._filter_piece_bytes()
         mates = pair != "single"
-        tot = torch.zeros(8, dtype=torch.int64, device=dev)
+        tot = torch.zeros(11, dtype=torch.int64, device=dev)
         timed = []                                                       # (event, event) around every timed entry; read at the end
         ins, files, tmps = [], [], []
         try:
@@ -2144,6 +2214,35 @@ class _SpansStep:
     def gather(self, s, n, rows, kept, dst, n_kept, out):
         return _lib.load().pg_fastq_gather_trimmed(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), rows[0].data_ptr(), dst.data_ptr(),
                                                    n_kept, out.data_ptr(), out.numel(), _stream_ptr(self.table.device))
+
+
+class _CorrectStep:
+    """what ``KmerTable.correct_fastq`` does with a piece: pg_table_correct_reads on the piece IN PLACE (the piece is the device's
+    copy; what the host keeps for the next round is untouched), every record passes, and the records leave whole
+    (pg_fastq_gather)"""
+
+    def __init__(self, table, window, lenient):
+        self.table, self.window, self.lenient = table, window, lenient
+
+    def launch(self, s, n, status, events):
+        return self.table._corrections_of(s.text, s.have, s.idx, n, s.done, self.window, self.lenient, s.text, status, events)[0]
+
+    def judge(self, rows, tot):
+        wide = rows.to(torch.int64) & 0xFFFFFFFF
+        tot[2] += wide.shape[0]
+        tot[4] += wide[:, 0].sum()
+        tot[5] += wide[:, 1].sum()
+        tot[8] += wide[:, 2].sum()
+        tot[9] += wide[:, 3].sum()
+        tot[10] += (wide[:, 3] > 0).sum()
+        return torch.ones(wide.shape[0], dtype=torch.bool, device=rows.device)
+
+    def sizes(self, s, rows, kept, tot):
+        return s.idx[4 * kept + 4] - s.idx[4 * kept]
+
+    def gather(self, s, n, rows, kept, dst, n_kept, out):
+        return _lib.load().pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept, out.data_ptr(),
+                                           out.numel(), _stream_ptr(self.table.device))
 
 
 def _temp_beside(path: str) -> tuple:
