@@ -599,6 +599,40 @@ int pg_table_correct_reads(const pg_table *t, int k, const uint8_t *text, int64_
                            void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Depth of the reads of a FASTQ text (device; one GPU, any of the five kinds; the table is only read).  What BBNorm and khmer's
+ * normalize-by-median decide a read's fate by: the median -- here any percentile -- of the counts of its k-mers, and beside it
+ * a reproducible draw per read or pair, so that the caller can keep a read with probability target / depth.  Beside the same
+ * step of the reference, scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp.  INPUT, K-MERS, lowercase_is_base, min_qual_char
+ * and the status words are exactly those of pg_table_read_hits.  The entry is additive to ABI 9; every argument is checked
+ * before the first HIP call (PG_EINVAL with a pg_last_error text: a null pointer by name, a k that is not the table's,
+ * lower < 1, a percentile outside [0, 100], a unit_log2 that is neither 0 nor 1, negative sizes, a min_qual_char that is no
+ * byte, a text or rows base that is not 16-byte aligned).
+ *   VALUE    of a k-mer: its stored count c (0: absent; saturated counts as stored), taken as 0 when c < lower.
+ *   ROW      n, present, d, w of record r < n_records: n = the k-mers of the record, present = its values > 0, d = the value
+ *            at index ((n - 1) * percentile) / 100 (integer division) of the n values in ascending order, 0 when n = 0 --
+ *            percentile 50 is the lower median of pg_table_depth --, w = the draw of the record's unit.  A malformed record
+ *            gives 0, 0, 0, 0 and the status words as pg_table_read_hits writes them.
+ *   DRAW     of unit u = (first_record + r) >> unit_log2 (0: every record is a unit; 1: records 2i and 2i + 1 of an
+ *            interleaved file share one), in arithmetic mod 2^64 -- splitmix64 of seed + (u + 1) * its increment, top 24 bits:
+ *                z = seed + (u + 1) * 0x9E3779B97F4A7C15;   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                z = (z ^ (z >> 27)) * 0x94D049BB133111EB;   z ^= z >> 31;   w = z >> 40
+ *            w depends on nothing but seed and the record's ordinal: pieces of any size give the same draws.  A caller that
+ *            keeps a read iff w * d < target * 2^24 (exact in 64 bits: w < 2^24, d < 2^32) keeps it with probability
+ *            min(1, target / d).
+ *   pg_table_read_depths   beside scripts/low_abd_reads.sh:10 / extract_unmapped.cpp (its decision which read to keep, here from
+ *                          the depth the table gives the read).  One wavefront per record and any read length, with no
+ *                          workspace: a record of at most 512 positions keeps its values in registers and finds d by a search
+ *                          over the bits of the value; a longer one takes one sweep for n, present and the maximum and one per
+ *                          8-bit digit of d, each looking its k-mers up again (at most 1 + 4 sweeps).  Each row leaves as one
+ *                          16-byte store.  n_records == 0: PG_OK, nothing launched, nothing written.
+ * ---------------------------------------------------------------------------------------------- */
+int pg_table_read_depths(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                         int64_t first_record, int64_t lower /* >= 1 */, int percentile /* 0 .. 100 */, int lowercase_is_base,
+                         int min_qual_char /* 0: none */, uint64_t seed, int unit_log2 /* 0 or 1 */,
+                         uint32_t *rows /* device, 16-byte aligned, [n_records][4]: n, present, d, w */, uint64_t *status /* device [2] */,
+                         void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
  * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
  * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for

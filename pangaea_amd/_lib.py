@@ -197,6 +197,7 @@ def load() -> C.CDLL:
         "pg_table_read_spans": (i32, [tp, i32, vp, i64, vp, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp]),
         "pg_fastq_gather_trimmed": (i32, [vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, vp]),
         "pg_table_correct_reads": (i32, [tp, i32, vp, i64, vp, i64, i64, i64, i64, i32, i32, vp, vp, vp, vp]),
+        "pg_table_read_depths": (i32, [tp, i32, vp, i64, vp, i64, i64, i64, i32, i32, i32, C.c_uint64, i32, vp, vp, vp]),
         "pg_table_dump_units": (i64, [tp]),
         "pg_table_dump_sizes": (i32, [tp, i64, vp, vp, vp]),
         "pg_table_dump_text": (i32, [tp, i64, i64, i64, vp, i64, i64, vp, i64, vp]),
@@ -240,7 +241,7 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_mini_plan_masked", "pg_mini_count_half_masked", "pg_mini_count_half_piece_masked", "pg_mini_merge_bins_masked",
            "pg_table_query", "pg_table_spectrum", "pg_table_profile", "pg_table_depth_workspace_bytes", "pg_table_depth",
            "pg_fastq_index_workspace_bytes", "pg_fastq_index", "pg_table_read_hits", "pg_fastq_gather",
-           "pg_table_read_spans", "pg_fastq_gather_trimmed", "pg_table_correct_reads",
+           "pg_table_read_spans", "pg_fastq_gather_trimmed", "pg_table_correct_reads", "pg_table_read_depths",
            "pg_table_dump_units", "pg_table_dump_sizes", "pg_table_dump_text", "pg_dump_parse_workspace_bytes", "pg_dump_parse",
            "pg_table_merge", "pg_table_merge_aligned", "pg_table_merge_aligned_applies",
            "pg_table_combine_aligned", "pg_table_combine_items", "pg_table_compare",

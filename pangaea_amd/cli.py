@@ -16,6 +16,8 @@
                     [--pair any|both|single] [--min-qual-char C] -o OUT [-o2 OUT2]        (one JSON line on stdout)
     kmer_table correct {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} [-L LOWER] [-U UPPER] [--min-qual-char C]
                        -o OUT [-o2 OUT2]                                                   (one JSON line on stdout)
+    kmer_table normalize {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} --target T [--min-depth M] [-L LOWER] [--percentile P]
+                         [--pair any|both|single] [--seed S] [--min-qual-char C] -o OUT [-o2 OUT2]  (one JSON line on stdout)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -248,12 +250,36 @@ def _correct_plan(a) -> tuple:
     return source, reads, kw
 
 
+def _normalize_plan(a) -> tuple:
+    """the checked arguments of ``kmer_table normalize``: (table source, reads, keyword arguments of ``KmerTable.normalize_fastq``), as
+    ``_filter_plan`` gives them (there is no upper count).  Nothing is opened but the question whether the inputs exist."""
+    _reads_checks(a, "normalize")
+    if a.target is None or a.target < 1:
+        raise ValueError(f"--target is the depth to normalise to, a whole number of at least 1 (got {a.target})")
+    if a.target >= 1 << 31:
+        raise ValueError(f"--target must be below 2^31 (got {a.target})")
+    if a.min_depth < 0:
+        raise ValueError(f"--min-depth must be at least 0 (got {a.min_depth})")
+    if not 0 <= a.percentile <= 100:
+        raise ValueError(f"--percentile must lie in 0..100 (got {a.percentile})")
+    if not 0 <= a.seed < 1 << 64:
+        raise ValueError(f"--seed must lie in [0, 2^64) (got {a.seed})")
+    if a.lower < 1:
+        raise ValueError(f"-L must be at least 1 (got {a.lower})")
+    kw = dict(target=a.target, min_depth=a.min_depth, lower=a.lower, percentile=a.percentile, pair=a.pair, seed=a.seed,
+              min_qual_char=a.min_qual_char, lowercase_is_base=os.environ.get("PANGAEA_LOWERCASE_IS_BASE", "1") not in ("", "0"))
+    source, reads = _reads_sources(a)
+    return source, reads, kw
+
+
 def _kmer_table_filter(a) -> int:
-    """``kmer_table filter``, ``kmer_table trim`` and ``kmer_table correct``: the table from its source, the call, one JSON line"""
+    """``kmer_table filter``, ``kmer_table trim``, ``kmer_table correct`` and ``kmer_table normalize``: the table from its source, the
+    call, one JSON line"""
     import json
     import torch
     from .kmer import KmerTable
-    source, (r1, r2, o1, o2), kw = _trim_plan(a) if a.cmd == "trim" else _correct_plan(a) if a.cmd == "correct" else _filter_plan(a)
+    plan = {"trim": _trim_plan, "correct": _correct_plan, "normalize": _normalize_plan}.get(a.cmd, _filter_plan)
+    source, (r1, r2, o1, o2), kw = plan(a)
     device = torch.device("cuda", torch.cuda.current_device())
     if source is None:
         table = _counted(r1, r2, a.kmer, device)
@@ -261,7 +287,7 @@ def _kmer_table_filter(a) -> int:
         table = KmerTable.from_dump(source[1], a.kmer, device)
     else:
         table = _counted(source[1], source[2], a.kmer, device)
-    call = {"trim": table.trim_fastq, "correct": table.correct_fastq}.get(a.cmd, table.filter_fastq)
+    call = {"trim": table.trim_fastq, "correct": table.correct_fastq, "normalize": table.normalize_fastq}.get(a.cmd, table.filter_fastq)
     res = call(r1, o1, r2, o2, **kw)
     sys.stdout.write(json.dumps(res) + "\n")
     return 0
@@ -271,6 +297,12 @@ _CORRECT_HELP = ("put single-base substitutions in the reads right from a k-mer 
                  "with.  The table is loaded from -g DUMP, counted from -ti F or -t1 F -t2 F, or -- no table source -- counted from "
                  "the reads themselves; every k-mer of the reads is then in the table at least once, so that -L 2 or more is what "
                  "makes sense there.")
+
+
+_NORMALIZE_HELP = ("normalise the read depth from a k-mer table: a read's depth is the --percentile (50: the median) of its k-mers' "
+                   "counts, a read -- a pair under --pair any or both, with one draw for both mates -- is kept with probability "
+                   "target / depth and dropped when its depth is below --min-depth.  The table is loaded from -g DUMP, counted "
+                   "from -ti F or -t1 F -t2 F, or -- no table source, the usual call -- counted from the reads themselves.")
 
 
 def _kmer_table_parser() -> _Parser:
@@ -317,8 +349,8 @@ def _kmer_table_parser() -> _Parser:
             q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
             q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
             q.add_argument("-o", "--output", required=True)
-    for name in ("filter", "trim", "correct"):
-        q = sub.add_parser(name, description=_CORRECT_HELP if name == "correct" else None)
+    for name in ("filter", "trim", "correct", "normalize"):
+        q = sub.add_parser(name, description={"correct": _CORRECT_HELP, "normalize": _NORMALIZE_HELP}.get(name))
         q.add_argument("-g", "--global", dest="global_", default="")
         q.add_argument("-ti", "--table-interleaved", dest="table_interleaved", default="")
         q.add_argument("-t1", "--table-reads1", dest="table1", default="")
@@ -328,7 +360,10 @@ def _kmer_table_parser() -> _Parser:
         q.add_argument("-1", "--reads1", default="")
         q.add_argument("-2", "--reads2", default="")
         q.add_argument("-L", "--lower-count", dest="lower", type=int, default=1)
-        q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
+        if name == "normalize":
+            q.set_defaults(upper=None)                       # (no upper count: what the shared checks read)
+        else:
+            q.add_argument("-U", "--upper-count", dest="upper", type=int, default=None)
         if name == "filter":
             q.add_argument("--min-hits", dest="min_hits", default="1")
             q.add_argument("--max-hits", dest="max_hits", default=None)
@@ -337,6 +372,12 @@ def _kmer_table_parser() -> _Parser:
             q.add_argument("--mode", default="longest")
             q.add_argument("--min-len", dest="min_len", type=int, default=None)
             q.add_argument("--pair", default="both")
+        elif name == "normalize":
+            q.add_argument("--target", type=int, default=None)
+            q.add_argument("--min-depth", dest="min_depth", type=int, default=0)
+            q.add_argument("--percentile", type=int, default=50)
+            q.add_argument("--seed", type=int, default=0)
+            q.add_argument("--pair", default="any")
         else:
             q.set_defaults(pair="both")                      # (no pair rule: every record is written; what the shared checks read)
         q.add_argument("--min-qual-char", dest="min_qual_char", default=None)
@@ -389,11 +430,20 @@ def main_kmer_table(argv=None) -> int:
     no ``--pair``.  Without a table source the table is the reads' own, where every k-mer has count 1 at least: ``-L 2`` or more is
     then what makes sense.  One JSON line on stdout: records, bases, kmers, hits, candidates, corrected, reads_corrected, seconds,
     device_ms.
+    ``kmer_table normalize``: the same reads and table sources; coverage normalisation as BBNorm and khmer's normalize-by-median
+    do it (``KmerTable.normalize_fastq``).  A read's depth d is the ``--percentile`` (default 50: the lower median) of its k-mers'
+    counts in the table, counts below ``-L`` taken as 0 (there is no ``-U``).  Every pair -- every record under ``--pair single`` --
+    has one draw w in [0, 2^24) that depends on ``--seed`` and its ordinal alone; a read passes iff it has a k-mer,
+    d >= ``--min-depth`` (default 0) and w * d < T * 2^24, i.e. with probability min(1, T / d): what is covered deeper than
+    ``--target`` is thinned to about that depth, the rest passes untouched.  ``--pair any`` (the default) keeps a pair at its
+    smaller depth, ``both`` at its larger.  Kept records are written byte for byte.  Without a table source the table is the
+    reads' own: the usual call.  One JSON line on stdout: records, kept, passed, low, bases, kmers, hits, depth_in, depth_out,
+    seconds, device_ms.
     Exit status 0, or 1 with a message on stderr, as ``main_count_kmer``."""
     a = _kmer_table_parser().parse_args(argv)
     from . import _lib
     try:
-        if a.cmd in ("filter", "trim", "correct"):
+        if a.cmd in ("filter", "trim", "correct", "normalize"):
             return _kmer_table_filter(a)
         if a.cmd in ("combine", "compare"):
             for side, g, i in (("A", a.global_a, a.interleaved_a), ("B", a.global_b, a.interleaved_b)):

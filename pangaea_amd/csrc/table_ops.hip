@@ -1738,6 +1738,159 @@ __global__ __launch_bounds__(BLOCK) void read_correct_kernel(const uint8_t *text
     }
 }
 
+// ---- 7. the depth of every record: an order statistic of its k-mers' counts, and the draw of its unit.  read_hits_kernel's
+// staging and lookups again; what is new is that the answer is not additive over the batches of a record.  Every k-mer has the
+// value c = its stored count, 0 when absent or below `lower`; d is the value at index ((n - 1) * percentile) / 100 of the n
+// values in ascending order.  Two forms in one kernel, chosen per record and the same for the whole wavefront:
+//   SHORT  n_pos <= 64 * DEPTH_BATCH (every linked short read): one batch, its values stay in the lanes' DEPTH_BATCH registers
+//          and d comes from depth_short_kernel's search over the bits of the value -- one ballot per register and bit, from the
+//          maximum's top bit down.
+//   LONG   a radix select that keeps nothing per position: a first sweep over the batches gives n, present and the maximum,
+//          then one sweep per 8-bit digit from the maximum's top non-zero byte down stages and looks the batches up again and
+//          bins the digit of every value whose higher digits equal the prefix found so far into the wavefront's 256 bins in
+//          LDS; the bin the rank falls in is the next digit.  At most 1 + 4 sweeps, no workspace, no length limit.
+// The draw is splitmix64 of seed + (unit + 1) * the golden-ratio increment, its top 24 bits; semantics: the header's section
+// "Depth of the reads of a FASTQ text".
+constexpr int DRAW_BITS = 24;
+__device__ __forceinline__ uint32_t unit_draw(uint64_t seed, uint64_t unit)
+{
+    uint64_t z = seed + (unit + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (uint32_t)(z >> (64 - DRAW_BITS));
+}
+
+// hits_lookup with the values as the depth takes them: a count below `lower` is 0 (and so is a position without a k-mer)
+template <int TK>
+__device__ __forceinline__ void depth_values(const uint64_t *wc, const uint32_t *wv, int64_t base, int64_t n_pos, int lane, int k, uint64_t kmask,
+                                             uint64_t lower, const uint32_t *__restrict__ dense, const HashView &t, bool (&have)[DEPTH_BATCH],
+                                             uint32_t (&val)[DEPTH_BATCH])
+{
+    hits_lookup<TK>(wc, wv, base, n_pos, lane, k, kmask, dense, t, have, val);
+#pragma unroll
+    for (int u = 0; u < DEPTH_BATCH; ++u)
+        if (val[u] < lower) val[u] = 0;
+}
+
+constexpr int SELECT_DIGIT_BITS = 8, SELECT_BINS = 1 << SELECT_DIGIT_BITS, SELECT_PER_LANE = SELECT_BINS / 64;
+
+template <int TK>
+__global__ __launch_bounds__(BLOCK) void read_depths_kernel(const uint8_t *__restrict__ text, int64_t n_bytes, const long long *__restrict__ line_start,
+                                                            int64_t n_records, int64_t first_record, int k, uint64_t lower, uint32_t percentile,
+                                                            int lenient, uint32_t min_qual, uint64_t seed, int unit_log2,
+                                                            const uint32_t *__restrict__ dense, HashView t, uint4 *__restrict__ out,
+                                                            unsigned long long *status)
+{
+    __shared__ uint64_t s_codes[WAVES][HITS_WORDS];
+    __shared__ uint32_t s_valid[WAVES][HITS_WORDS];
+    __shared__ uint32_t s_bins[WAVES][SELECT_BINS];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));    // (as in read_spans_kernel: scalar loads of what is per record)
+    uint64_t *wc = s_codes[wave];
+    uint32_t *wv = s_valid[wave];
+    uint32_t *bins = s_bins[wave];
+    const uint64_t kmask = low_mask<uint64_t>(k);
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES;
+    for (int64_t r = (int64_t)blockIdx.x * WAVES + wave; r < n_records; r += n_waves) {
+        const int64_t s0 = line_start[4 * r], s1 = line_start[4 * r + 1], s2 = line_start[4 * r + 2], s3 = line_start[4 * r + 3], s4 = line_start[4 * r + 4];
+        int64_t len;
+        const uint32_t bad = fastq_record_check(text, n_bytes, s0, s1, s2, s3, s4, min_qual, &len);
+        if (bad) {                                           // (the same for the whole wavefront)
+            if (lane == 0) {
+                fastq_record_bad(status, first_record + r, bad);
+                out[r] = make_uint4(0, 0, 0, 0);
+            }
+            continue;
+        }
+        const int64_t n_pos = len >= k ? len - k + 1 : 0;
+        uint32_t n = 0, present = 0, vmax = 0, d = 0, rank = 0;
+        // sweep 0 gives n, present and the maximum, and is the only one of a SHORT record; sweep i > 0 of a LONG one bins the
+        // digit at `shift`.  One loop for both, so that the staging and the lookups exist once in the kernel's code
+        int shift = -1;
+        while (true) {
+            const uint64_t prefix = (uint64_t)d >> (shift + SELECT_DIGIT_BITS);
+            if (shift >= 0) {
+#pragma unroll
+                for (int j = 0; j < SELECT_PER_LANE; ++j) bins[lane + 64 * j] = 0;
+            }
+            bool have[DEPTH_BATCH];
+            uint32_t val[DEPTH_BATCH];
+#pragma unroll
+            for (int u = 0; u < DEPTH_BATCH; ++u) { have[u] = false; val[u] = 0; }
+            for (int64_t base = 0; base < n_pos; base += 64 * DEPTH_BATCH) {
+                hits_stage(text, s1, s3, len, base, lane, lenient, min_qual, wc, wv);     // (its sync orders the cleared bins too)
+                depth_values<TK>(wc, wv, base, n_pos, lane, k, kmask, lower, dense, t, have, val);
+                if (shift < 0) {
+#pragma unroll
+                    for (int u = 0; u < DEPTH_BATCH; ++u) {
+                        n += (uint32_t)__popcll(__ballot(have[u]));
+                        present += (uint32_t)__popcll(__ballot(val[u] > 0));
+                        vmax = val[u] > vmax ? val[u] : vmax;
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < DEPTH_BATCH; ++u)
+                        if (have[u] && ((uint64_t)val[u] >> (shift + SELECT_DIGIT_BITS)) == prefix)
+                            atomicAdd(&bins[(val[u] >> shift) & (SELECT_BINS - 1)], 1u);
+                }
+                wave_lds_sync();                             // (the next batch, sweep or record stages over these words; the bins are complete)
+            }
+            if (shift < 0) {
+#pragma unroll
+                for (int s = 32; s >= 1; s >>= 1) {
+                    const uint32_t m = __shfl_xor(vmax, s);
+                    vmax = m > vmax ? m : vmax;
+                }
+                if (!vmax) break;                            // (no k-mer, or none with a value: d = 0)
+                // the value at sorted index `rank`.  (n - 1 < 2^32 and percentile <= 100: 64 bits hold the product)
+                rank = (uint32_t)(((uint64_t)(n - 1) * percentile) / 100);
+                const int top = 31 - __clz((int)vmax);
+                if (n_pos <= 64 * DEPTH_BATCH) {
+                    // SHORT: the values of the one batch are still in the registers.  The largest x with at most `rank` values below it
+                    for (int bit = top; bit >= 0; --bit) {
+                        const uint32_t cand = d | (1u << bit);
+                        uint32_t below = 0;
+#pragma unroll
+                        for (int u = 0; u < DEPTH_BATCH; ++u) below += (uint32_t)__popcll(__ballot(have[u] && val[u] < cand));
+                        if (below <= rank) d = cand;
+                    }
+                    break;
+                }
+                shift = top & ~(SELECT_DIGIT_BITS - 1);
+                continue;
+            }
+            // lane l holds bins 4 l .. 4 l + 3: the lane, then the bin, in which the running sum passes the rank.  (rank is below the
+            // number of values that share the prefix, at every digit: the search ends inside the bins)
+            uint32_t b[SELECT_PER_LANE], mine = 0;
+#pragma unroll
+            for (int j = 0; j < SELECT_PER_LANE; ++j) { b[j] = bins[SELECT_PER_LANE * lane + j]; mine += b[j]; }
+            uint32_t upto = mine;                            // (inclusive sum over the lanes up to this one)
+#pragma unroll
+            for (int s = 1; s < 64; s <<= 1) {
+                const uint32_t o = __shfl_up(upto, s);
+                if (lane >= s) upto += o;
+            }
+            const uint64_t past = __ballot(upto > rank);
+            const int owner = past ? __builtin_ctzll(past) : 63;
+            uint32_t before = upto - mine, digit = SELECT_PER_LANE * lane + SELECT_PER_LANE - 1;
+            bool found = false;
+#pragma unroll
+            for (int j = 0; j < SELECT_PER_LANE; ++j) {
+                if (!found && before + b[j] > rank) { digit = SELECT_PER_LANE * lane + j; found = true; }
+                if (!found) before += b[j];
+            }
+            digit = __shfl(digit, owner);
+            rank -= __shfl(before, owner);
+            d |= digit << shift;
+            wave_lds_sync();                                 // (the next digit clears the bins)
+            if (shift == 0) break;
+            shift -= SELECT_DIGIT_BITS;
+        }
+        if (lane == 0) out[r] = make_uint4(n, present, d, unit_draw(seed, (uint64_t)(first_record + r) >> unit_log2));
+    }
+}
+
 }  // namespace
 
 // the table as the streaming kernels see it (spectrum, dump, merge, combine): layout, entries, the counts plane of the planes form
@@ -2363,6 +2516,44 @@ extern "C" int pg_table_correct_reads(const pg_table *t, int k, const uint8_t *t
         return launch(read_correct_kernel<decltype(tk)::value>, dim3(grid), dim3(BLOCK), 0, s, who, text, n_bytes, (const long long *)line_start, n_records,
                       first_record, k, (uint64_t)lower, up, lowercase_is_base ? 1 : 0, (uint32_t)min_qual_char, pa.dense, pa.view, out, rows,
                       (unsigned long long *)status);
+    });
+    return rc ? rc : check_launch(who);
+}
+
+// ---- depth of the reads of a FASTQ text (kernel: 7. of the section above); beside the read set of
+// scripts/low_abd_reads.sh:10 / extract_unmapped.cpp, replacing nothing
+extern "C" int pg_table_read_depths(const pg_table *t, int k, const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_records,
+                                    int64_t first_record, int64_t lower, int percentile, int lowercase_is_base, int min_qual_char, uint64_t seed,
+                                    int unit_log2, uint32_t *rows, uint64_t *status, void *stream)
+{
+    const char *who = "pg_table_read_depths";
+    if (!t) return pg_fail(PG_EINVAL, "%s: t is null", who);
+    if (!text) return pg_fail(PG_EINVAL, "%s: text is null", who);
+    if (!line_start) return pg_fail(PG_EINVAL, "%s: line_start is null", who);
+    if (!rows) return pg_fail(PG_EINVAL, "%s: rows is null", who);
+    if (!status) return pg_fail(PG_EINVAL, "%s: status is null", who);
+    if (n_bytes < 0) return pg_fail(PG_EINVAL, "%s: n_bytes is negative (%lld)", who, (long long)n_bytes);
+    if (n_records < 0) return pg_fail(PG_EINVAL, "%s: n_records is negative (%lld)", who, (long long)n_records);
+    if (first_record < 0) return pg_fail(PG_EINVAL, "%s: first_record is negative (%lld)", who, (long long)first_record);
+    if (lower < 1) return pg_fail(PG_EINVAL, "%s: lower is below 1 (%lld)", who, (long long)lower);
+    if (percentile < 0 || percentile > 100) return pg_fail(PG_EINVAL, "%s: percentile %d outside [0, 100]", who, percentile);
+    if (min_qual_char < 0 || min_qual_char > 255) return pg_fail(PG_EINVAL, "%s: min_qual_char %d is no byte (0: none)", who, min_qual_char);
+    if (unit_log2 != 0 && unit_log2 != 1) return pg_fail(PG_EINVAL, "%s: unit_log2 %d is neither 0 nor 1", who, unit_log2);
+    if ((uintptr_t)text & 15) return pg_fail(PG_EINVAL, "%s: text is not 16-byte aligned", who);
+    if ((uintptr_t)rows & 15) return pg_fail(PG_EINVAL, "%s: rows is not 16-byte aligned", who);
+    int rc = check_table(t);
+    if (rc) return rc;
+    if (t->k != k) return pg_fail(PG_EINVAL, "%s: k differs (table %d, asked %d)", who, t->k, k);
+    if (n_records == 0) return PG_OK;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(status, 0, sizeof(uint64_t), s) != hipSuccess || hipMemsetAsync(status + 1, 0xff, sizeof(uint64_t), s) != hipSuccess)
+        return pg_fail(PG_EHIP, "%s: cannot clear the status", who);
+    const ProbeArgs pa = probe_args(t);
+    const int grid = grid_for(n_records, WAVES);
+    rc = with_kind(t->kind, [&](auto tk) {
+        return launch(read_depths_kernel<decltype(tk)::value>, dim3(grid), dim3(BLOCK), 0, s, who, text, n_bytes, (const long long *)line_start,
+                      n_records, first_record, k, (uint64_t)lower, (uint32_t)percentile, lowercase_is_base ? 1 : 0, (uint32_t)min_qual_char, seed,
+                      unit_log2, pa.dense, pa.view, (uint4 *)rows, (unsigned long long *)status);
     });
     return rc ? rc : check_launch(who);
 }

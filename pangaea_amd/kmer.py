@@ -1720,6 +1720,87 @@ class KmerTable:
         return {"records": totals[0], "bases": totals[3], "kmers": totals[4], "hits": totals[5], "candidates": totals[8], "corrected": totals[9],
                 "reads_corrected": totals[10], "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
 
+    def _depth_args(self, lower, percentile, min_qual_char) -> tuple:
+        """(lower, percentile, quality threshold byte or 0) as pg_table_read_depths takes them"""
+        for name, v in (("lower", lower), ("percentile", percentile)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an int (got {v!r})")
+        if lower < 1:
+            raise ValueError(f"lower must be at least 1 (got {lower})")
+        if not 0 <= percentile <= 100:
+            raise ValueError(f"percentile must lie in [0, 100] (got {percentile})")
+        return int(lower), int(percentile), self._hits_window(1, None, min_qual_char)[2]
+
+    def _depths_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, args: tuple,
+                   lowercase_is_base: bool, seed: int = 0, unit_log2: int = 0, status: torch.Tensor | None = None,
+                   events: tuple | None = None) -> tuple:
+        """(rows: int32 [n_records, 4] holding the 32-bit n, present, d, w; status: int64 [2]) of pg_table_read_depths, both on the
+        device; ``args``: what ``_depth_args`` gave; ``status`` and ``events`` as for ``_hits_of``"""
+        dev = self.device
+        rows = torch.empty((n_records, 4), dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.empty(2, dtype=torch.int64, device=dev)
+        lower, percentile, mq = args
+        L = _lib.load()
+        if events:
+            events[0].record()
+        rc = L.pg_table_read_depths(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, percentile,
+                                    1 if lowercase_is_base else 0, mq, seed, unit_log2, rows.data_ptr(), status.data_ptr(), _stream_ptr(dev))
+        if events:
+            events[1].record()
+        _lib.check(rc)
+        return rows, status
+
+    def read_depths(self, text: torch.Tensor, lower: int = 1, percentile: int = 50, lowercase_is_base: bool = True,
+                    min_qual_char=None) -> torch.Tensor:
+        """(n, present, d) of every record of a four-line FASTQ text: int64 [n_records, 3] on the table's device -- n = the k-mers
+        of the record's sequence line; every k-mer has a value, its count c in this table (0: absent; saturated counts as
+        stored), taken as 0 when ``c < lower`` (``lower >= 1``); present = the values above 0; d = the value at index
+        ``((n - 1) * percentile) // 100`` of the n values in ascending order, 0 when n = 0.  ``percentile`` 50 gives the lower
+        median, as ``depth`` does over a packed stream -- the read's depth as BBNorm and khmer's normalize-by-median estimate it;
+        0 and 100 give the smallest and the largest value.  Exact for reads of any length.  ``text``, the k-mer rules and the
+        errors are those of ``read_hits``.  The table is only read (pg_fastq_index, pg_table_read_depths)."""
+        rows = self._rows_of_text(text, 4, lambda: self._depth_args(lower, percentile, min_qual_char),
+                                  lambda t, n, idx, n_rec, a: self._depths_of(t, n, idx, n_rec, 0, a, bool(lowercase_is_base)))
+        return rows[:, :3].contiguous()
+
+    def normalize_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, target: int | None = None,
+                        min_depth: int = 0, lower: int = 1, percentile: int = 50, pair: str = "any", seed: int = 0,
+                        lowercase_is_base: bool = True, min_qual_char=None) -> dict:
+        """normalise the read depth of a FASTQ file from this table (BBNorm, khmer's normalize-by-median; beside the read set of
+        scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp) and write the kept records, byte for byte and in input order, to
+        ``out1`` (and ``out2``): what the table covers more than ``target`` deep is thinned to about that depth, what it covers
+        less deep passes untouched, and reads whose depth marks them as errors can be dropped.
+
+        The depth d of a record among its n k-mers: ``read_depths`` (``lower``, ``percentile``, ``lowercase_is_base``,
+        ``min_qual_char`` as there).  Every unit -- a pair, or a record under ``pair`` "single" -- has ONE draw w in [0, 2^24), a
+        function of ``seed`` and the unit's ordinal alone (include/pangaea_feat.h, pg_table_read_depths: DRAW).  A record PASSES
+        iff n >= 1, d >= ``min_depth`` and ``w * d < target * 2^24`` (exact integers): with probability ``min(1, target / d)``;
+        a read of absent k-mers only has d = 0 and always passes the draw.  ``pair`` as for ``filter_fastq``; mates share their
+        draw, so "any" keeps a pair at its smaller depth and "both" at its larger.  ``target``: an int in [1, 2^31);
+        ``min_depth``: an int >= 0; ``seed``: an int in [0, 2^64).  The same arguments give the same output whatever the piece
+        size.  Input forms, pieces, the plain-text output under a temporary name, "after any error no output file is left" and
+        the ValueErrors naming the record's ordinal are those of ``filter_fastq``.
+
+        Returns ``records``, ``kept``, ``passed`` (records that passed on their own), ``low`` (records with n = 0 or
+        d < ``min_depth``), ``bases`` (bytes of the sequence lines), ``kmers``, ``hits`` (the sum of present), ``depth_in`` and
+        ``depth_out`` (the sum of d over all records and over the kept ones) -- totals over all inputs, exact -- and ``seconds``
+        (wall), ``device_ms`` (the pg_table_read_depths and pg_fastq_gather entries of every piece, each between two device
+        events of its own)."""
+        import time
+        t0 = time.perf_counter()
+        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
+        args = self._depth_args(lower, percentile, min_qual_char)
+        for name, v, lo, hi in (("target", target, 1, 1 << 31), ("min_depth", min_depth, 0, None), ("seed", seed, 0, 1 << 64)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v >= hi):
+                raise ValueError(f"{name} must be an int, at least {lo}" + (f" and below 2^{hi.bit_length() - 1}" if hi else "") + f" (got {v!r})")
+        unit_log2 = 1 if len(srcs) == 1 and pair != "single" else 0
+        step = _DepthsStep(self, args, bool(lowercase_is_base), int(target), int(min_depth), int(seed), unit_log2)
+        totals, device_ms = self._fastq_pieces(srcs, outs, pair, step)
+        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "low": totals[11], "bases": totals[3], "kmers": totals[4],
+                "hits": totals[5], "depth_in": totals[12], "depth_out": totals[13], "seconds": round(time.perf_counter() - t0, 6),
+                "device_ms": round(device_ms, 4)}
+
     def filter_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
                      min_hits=1, max_hits=None, pair: str = "any", lowercase_is_base: bool = True, min_qual_char=None) -> dict:
         """keep or drop the reads of a FASTQ file by the counts of their k-mers in this table (`kmc_tools filter`, khmer's
@@ -1792,8 +1873,9 @@ class KmerTable:
                 "kmers": totals[4], "hits": totals[5], "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
 
     def _fastq_pieces(self, srcs: list, outs: list, pair: str, step) -> tuple:
-        """the piece loop of ``filter_fastq``, ``trim_fastq`` and ``correct_fastq``: (totals: records, kept, passed, bases, kmers, hits,
-        trimmed, bases written, candidates, corrected, reads corrected -- exact ints --, device milliseconds of the timed entries).
+        """the piece loop of ``filter_fastq``, ``trim_fastq``, ``correct_fastq`` and ``normalize_fastq``: (totals: records, kept, passed,
+        bases, kmers, hits, trimmed, bases written, candidates, corrected, reads corrected, low, depth in, depth out -- exact ints --,
+        device milliseconds of the timed entries).
         ``step`` is what differs between them: its
         ``launch`` enqueues the per-record kernel of a piece, its ``judge`` turns the kernel's rows into pass flags and totals, its
         ``sizes`` gives the bytes each kept record leaves with and its ``gather`` writes them to their places."""
@@ -1801,7 +1883,7 @@ class KmerTable:
         dev = self.device
         piece = self._filter_piece_bytes()
         mates = pair != "single"
-        tot = torch.zeros(11, dtype=torch.int64, device=dev)
+        tot = torch.zeros(14, dtype=torch.int64, device=dev)
         timed = []                                                       # (event, event) around every timed entry; read at the end
         ins, files, tmps = [], [], []
         try:
@@ -2238,6 +2320,38 @@ class _CorrectStep:
         return torch.ones(wide.shape[0], dtype=torch.bool, device=rows.device)
 
     def sizes(self, s, rows, kept, tot):
+        return s.idx[4 * kept + 4] - s.idx[4 * kept]
+
+    def gather(self, s, n, rows, kept, dst, n_kept, out):
+        return _lib.load().pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept, out.data_ptr(),
+                                           out.numel(), _stream_ptr(self.table.device))
+
+
+class _DepthsStep:
+    """what ``KmerTable.normalize_fastq`` does with a piece: pg_table_read_depths (n, present, d and the unit's draw w per record),
+    n >= 1 and d >= min_depth and w * d < target * 2^24 in exact 64-bit integers, the records byte for byte (pg_fastq_gather)"""
+
+    def __init__(self, table, args, lenient, target, min_depth, seed, unit_log2):
+        self.table, self.args, self.lenient, self.target, self.min_depth = table, args, lenient, target, min_depth
+        self.seed, self.unit_log2 = seed, unit_log2
+
+    def launch(self, s, n, status, events):
+        return self.table._depths_of(s.text, s.have, s.idx, n, s.done, self.args, self.lenient, self.seed, self.unit_log2, status, events)[0]
+
+    def judge(self, rows, tot):
+        wide = rows.to(torch.int64) & 0xFFFFFFFF
+        nk, d, w = wide[:, 0], wide[:, 2], wide[:, 3]
+        low = (nk < 1) | (d < self.min_depth)
+        ok = ~low & (w * d < self.target << 24)              # (w < 2^24, d < 2^32, target < 2^31: both sides below 2^56)
+        tot[2] += ok.sum()
+        tot[4] += nk.sum()
+        tot[5] += wide[:, 1].sum()
+        tot[11] += low.sum()
+        tot[12] += d.sum()
+        return ok
+
+    def sizes(self, s, rows, kept, tot):
+        tot[13] += (rows[kept, 2].to(torch.int64) & 0xFFFFFFFF).sum()
         return s.idx[4 * kept + 4] - s.idx[4 * kept]
 
     def gather(self, s, n, rows, kept, dst, n_kept, out):
