@@ -981,6 +981,34 @@ int pg_mini_merge_bins_masked(const uint64_t *recv, int64_t part_stride, const i
 int pg_normalize_rows(const int32_t *m, int64_t n_rows, int n_cols, float *out, double *weight, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * An affine map of the rows of two matrices that lie side by side (additive to ABI 9): the eval-mode VAE encoder, whose
+ * Linear / BatchNorm1d (running statistics) / LeakyReLU(slope 1) / Dropout layers and l_mu fold into one matrix and one
+ * offset (pangaea_amd/models/VAENET.py: affine_encoder).  Device float32 abd [n_rows, n_abd] and tnf [n_rows, n_tnf], both
+ * contiguous; device float64 w [(n_abd + n_tnf), n_out] and b [n_out]; device float32 out [n_rows, n_out]:
+ *     out[r, :] = (float)([abd[r, :], tnf[r, :]] . w + b)
+ * Products and sums in float64, each output one chain of fused multiply-adds over the inputs in order, starting from b, and
+ * narrowed once: the bits of a row do not depend on n_rows or on where in the batch it lies.  Checked before anything is
+ * enqueued (PG_EINVAL, the argument named in pg_last_error): n_abd, n_tnf >= 0 with n_abd + n_tnf >= 1,
+ * 1 <= n_out <= PG_AFFINE_MAX_OUT, n_rows >= 0, no null pointer (abd / tnf may be null when it has no columns).
+ * n_rows == 0: PG_OK, nothing enqueued.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_AFFINE_MAX_OUT 64
+int pg_affine_rows(const float *abd, int n_abd, const float *tnf, int n_tnf, int64_t n_rows, const double *w, const double *b, int n_out,
+                   float *out, void *stream);
+/* One step of the fold that produces w and b, from the back (additive to ABI 9).  In front of the map out = y . a + c stands
+ * the eval-mode layer y = BatchNorm1d(Linear(h)): device float32 weight [n_mid, n_in], bias [n_mid] (NULL: none), the
+ * BatchNorm1d's running mean and variance [n_mid] (both NULL: no BatchNorm1d), gamma and beta [n_mid] (NULL: 1 and 0) and its
+ * eps; device float64 a [n_mid, n_out] (NULL: the identity, n_mid == n_out) and c [n_out] (NULL: zeros).  With
+ * s = gamma / sqrt(var + eps):
+ *     a_out[i, o] = sum_j weight[j, i] * s[j] * a[j, o]        c_out[o] = c[o] + sum_j ((bias[j] - mean[j]) * s[j] + beta[j]) * a[j, o]
+ * device float64 a_out [n_in, n_out] and c_out [n_out] (neither may overlap a or c), all contiguous, in float64, one launch.
+ * PG_EINVAL with the argument named: sizes outside [1, 2^24], n_out > PG_AFFINE_MAX_OUT, a null weight, a_out or c_out, a mean
+ * without a variance, gamma or beta without a mean, a null a with n_mid != n_out. */
+int pg_affine_fold(const float *weight, const float *bias, const float *bn_mean, const float *bn_var, const float *bn_gamma,
+                   const float *bn_beta, double bn_eps, int n_in, int n_mid, const double *a, const double *c, int n_out,
+                   double *a_out, double *c_out, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Cache files.  Rows as the reference binaries print them: "<name>,v1,...,vD\n", numbers through
  * ostream<<double (%g, six significant digits; count_tnf.cpp:293-303), gzip container.
  * names: n_rows NUL-terminated strings back to back.  mat: host int32 [n_rows, n_cols].

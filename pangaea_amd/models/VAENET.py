@@ -23,8 +23,39 @@ import torch
 import torch.nn as nn
 from torch.nn import functional as F
 
+from .. import _lib
 from ..runtime import join_warm_blas
 from ..utils import EarlyStopping
+
+
+def _fold_layer(lin, bn, A, c):
+    """the map ``out = y @ A + c`` (float64; ``A`` None: the identity) behind the eval-mode layer ``y = bn(lin(h))`` (``bn`` may be
+    None) as ``out = h @ A2 + c2``: with ``s = gamma / sqrt(var + eps)``, ``A2 = (lin.weight.T * s) @ A`` and
+    ``c2 = c + ((lin.bias - mean) * s + beta) @ A``.  float32 parameters on a GPU take ONE kernel (pg_affine_fold) instead of
+    fourteen small ones; anything else (the CPU, other dtypes) the same arithmetic as tensor operations."""
+    params = [lin.weight, lin.bias] + ([bn.running_mean, bn.running_var, bn.weight, bn.bias] if bn is not None else [None] * 4)
+    n_out = lin.out_features if A is None else A.shape[1]
+    if lin.weight.is_cuda and n_out <= _lib.AFFINE_MAX_OUT and all(p is None or (p.dtype == torch.float32 and p.is_contiguous()) for p in params):
+        from ..kmer import _stream_ptr
+        dev = lin.weight.device
+        A2 = torch.empty((lin.in_features, n_out), dtype=torch.float64, device=dev)
+        c2 = torch.empty(n_out, dtype=torch.float64, device=dev)
+        ptr = [None if t is None else t.data_ptr() for t in params + [A, c, A2, c2]]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().pg_affine_fold(*ptr[:6], bn.eps if bn is not None else 0.0, lin.in_features, lin.out_features,
+                                                  ptr[6], ptr[7], n_out, ptr[8], ptr[9], _stream_ptr(dev)))
+        return A2, c2
+    W = lin.weight.double().t()
+    t = lin.bias.double() if lin.bias is not None else W.new_zeros(W.shape[1])
+    if bn is not None:
+        s = torch.sqrt(bn.running_var.double() + bn.eps)
+        s = bn.weight.double() / s if bn.weight is not None else s.reciprocal()
+        beta = bn.bias.double() if bn.bias is not None else torch.zeros_like(s)
+        t = torch.addcmul(beta, t - bn.running_mean.double(), s)
+        W = W * s
+    if A is None:
+        return W.contiguous(), t
+    return W @ A, torch.addmv(c, A.t(), t)
 
 
 class VaritionalAutoEncoder(nn.Module):
@@ -58,6 +89,39 @@ class VaritionalAutoEncoder(nn.Module):
 
     def emebdding(self, abd, tnf):          # (sic) the reference's spelling, VAENET.py:232
         return self.l_mu(self.encoder(torch.cat((abd, tnf), 1)))
+
+    @torch.no_grad()
+    def affine_encoder(self):
+        """``emebdding`` as ONE affine map, when it is one: ``(W_eff float64 [input, latent], b_eff float64 [latent])`` on the
+        module's device with ``mu = cat(abd, tnf) @ W_eff + b_eff``, else ``None``.  In eval mode BatchNorm1d is the affine map
+        of its running statistics, Dropout the identity and ``LeakyReLU(True)`` (slope 1.0, the reference's quirk) too, so the
+        whole stack folds into ``l_mu``.  The fold runs from ``l_mu`` backwards, a Linear with the BatchNorm1d behind it at a
+        time (every product is as narrow as the latent), in float64, on the device and without a host sync.  Any other module,
+        a BatchNorm1d in training mode, without running statistics or not behind a Linear, an active Dropout or another slope
+        give ``None``: the caller runs the layers then."""
+        layers, bn = [(self.l_mu, None)], None            # (Linear, the BatchNorm1d behind it), from the back
+        for m in reversed(list(self.encoder.children())):
+            if isinstance(m, nn.Linear):
+                layers.append((m, bn))
+                bn = None
+            elif isinstance(m, nn.BatchNorm1d):
+                if bn is not None or m.training or m.running_mean is None or m.running_var is None:
+                    return None
+                bn = m
+            elif isinstance(m, nn.LeakyReLU):
+                if m.negative_slope != 1.0:
+                    return None
+            elif isinstance(m, nn.Dropout):
+                if m.training:
+                    return None
+            else:
+                return None
+        if bn is not None:
+            return None
+        A = c = None
+        for lin, bn in layers:
+            A, c = _fold_layer(lin, bn, A, c)
+        return A, c
 
     def forward(self, abd, tnf, epsilon=None):
         mu, logsigma, latent = self.calcu_latent(abd, tnf, epsilon)
@@ -104,12 +168,34 @@ class VAENET:
 
     @torch.no_grad()
     def encode(self, data, batch_rows: int = 1 << 16) -> torch.Tensor:
-        """mu for every row of a ``pangaea_amd.data.Data`` set, in dataset order, on the device"""
+        """mu for every row of a ``pangaea_amd.data.Data`` set, in dataset order, on the device.
+
+        In eval mode the encoder is one affine map (``VaritionalAutoEncoder.affine_encoder``): it is folded once per call --
+        never kept, training changes the weights between two encodes -- and every slice is ONE kernel (pg_affine_rows) that
+        reads the two normalised matrices where they lie, instead of cat, two 512-wide fp32 GEMMs, two BatchNorm passes, two
+        identity activations and l_mu.  The layers themselves (``emebdding``) run when the stack is not affine, on the CPU,
+        for inputs that are not contiguous float32 matrices, for a latent wider than the kernel takes, and with
+        PG_ENCODE_FUSED=0 (the A/B switch)."""
         self.network.eval()
         abd, tnf = data.abd_dev.to(self.device), data.tnf_dev.to(self.device)
         out = torch.empty((abd.shape[0], self.network.l_mu.out_features), dtype=torch.float32, device=self.device)
-        for a in range(0, abd.shape[0], batch_rows):
-            out[a:a + batch_rows] = self.network.emebdding(abd[a:a + batch_rows], tnf[a:a + batch_rows])
+        fold = None
+        if (self.device.type == "cuda" and os.environ.get("PG_ENCODE_FUSED", "1") != "0" and out.shape[1] <= _lib.AFFINE_MAX_OUT
+                and all(m.dim() == 2 and m.dtype == torch.float32 and m.is_contiguous() for m in (abd, tnf))):
+            fold = self.network.affine_encoder()
+        if fold is None:
+            for a in range(0, abd.shape[0], batch_rows):
+                out[a:a + batch_rows] = self.network.emebdding(abd[a:a + batch_rows], tnf[a:a + batch_rows])
+            return out
+        from ..kmer import _stream_ptr
+        w, b = fold
+        L = _lib.load()
+        with torch.cuda.device(self.device):
+            stream = _stream_ptr(self.device)
+            for a in range(0, abd.shape[0], batch_rows):
+                xa, xt, o = abd[a:a + batch_rows], tnf[a:a + batch_rows], out[a:a + batch_rows]
+                _lib.check(L.pg_affine_rows(xa.data_ptr(), xa.shape[1], xt.data_ptr(), xt.shape[1], xa.shape[0],
+                                            w.data_ptr(), b.data_ptr(), o.shape[1], o.data_ptr(), stream))
         return out
 
     # ------------------------------------------------------------------ hipGraph capture of the two launch-bound loops
