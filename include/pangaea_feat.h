@@ -1009,6 +1009,36 @@ int pg_affine_fold(const float *weight, const float *bias, const float *bn_mean,
                    double *a_out, double *c_out, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Pairwise-distance sums per cluster (additive to ABI 9): the O(N^2) part of the silhouette score by which
+ * pangaea_amd/clustering.py: choose_clusters picks the number of clusters (the sweep whose parameters the reference's
+ * cluster_barcode_reads still carries -- range_step, patience, delta, src/clustering.py:70 -- next to its unused import of
+ * silhouette_score, src/clustering.py:5).  Device float32 q [n_q, dim] and x [n_x, dim], contiguous, x SORTED by cluster;
+ * device int64 seg [k + 1] with seg[0] == 0, seg[k] == n_x, non-decreasing (rows seg[c] .. seg[c+1]-1 of x are cluster c; empty
+ * clusters anywhere); device float64 out [n_q, k]:
+ *     out[i][c] = sum over j in cluster c of |q_i - x_j|_2
+ * |q_i - x_j| from the differences (subtract, square, accumulate over dim in float32, one square root), never from
+ * |q|^2 + |x|^2 - 2 q.x; the sum over j in float64, float32 partial sums of at most PG_CLUSTER_GROUP distances folded into it.
+ * A sum over an empty cluster and a sum over rows identical to q_i are exactly 0.  The reference range is cut into n_splits
+ * pieces [n_x * s / n_splits, n_x * (s + 1) / n_splits), one set of workgroups each (0: the library chooses, one when the query
+ * rows alone fill the device; > 0: forced); with more than one, every piece writes its own [n_q, k] plane into the workspace
+ * and the planes are added in order of s: no floating-point atomics, the same bits from run to run for the same arguments.
+ * pg_cluster_dist_sums_workspace_bytes: what that takes (0 with one split; at most n_splits * n_q * k * 8), or PG_EINVAL.
+ * dim == 32 (the -ld default) keeps the query row in registers; every other dim takes a generic loop.
+ * Checked before anything is enqueued (PG_EINVAL, the argument named in pg_last_error): n_q, n_x >= 0, 1 <= dim <=
+ * PG_CLUSTER_MAX_DIM, 1 <= k <= PG_CLUSTER_MAX_K, 0 <= n_splits <= PG_CLUSTER_MAX_SPLITS, no null q, x, seg or out, a workspace of
+ * the size above.  seg lies on the device and is not looked at by the host (its caller built it); the kernel clamps its values
+ * into the range of its piece, so whatever it holds, nothing outside x is read.  n_q == 0 or n_x == 0: PG_OK, nothing enqueued,
+ * out untouched.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_CLUSTER_MAX_DIM 256
+#define PG_CLUSTER_MAX_K 4096
+#define PG_CLUSTER_MAX_SPLITS 64
+#define PG_CLUSTER_GROUP 8
+int64_t pg_cluster_dist_sums_workspace_bytes(int64_t n_q, int64_t n_x, int k, int n_splits);
+int pg_cluster_dist_sums(const float *q, int64_t n_q, const float *x, int64_t n_x, int dim, const int64_t *seg, int k, int n_splits,
+                         double *out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * Cache files.  Rows as the reference binaries print them: "<name>,v1,...,vD\n", numbers through
  * ostream<<double (%g, six significant digits; count_tnf.cpp:293-303), gzip container.
  * names: n_rows NUL-terminated strings back to back.  mat: host int32 [n_rows, n_cols].

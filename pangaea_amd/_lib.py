@@ -59,6 +59,7 @@ DUMP_CLEAN = (1 << 64) - 1         # PG_DUMP_CLEAN: pg_dump_parse's status word 
 DUMP_BAD_LENGTH, DUMP_NO_TAB, DUMP_BAD_COUNT, DUMP_CAPACITY = 1, 2, 3, 4
 MAX_ROWS = (1 << 22) - 2
 AFFINE_MAX_OUT = 64                # PG_AFFINE_MAX_OUT: the widest output of pg_affine_rows / pg_affine_fold
+CLUSTER_MAX_DIM, CLUSTER_MAX_K, CLUSTER_MAX_SPLITS, CLUSTER_GROUP = 256, 4096, 64, 8      # PG_CLUSTER_*: the limits of pg_cluster_dist_sums
 # PG_COMBINE_*: what pg_table_combine_aligned / pg_table_combine_items store for the counts a, b two tables hold of a k-mer
 COMBINE_MIN, COMBINE_MAX, COMBINE_DIFF, COMBINE_LEFT, COMBINE_ONLY, COMBINE_KEEP = 0, 1, 2, 3, 4, 5
 COMBINE_OPS = {"min": COMBINE_MIN, "max": COMBINE_MAX, "diff": COMBINE_DIFF, "left": COMBINE_LEFT, "only": COMBINE_ONLY, "keep": COMBINE_KEEP}
@@ -214,6 +215,8 @@ def load() -> C.CDLL:
         "pg_normalize_rows": (i32, [vp, i64, i32, vp, vp, vp]),
         "pg_affine_rows": (i32, [vp, i32, vp, i32, i64, vp, vp, i32, vp, vp]),
         "pg_affine_fold": (i32, [vp, vp, vp, vp, vp, vp, C.c_double, i32, i32, vp, vp, i32, vp, vp, vp]),
+        "pg_cluster_dist_sums_workspace_bytes": (i64, [i64, i64, i32, i32]),
+        "pg_cluster_dist_sums": (i32, [vp, i64, vp, i64, i32, vp, i32, i32, vp, vp, i64, vp]),
         "pg_write_csv_gz": (i32, [cp, cp, vp, i64, i64]),
         "pg_extract_reads": (i32, [cp, cp, cp, cp, C.POINTER(i64)]),
     }
@@ -249,7 +252,8 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_table_merge", "pg_table_merge_aligned", "pg_table_merge_aligned_applies",
            "pg_table_combine_aligned", "pg_table_combine_items", "pg_table_compare",
            "pg_mini_find_applies", "pg_mini_find",
-           "pg_features", "pg_normalize_rows", "pg_affine_rows", "pg_affine_fold", "pg_write_csv_gz", "pg_extract_reads"]
+           "pg_features", "pg_normalize_rows", "pg_affine_rows", "pg_affine_fold",
+           "pg_cluster_dist_sums_workspace_bytes", "pg_cluster_dist_sums", "pg_write_csv_gz", "pg_extract_reads"]
 
 
 def check(rc: int) -> int:

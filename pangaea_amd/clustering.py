@@ -15,6 +15,9 @@ row argmin).  Nothing but the final labels returns to the host.  Random draws co
 reference's order (``init_all`` seeds it; the device generator of the k-means++ seeding is seeded from it), but bucket numbering follows
 ``torch.unique`` instead of ``unordered_map`` iteration, so labels are NOT bit-comparable with the reference
  -- parity is by inertia and adjusted Rand index.
+
+Without ``-c``: ``choose_clusters`` picks k by a silhouette sweep (``--auto_clusters silhouette``), its O(N^2) distance sums in
+one HIP kernel (``dist_sums``: pg_cluster_dist_sums); the sweep's own draws are put back, so the fit that follows is ``-c K``'s.
 """
 from __future__ import annotations
 
@@ -184,6 +187,10 @@ def weighted_kmeans(x: torch.Tensor, w: torch.Tensor, k: int, n_init: int = 1, m
     return best
 
 
+class TooFewReducedPoints(RuntimeError):
+    """the point reducer left fewer points than clusters were asked for (the library's RuntimeError, by a name of its own)"""
+
+
 class RPHKMeans:
     """device-resident ``rph_kmeans.RPHKMeans`` (constructor arguments and fitted attributes as the library's)"""
 
@@ -243,7 +250,7 @@ class RPHKMeans:
         skeleton labels) -- the weighted skeleton k-means of rph_kmeans_.py:116-129, on the device"""
         red, weight, labels, it = self.reduce_points(x)
         if red.shape[0] < self.n_clusters:
-            raise RuntimeError("Number of reduced points is too small, please try smaller w or larger proj_num")
+            raise TooFewReducedPoints("Number of reduced points is too small, please try smaller w or larger proj_num")
         centers, pred, inertia = weighted_kmeans(red, weight, self.n_clusters, n_init=self.skeleton_n_init)
         return centers, red, weight, labels, it, inertia, pred
 
@@ -315,6 +322,187 @@ def clustering_rph_kmeans_sharded(mu_local: torch.Tensor, mu_all, k: int, n_init
     return got[:, 0].cpu().numpy().astype(np.int32) if me == 0 else None
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The number of clusters by silhouette score.  The reference's cluster_barcode_reads still carries the parameters of a sweep
+# over k (range_step=(4, 100, 3), patience=7, delta=0.0001; clustering.py:70) next to an unused import of sklearn's
+# silhouette_score (clustering.py:5): O(N^2) distances per k, hopeless on the host at 10^6 barcodes.  Here the distance sums
+# are one HIP kernel (csrc/cluster.hip: pg_cluster_dist_sums), the score a few float64 tensor operations on top of it.
+
+# the torch form of dist_sums works in [query rows, reference rows] tiles of at most 2^20 distances: torch.cdist calls with tens
+# of millions of outputs came back partly zero on the MI355X (50 000 x 50 000 rows in blocks of 1 342 x 50 000), small ones agree
+# with the kernel and with numpy
+_TORCH_FORM_TILE, _TORCH_FORM_ROWS = 1 << 20, 1 << 14
+
+
+def _as_labels(labels, device) -> torch.Tensor:
+    return torch.as_tensor(np.ascontiguousarray(labels) if isinstance(labels, np.ndarray) else labels).to(device=device, dtype=torch.int64)
+
+
+@torch.no_grad()
+def dist_sums(q, x, labels, k: int, n_splits: int = 0) -> torch.Tensor:
+    """``S[i, c] = sum over the rows j of x with labels[j] == c of |q_i - x_j|_2``: float64 [n_q, k] on the device of ``x``.
+
+    On the GPU: ``x`` is sorted by label (stable argsort, gathered on the device), the segment starts come from ``bincount``,
+    and pg_cluster_dist_sums does the rest on float32 rows -- ``q`` and ``x`` are converted to contiguous float32 when they
+    are not (a non-contiguous slice is COPIED, not refused).  ``n_splits``: 0 lets the library cut the reference range so that
+    few query rows still fill the device; > 0 forces it (tests).  On a CPU tensor, or with PG_SILHOUETTE_KERNEL=0 (the A/B
+    switch), the torch form: tiles of ``torch.cdist`` on float64 copies, formed from the differences, times a one-hot matrix."""
+    x = torch.as_tensor(x)
+    q = torch.as_tensor(q).to(x.device)
+    labels = _as_labels(labels, x.device)
+    if q.dim() != 2 or x.dim() != 2 or q.shape[1] != x.shape[1]:
+        raise ValueError(f"dist_sums: q {tuple(q.shape)} and x {tuple(x.shape)} are not two matrices of one width")
+    if labels.shape != (x.shape[0],):
+        raise ValueError(f"dist_sums: {tuple(labels.shape)} labels for {x.shape[0]} rows")
+    n_q, n_x = q.shape[0], x.shape[0]
+    out = torch.zeros((n_q, k), dtype=torch.float64, device=x.device)
+    if n_q == 0 or n_x == 0:
+        return out
+    if not x.is_cuda or os.environ.get("PG_SILHOUETTE_KERNEL", "1") == "0":
+        onehot = torch.zeros((n_x, k), dtype=torch.float64, device=x.device)
+        onehot[torch.arange(n_x, device=x.device), labels] = 1.0
+        xd, qd = x.double(), q.double()
+        x_step = min(n_x, _TORCH_FORM_ROWS)
+        q_step = max(1, _TORCH_FORM_TILE // x_step)
+        for lo in range(0, n_q, q_step):
+            for xlo in range(0, n_x, x_step):
+                d = torch.cdist(qd[lo:lo + q_step], xd[xlo:xlo + x_step], compute_mode="donot_use_mm_for_euclid_dist")
+                out[lo:lo + q_step] += d @ onehot[xlo:xlo + x_step]
+        return out
+    from . import _lib
+    L = _lib.load()
+    order = torch.argsort(labels, stable=True)
+    xs = x.to(torch.float32)[order].contiguous()
+    qs = q.to(torch.float32).contiguous()
+    counts = torch.bincount(labels, minlength=k)            # (refuses negative labels itself)
+    if counts.numel() != k:
+        raise ValueError(f"dist_sums: labels outside [0, {k})")
+    seg = torch.zeros(k + 1, dtype=torch.int64, device=x.device)
+    seg[1:] = torch.cumsum(counts, 0)                       # seg[0] = 0, seg[k] = n_x, non-decreasing: what the kernel is promised
+    need =_lib.check(L.pg_cluster_dist_sums_workspace_bytes(n_q, n_x, k, n_splits))
+    work = torch.empty(need, dtype=torch.uint8, device=x.device) if need else None
+    with torch.cuda.device(x.device):
+        _lib.check(L.pg_cluster_dist_sums(qs.data_ptr(), n_q, xs.data_ptr(), n_x, x.shape[1], seg.data_ptr(), k, n_splits, out.data_ptr(),
+                                          work.data_ptr() if need else None, need, torch.cuda.current_stream().cuda_stream))
+    return out
+
+
+def _checked_labels(x: torch.Tensor, labels, k: int):
+    """(labels int64 on the device of x, cluster sizes int64 [k]) after the refusals of the silhouette"""
+    if k < 2:
+        raise ValueError(f"silhouette: k = {k}, at least 2 clusters are needed")
+    labels = _as_labels(labels, x.device)
+    if labels.shape != (x.shape[0],):
+        raise ValueError(f"silhouette: {tuple(labels.shape)} labels for {x.shape[0]} rows")
+    if labels.numel() and (int(labels.min()) < 0 or int(labels.max()) >= k):
+        raise ValueError(f"silhouette: labels outside [0, {k})")
+    counts = torch.bincount(labels, minlength=k)
+    if int((counts > 0).sum()) < 2:
+        raise ValueError("silhouette: fewer than two non-empty clusters")
+    return labels, counts
+
+
+@torch.no_grad()
+def silhouette_samples(x, labels, k: int, rows=None) -> torch.Tensor:
+    """the silhouette coefficient of every row (or of ``rows``, indices into x) as scikit-learn defines it: with
+    ``S = dist_sums(.)``, ``a_i = S[i, own] / (n_own - 1)``, ``b_i = min over the other non-empty clusters of S[i, c] / n_c``,
+    ``s_i = (b_i - a_i) / max(a_i, b_i)``, and 0 for the only row of its cluster or where the quotient is not finite.
+    ``rows`` restricts the QUERY side only: the distances still run to all rows of x and the cluster sizes are those of all
+    rows, so every s_i is exact (scikit-learn's ``sample_size`` thins both sides instead).  float64 on the device of x."""
+    x = torch.as_tensor(x)
+    labels, counts = _checked_labels(x, labels, k)
+    if rows is None:
+        q, own = x, labels
+    else:
+        rows = torch.as_tensor(rows).to(device=x.device, dtype=torch.int64)
+        q, own = x[rows], labels[rows]
+    s = dist_sums(q, x, labels, k)
+    n_own = counts[own]
+    a = s.gather(1, own[:, None]).squeeze(1) / (n_own - 1).clamp(min=1).double()
+    other = s / counts.double()[None, :]                                    # (an empty cluster: 0 / 0, masked next)
+    other.masked_fill_((counts == 0)[None, :], float("inf"))
+    other.scatter_(1, own[:, None], float("inf"))
+    b = other.min(dim=1).values
+    sil = (b - a) / torch.maximum(a, b)
+    return torch.where((n_own > 1) & torch.isfinite(sil), sil, torch.zeros_like(sil))
+
+
+def _sample_rows(n: int, sample, seed: int):
+    """``sample`` distinct rows of n, sorted, from a generator of its own (numpy's global one, whose order the RPH draws depend
+    on, is never touched); None when that is all rows"""
+    if sample is None or sample >= n:
+        return None
+    return np.sort(np.random.RandomState(seed).choice(n, int(sample), replace=False))
+
+
+def silhouette_score(x, labels, k: int, sample=None, seed: int = 0) -> float:
+    """the mean silhouette coefficient; with ``sample`` < N the mean over that many rows drawn by ``RandomState(seed)`` --
+    an unbiased estimate, every term exact (see silhouette_samples)"""
+    x = torch.as_tensor(x)
+    return float(silhouette_samples(x, labels, k, rows=_sample_rows(x.shape[0], sample, seed)).mean())
+
+
+def choose_clusters(embedding, range_step=(4, 100, 3), patience=7, delta=1e-4, sweep_n_init=5, sample=16384, seed=0, device=None):
+    """the number of clusters by silhouette score: ``(best_k, table)``.  Visits k in ``range(*range_step)`` (no further than
+    N - 1), fits ``RPHKMeans(n_clusters=k, n_init=sweep_n_init)`` to the embedding -- copied to the device once -- and scores the
+    fit on the same ``sample`` rows every time.  A k becomes the best when its score exceeds the best so far by more than
+    ``delta``; after ``patience`` consecutive k without that the sweep ends.  ``table``: ``(k, score, inertia, n_nonempty)``
+    per visited k; a fit with fewer than two non-empty clusters scores -1; a k for which the point reducer leaves fewer than k
+    points (TooFewReducedPoints) ends the sweep like patience does.  The defaults are the reference's
+    (cluster_barcode_reads, clustering.py:70).  The fits draw from numpy's global generator as every RPHKMeans does; its
+    state is put back at the end, so that whatever follows draws what it would have drawn without the sweep."""
+    if device is None:
+        if not torch.cuda.is_available():
+            raise RuntimeError("choose_clusters runs on the GPU; pass device='cpu' explicitly to run the same torch ops on the host")
+        device = torch.device("cuda", torch.cuda.current_device())
+    x = torch.as_tensor(np.ascontiguousarray(embedding) if isinstance(embedding, np.ndarray) else embedding).to(device)
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.float()
+    n = x.shape[0]
+    if n < 6:
+        raise ValueError(f"choose_clusters: {n} rows, at least 6 are needed")
+    rows = _sample_rows(n, sample, seed)
+    table, best_k, best, stale = [], None, -np.inf, 0
+    state = np.random.get_state()
+    try:
+        for k in range(*range_step):
+            if k > n - 1:
+                break
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore")
+                    clt = RPHKMeans(n_clusters=k, n_init=sweep_n_init, verbose=0, device=device).fit(x)
+            except TooFewReducedPoints:
+                # the rows collapse onto fewer than k reduced points (tight, well separated groups): this k cannot be fitted,
+                # larger ones neither -- the sweep ends here with what it has, unless it has nothing
+                if best_k is None:
+                    raise
+                logging.info(f"silhouette sweep: fewer than {k} reduced points, stopping at k = {table[-1][0]}")
+                break
+            labels =torch.from_numpy(clt.labels_.astype(np.int64)).to(device)
+            nonempty = int((torch.bincount(labels, minlength=k) > 0).sum())
+            score = float(silhouette_samples(x, labels, k, rows=rows).mean()) if nonempty >= 2 else -1.0
+            table.append((k, score, float(clt.inertia_), nonempty))
+            if score > best + delta:
+                best_k, best, stale = k, score, 0
+            else:
+                stale += 1
+                if stale >= patience:
+                    break
+    finally:
+        np.random.set_state(state)
+    if best_k is None:
+        raise ValueError(f"choose_clusters: range_step = {tuple(range_step)} holds no k in [2, {n - 1}]")
+    return best_k, table
+
+
+def write_silhouette_tsv(path: str, table) -> None:
+    with open(path, "w") as tsv:
+        tsv.write("k\tscore\tinertia\tclusters\n")
+        for k, score, inertia, nonempty in table:
+            tsv.write("%d\t%.6f\t%.6f\t%d\n" % (k, score, inertia, nonempty))
+
+
 def write_clusters_tsv(path: str, clusters, barcodes) -> None:
     """``<label>\\t<bc1>,<bc2>,...`` per label in first-seen order (clustering.py:107-112)"""
     cluster2barcodes = defaultdict(list)
@@ -325,10 +513,13 @@ def write_clusters_tsv(path: str, clusters, barcodes) -> None:
             tsv.write("{}\t{}\n".format(cluster_id, ",".join(cluster2barcodes[cluster_id])))
 
 
-def cluster_barcode_reads(args, model_path, cluster_path, script_path, clusters=None):
+def cluster_barcode_reads(args, model_path, cluster_path, script_path, clusters=None, device=None):
     """step 3 of pangaea.py: latent.npz/barcodes.npz -> clusters.npz, clusters.tsv, cluster_bin<label>.{fq,barcode},
     clustering_finished -- the on-disk bin layout the unchanged reassembly stage reads (bin_assembly.sh:18).
-    ``clusters``: labels already computed for the rows of latent.npz (the sharded Lloyd of a multi-rank run)."""
+    ``clusters``: labels already computed for the rows of latent.npz (the sharded Lloyd of a multi-rank run).
+    Without ``args.clusters``: ``args.auto_clusters == "silhouette"`` picks the number by the silhouette sweep over
+    ``args.cluster_range`` (choose_clusters; its table goes to silhouette.tsv), anything else asks the reference's metaphlan
+    script.  ``device``: where the sweep and the fit run when not on the current GPU."""
     from .binwriter import extract_reads
     output_npz = os.path.join(cluster_path, "clusters.npz")
     output_tsv = os.path.join(cluster_path, "clusters.tsv")
@@ -347,6 +538,15 @@ def cluster_barcode_reads(args, model_path, cluster_path, script_path, clusters=
         barcodes = np.load(barcodes_path)["arr_0"]
         if args.clusters:
             num_classes = args.clusters
+        elif getattr(args, "auto_clusters", "metaphlan") == "silhouette":
+            # no external profiler: the sweep the reference's signature still describes, scored on the GPU (choose_clusters)
+            spec = getattr(args, "cluster_range", None) or "4,100,3"
+            range_step = tuple(int(v) for v in spec.split(",")) if isinstance(spec, str) else tuple(spec)
+            if len(range_step) != 3 or range_step[2] < 1:
+                raise ValueError(f"--cluster_range {spec!r}: LO,HI,STEP with STEP >= 1 expected")
+            num_classes, table = choose_clusters(embedding, range_step=range_step, device=device)
+            write_silhouette_tsv(os.path.join(cluster_path, "silhouette.tsv"), table)
+            logging.info(f"estimated num_classes: {num_classes}")
         else:
             # the reference estimates 8 x Shannon diversity with metaphlan (clustering.py:92-102): an external tool,
             # outside this path -- run the reference's own script when it is installed next to us
@@ -359,7 +559,12 @@ def cluster_barcode_reads(args, model_path, cluster_path, script_path, clusters=
             num_classes = int(8 * shannon)
             logging.info(f"estimated num_classes: {num_classes}")
             run_cmd(["rm", "-rf", os.path.join(cluster_path, "metaphlan_tmp")])
-        clusters = clustering_rph_kmeans(embedding, num_classes)
+        if device is None:
+            clusters = clustering_rph_kmeans(embedding, num_classes)
+        else:                                               # (the same call on a named device: the host tests)
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                clusters = RPHKMeans(n_init=20, n_clusters=num_classes, verbose=0, device=device).fit_predict(embedding)
         np.savez(output_npz, clusters)
         logging.info("saving clustering tsv")
         write_clusters_tsv(output_tsv, clusters, barcodes)

@@ -70,6 +70,11 @@ def build_parser() -> argparse.ArgumentParser:
     # additive option (not in the reference)
     p.add_argument("--reference_src", type=str, default=os.environ.get("PANGAEA_SRC", ""),
                    help="src/ directory of a Pangaea checkout: where step 4 and the metaphlan helper scripts live")
+    p.add_argument("--auto_clusters", choices=("metaphlan", "silhouette"), default="metaphlan",
+                   help="how step 3 picks the number of clusters without -c: metaphlan (the reference's 8 x Shannon diversity, needs its "
+                        "scripts/calculate_diversity.sh and a metaphlan db) or silhouette (a sweep over k scored by silhouette on the GPU, "
+                        "from this package alone; in a multi-rank run rank 0 sweeps alone after the ranks have left the group)")
+    p.add_argument("--cluster_range", type=str, default="4,100,3", help="LO,HI,STEP of the silhouette sweep over k (default 4,100,3)")
     return p
 
 
