@@ -128,51 +128,12 @@ struct RowBits {
 // it ends (the callers keep the bucket of EVERY position in an LDS column of the lane and walk over the set bits of the end mask).
 // DELAY (k > 21): the minimizer of a k-mer is taken over its central W M-mers only (pg_device.hpp: mini_window), i.e. the
 // window that ends `off` characters before the k-mer does -- the window minimum passes through a delay line of `off` <= 5 steps.
-constexpr int MINI_MAX_OFF = 5;
+// The forms themselves -- the canonical M-mer in six instructions, the window minimum in two, the "same value as before" mask in
+// two -- are in mini_forms.hpp, where host code can compile and check them against the definition.
 template <int W, bool DELAY, int M, class PerPos>
 __device__ __forceinline__ void mini_minimizers(const Word &x, int off, PerPos &&per_pos)
 {
-    constexpr uint32_t MMASK = (1u << (2 * M)) - 1u;
-    uint32_t win[W];                                            // win[0] = newest hashed canonical M-mer
-    uint32_t dl[DELAY ? MINI_MAX_OFF : 1];                      // dl[i] = window minimum i + 1 characters ago
-#pragma unroll
-    for (int i = 0; i < W; ++i) win[i] = 0xffffffffu;
-#pragma unroll
-    for (int i = 0; i < (DELAY ? MINI_MAX_OFF : 1); ++i) dl[i] = 0xffffffffu;
-    // The M-mer that ends at character q of the 64 characters (pw, cw) is cut straight out of them -- its reverse complement out of
-    // the words as they are (oldest character lowest, complemented: ^ 2 per character), the M-mer itself out of the character-
-    // reversed words (newest character lowest) --, at offsets that are constants once the loops below are unrolled: one funnel
-    // shift + one mask each, no rolling state, no pre-roll of the characters in front of the first wanted M-mer.  (The values
-    // are those of the rolling forms fwm = ((fwm << 2) | ch) & MMASK, rcm = (rcm >> 2) | ((ch ^ 2) << 2 (M - 1)).)
-    const uint64_t rlo = rev2_64(x.cw), rhi = rev2_64(x.pw);
-    auto cut = [](uint64_t lo, uint64_t hi, int b) -> uint32_t {                  // 32 bits from bit b of (hi:lo)
-        return b == 0 ? (uint32_t)lo : b < 64 ? (uint32_t)((lo >> b) | (hi << (64 - b))) : (uint32_t)(hi >> (b - 64));
-    };
-    constexpr uint32_t COMPL = 0xAAAAAAAAu & MMASK;
-    constexpr int PRE = W - 1 + (DELAY ? MINI_MAX_OFF : 0);     // M-mers in front of the word that are wanted in the window
-    static_assert(32 - PRE >= M - 1, "the first wanted M-mer lies inside the previous word");
-    auto step = [&](int q) -> uint32_t {                         // the minimizer value of the k-mer that ends at character q
-        const uint32_t fwm = cut(rlo, rhi, 2 * (63 - q)) & MMASK;
-        const uint32_t rcm = (cut(x.pw, x.cw, 2 * (q - (M - 1))) & MMASK) ^ COMPL;
-#pragma unroll
-        for (int i = W - 1; i > 0; --i) win[i] = win[i - 1];
-        win[0] = mhash(fwm < rcm ? fwm : rcm);
-        uint32_t mv = win[0];
-#pragma unroll
-        for (int i = 1; i < W; ++i) mv = win[i] < mv ? win[i] : mv;
-        if (!DELAY) return mv;
-        uint32_t use = mv;                                      // (off is wave-uniform: scalar selects)
-#pragma unroll
-        for (int i = 0; i < MINI_MAX_OFF; ++i) use = off == i + 1 ? dl[i] : use;
-#pragma unroll
-        for (int i = MINI_MAX_OFF - 1; i > 0; --i) dl[i] = dl[i - 1];
-        dl[0] = mv;
-        return use;
-    };
-#pragma unroll
-    for (int c = 32 - PRE; c < 32; ++c) step(c);
-#pragma unroll
-    for (int p = 0; p < 32; ++p) per_pos(p, step(32 + p));
+    mini_minimizers_of_word<W, DELAY, M>(x.pw, x.cw, off, per_pos);
 }
 
 // bit p of the result: bits p - n + 1 .. p of m are all set (1 <= n <= 32)
@@ -253,8 +214,9 @@ __global__ __launch_bounds__(BLOCK) void mini_plan_kernel(const uint64_t *__rest
 {
     __shared__ uint32_t coarse[1 << MINI_MAX_BITS1];
     __shared__ uint32_t n_long_here;                             // records of more than SHORT_MAX k-mers in this chunk
-    __shared__ uint16_t col[32 * BLOCK];                         // the bucket of every position of the lane's word (a column per lane)
-    const int n_dig = 1 << (bits - bits2);
+    __shared__ uint32_t col[8 * BLOCK];                          // the region byte of every position of the lane's word (a column per lane,
+                                                                 // four positions to a dword: region_bytes_push)
+    const int bits1 = bits - bits2, n_dig = 1 << bits1;
     for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         for (int i = threadIdx.x; i < (1 << MINI_MAX_BITS1); i += BLOCK) coarse[i] = 0;
         if (threadIdx.x == 0) n_long_here = 0;
@@ -269,16 +231,19 @@ __global__ __launch_bounds__(BLOCK) void mini_plan_kernel(const uint64_t *__rest
             rb.init(row_start, row_end, n_rows, row_start ? round_row[wi / ROUND_WORDS] : 0, w << 5);
             uint32_t cuts = rb.cuts();
             if constexpr (MASKED) mask_lane_word(lw, rb, cuts, tabv, w, k);
-            uint32_t eq = 0, prev = 0;
+            uint32_t eq = 0, prev = 0, acc = 0;
             mini_minimizers<W, DELAY, M>(lw.x, woff, [&](int p, uint32_t mv) {
-                eq |= mv == prev ? 1u << p : 0u;
+                if (p > 0) eq_mask_push(eq, mv, prev);
                 prev = mv;
-                col[p * BLOCK + threadIdx.x] = (uint16_t)mini_bucket(mv, bits);
+                acc = region_bytes_push(acc, mv);
+                if ((p & 3) == 3) col[(p >> 2) * BLOCK + threadIdx.x] = acc;
             });
-            const uint32_t has = mini_record_ends(lw.ok, lw.ok_row, cuts, eq, cap);
+            const uint32_t has = mini_record_ends(lw.ok, lw.ok_row, cuts, eq_mask_finish(eq), cap);
             // (the column is the lane's own: no barrier between its writes and these reads)
-            for (uint32_t m = has; m; m &= m - 1u)
-                atomicAdd(&coarse[(uint32_t)col[(uint32_t)__builtin_ctz(m) * BLOCK + threadIdx.x] >> bits2], 1u);
+            for (uint32_t m = has; m; m &= m - 1u) {
+                const int e = __builtin_ctz(m);
+                atomicAdd(&coarse[region_of_bytes(col[(e >> 2) * BLOCK + threadIdx.x], e, bits1)], 1u);
+            }
             // records of more than SHORT_MAX k-mers: ends with SHORT_MAX positions in front of them that neither end a record nor
             // fail to end a k-mer
             const uint32_t nonk = has | ~lw.ok;
@@ -479,11 +444,11 @@ __global__ __launch_bounds__(S1_BLOCK, 4) void mini_scatter_kernel(const uint64_
             if constexpr (MASKED) ok_tab = mask_lane_word(lw, rb, cuts, tabv, w, k);
             uint32_t eq = 0, prev = 0;
             mini_minimizers<W, DELAY, M>(lw.x, woff, [&](int p, uint32_t mv) {
-                eq |= mv == prev ? 1u << p : 0u;
+                if (p > 0) eq_mask_push(eq, mv, prev);
                 prev = mv;
                 mycol[p * S1_BLOCK] = (uint16_t)mini_bucket(mv, bits);
             });
-            has = mini_record_ends(lw.ok, lw.ok_row, cuts, eq, cap);
+            has = mini_record_ends(lw.ok, lw.ok_row, cuts, eq_mask_finish(eq), cap);
             for (uint32_t m = has; m; m &= m - 1u)
                 __hip_atomic_fetch_add(&L.cnt[(uint32_t)mycol[(uint32_t)__builtin_ctz(m) * S1_BLOCK] >> bits2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -2828,7 +2793,9 @@ static int mini_plan_impl(const uint64_t *codes, const uint32_t *valid, const ui
         if (with_rows)
             hipLaunchKernelGGL(round_rows_kernel, dim3((unsigned)((p.n_rounds + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, rows->row_end, rows->n_rows,
                                word_begin, p.n_rounds, p.round_row);
-        const int grid = (int)(p.n_chunks < 4096 ? p.n_chunks : 4096);
+        // one workgroup per chunk (the kernel's chunk loop only matters beyond 2^20 chunks): with 4096 workgroups of five or six
+        // chunks each, eight to a CU, the second half of them started together and ended one chunk apart -- 2.51 against 2.26 ms
+        const int grid = (int)(p.n_chunks < (1 << 20) ? p.n_chunks : (1 << 20));
         rc = with_flag(tabv != nullptr, [&](auto masked) {
             return with_window(t->k, [&](auto w, int woff) {
                 using Win = decltype(w);

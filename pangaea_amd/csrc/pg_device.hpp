@@ -10,6 +10,7 @@
 
 #include "pangaea_feat.h"
 #include "pg_internal.h"
+#include "mini_forms.hpp"
 
 namespace {
 
@@ -200,37 +201,8 @@ __global__ __launch_bounds__(BIG_BLOCK) void scan_kernel(const unsigned long lon
 // k-mers of a read mostly share their minimizer, so the occurrences that go to one bucket travel as SUPER-k-mers: one
 // 12-byte record (32 bases + row + length) for a run of up to 16 k-mers instead of 8 bytes per occurrence.  Inside the
 // bucket the home slot is slot_hash(code); slots hold (canonical code << 22) | count, 0 = empty.
-// M depends on k alone: 13 from k = 16 on, 11 for 13 <= k <= 15 (Pangaea's default k = 15 then has windows of five 11-mers;
-// with 13-mers it would have three and hardly any k-mer would share its minimizer with a neighbour)
-constexpr int MINI_M = PG_MINI_M, MINI_M_SMALL = PG_MINI_M_SMALL;
-__host__ __device__ __forceinline__ int mini_m(int k) { return k >= MINI_M + 3 ? MINI_M : MINI_M_SMALL; }
-static_assert(PG_MINI_MIN_K == MINI_M_SMALL + 2, "windows of at least three M-mers");
-
-// The order in which M-mers compete for "minimizer": a multiplicative hash of the low 24 bits of the canonical M-mer (its
-// oldest character does not take part: M-mers that differ only there tie, and a tie is harmless -- the bucket is a function of
-// the minimum VALUE, which both strands compute from the same multiset).  The xor keeps poly-A (code 0) from being the
-// smallest value of all.  Two full-rate instructions (v_xor, v_mul_u32_u24): this runs once per character of the stream in
-// kernels that are bound by VALU issue; the three-xorshift mixer it replaces took seven.
-__device__ __forceinline__ uint32_t mhash(uint32_t x)
-{
-    return __umul24(x ^ 0x5E3779u, 0xC2B2AFu);
-}
-// bucket of a minimizer value.  The value is a minimum -- its HIGH bits are biased towards 0 --, but its low 24 bits are a
-// bijection of the minimizer M-mer's own low 24 bits (mhash: a product with an odd constant), as uniform as the M-mers are: one
-// more 24-bit product mixes them upwards and the top bits of its low dword are the bucket.  (v_mul_u32_u24 takes the low 24 bits of
-// its operands by itself and issues at full rate; the 32-bit product this replaces, v_mul_lo_u32, at a quarter of it -- and since
-// round 4 the bucket of EVERY position of the stream is computed, not one per record.)
-__device__ __forceinline__ uint32_t mini_bucket(uint32_t minv, int bits)
-{
-    return bits ? (uint32_t)__umul24(minv, 0x9E3779u) >> (32 - bits) : 0u;       // (HIP declares __umul24 as returning int)
-}
-__device__ __forceinline__ uint32_t swap_pairs32(uint32_t x) { return ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1); }
-// order of the 32 two-bit characters of a word reversed
-__device__ __forceinline__ uint64_t rev2_64(uint64_t x)
-{
-    const uint32_t lo = swap_pairs32(__brev((uint32_t)x)), hi = swap_pairs32(__brev((uint32_t)(x >> 32)));
-    return ((uint64_t)lo << 32) | hi;
-}
+// (mini_forms.hpp, which host code compiles too: mini_m, mhash -- the order in which M-mers compete --, mini_bucket, rev2_64,
+// mini_window, and the per-position forms of the plan kernel and the first scatter pass)
 // (24-bit multiplies -- v_mul_u32_u24 issues at full rate, a 32-bit v_mul_lo_u32 at a quarter of it, and this runs once per
 // k-mer occurrence in kernels that are bound by VALU issue; the fold brings the well-mixed high product bits, which depend
 // on all bits of the code, down to the slot index).  WIDE: codes of k > 21 (up to 62 bits) add a third term, which is 0 for
@@ -242,17 +214,6 @@ template <bool WIDE = false> __device__ __forceinline__ uint32_t mini_slot_hash(
     if (WIDE) x ^= __umul24((uint32_t)(code >> 45), 0x85EBCBu);
     x ^= x >> 15;
     return x;
-}
-// The M-mers of a k-mer that compete for its minimizer: all k - M + 1 of them up to 9, beyond that (k > 21) the CENTRAL 8 or 9
-// (same parity as k - M + 1, so that `off` M-mers are left out on either side).  The reverse complement maps M-mer t to
-// k - M - t, i.e. the central window onto itself: both strands pick the same M-mer, as they must.  A window of at most 9
-// keeps the rolling minimum of the first scatter pass in 9 registers for every k.
-constexpr int MINI_MAX_WINDOW = 9;
-__host__ __device__ __forceinline__ void mini_window(int k, int *wc, int *off)
-{
-    const int w = k - mini_m(k) + 1;
-    *wc = w <= MINI_MAX_WINDOW ? w : MINI_MAX_WINDOW - 1 + (w & 1);
-    *off = (w - *wc) / 2;
 }
 // minimizer value of one k-mer given as a (forward or canonical) code, newest character in the low bits
 __device__ __forceinline__ uint32_t mini_minimizer_of(uint64_t code, int k)
