@@ -633,6 +633,62 @@ int pg_table_read_depths(const pg_table *t, int k, const uint8_t *text, int64_t 
                          void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Read pairs of a FASTQ text by their barcode tag (device; one GPU; no table).  Every entry point of this library takes a
+ * barcode-sorted interleaved FASTQ; the reference makes one in step 0 of its driver, src/run_pangaea:237-252: an awk pass glues
+ * each 8-line block to the BX:Z: tag of its first header, then `LANG=C sort -k1,1 | cut | tr`.  These entries are what that step
+ * needs to know about the barcode ON THE TEXT in device memory; the line index is pg_fastq_index's and the records are moved
+ * by pg_fastq_gather (pangaea_amd/sortreads.py: sort_fastq, check_fastq).  All entries are additive to ABI 9; every argument is
+ * checked before the first HIP call (PG_EINVAL with a pg_last_error text: a null pointer by name, negative sizes, a
+ * lines_per_unit that is neither 4 nor 8, a byte_begin that is negative or no multiple of 8, a text base that is not 16-byte
+ * aligned).  Whatever the device arrays hold, nothing outside [0, n_bytes) of the text is read and nothing outside the output
+ * arrays written; text and arrays go through plain loads and stores.
+ *   UNIT     a read pair: lines_per_unit = 8 lines of an interleaved four-line FASTQ, or lines_per_unit = 4: one record of an
+ *            R1 file (its mate is the same record of R2, which these entries never see).  The header of unit u is line
+ *            lines_per_unit * u of a line index of lines_per_unit * n_units + 1 entries.
+ *   TAG      taken from that header only -- a tag on the mate's header is ignored: the LEFTMOST match of "BX:Z:" followed by one
+ *            or more bytes that are no C-locale white space (space, \t, \n, \v, \f, \r), at its longest.  "BX:Z:" right in
+ *            front of white space or of the line's end is no match there; a later occurrence in the line can still match.
+ *            '\r' ends a tag (CRLF files).  A unit without a match is UNTAGGED.  NUL bytes in a header are outside the contract.
+ *   ORDER    tagged units first, by the bytes of their tags as unsigned bytes, of two tags of which one is a prefix of the
+ *            other the shorter first (memcmp, then length: `LANG=C sort -k1,1` on a key without blanks); untagged units behind
+ *            all tagged ones (the reference gives them the key "~~~"; every tag begins with 'B') and equal to each other.
+ *            WITHIN one tag the reference's order is GNU sort's last-resort comparison of the whole line (read name, then
+ *            sequence); callers of these entries keep the INPUT order instead (a stable sort): nothing downstream reads that
+ *            order, and a stable order is reproducible and cheaper.
+ *   pg_fastq_barcode_tags  beside src/run_pangaea:237-252 (awk's match(): which bytes are the tag): tag_off[u] = byte offset of
+ *                          the 'B' of the match or -1, tag_len[u] = length of the whole match ("BX:Z:" included) or 0, u <
+ *                          n_units.  status (device uint64_t[2], written whole by the call) as pg_table_read_hits writes it:
+ *                          [0] = PG_STATUS_FASTQ_FORMAT or 0, [1] = PG_FASTQ_CLEAN or (record << 8) | reason of the malformed
+ *                          record with the smallest ordinal, record = u * (lines_per_unit / 4) + (0: R1's, 1: R2's) --
+ *                          PG_FASTQ_NO_AT, PG_FASTQ_NO_PLUS and PG_FASTQ_BAD_INDEX for every record of the unit,
+ *                          PG_FASTQ_LONG_TAG for a tag of more than PG_FASTQ_MAX_TAG bytes behind "BX:Z:" (reported on the
+ *                          unit's first record).  A malformed unit leaves as untagged (-1, 0).  One wavefront per header, 64
+ *                          bytes per turn, any header length.  n_units == 0: PG_OK, nothing launched, nothing written.
+ *   pg_fastq_tag_keys      beside src/run_pangaea:237-252 (the key bytes `sort -k1,1` compares): keys[i] = bytes [byte_begin,
+ *                          byte_begin + 8) of the tag of unit order[i] (order NULL: unit i) counted BEHIND the 5-byte prefix,
+ *                          big-endian -- the first byte highest -- and zero behind the tag's end, i < n; 0 for an untagged unit
+ *                          and for an order[i] outside [0, n).  tag_off, tag_len: n entries, as the entry above wrote them
+ *                          (anything else reads as untagged).  Compared as UNSIGNED words, chunk after chunk, the keys give
+ *                          the order of the tagged units; untagged units must be told by tag_len, not by a key (eight 0xFF
+ *                          bytes are a legal tag).  n == 0: PG_OK, nothing launched.
+ *   pg_fastq_tag_compare   beside src/run_pangaea:237-252 (sort's comparison itself): out[0] = 0, out[i] = -1, 0 or +1 as
+ *                          tag(order[i - 1]) stands before, equal to or behind tag(order[i]) in ORDER, i < n (order NULL:
+ *                          identity).  Never goes through a key: the independent statement of the order.  On the identity any +1
+ *                          is a descent (the file is not sorted); on a sorted order the number of -1 plus one is the number of
+ *                          runs.  n == 0: PG_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_FASTQ_LONG_TAG 5u   /* beside PG_FASTQ_NO_AT .. PG_FASTQ_BAD_INDEX: a tag longer than PG_FASTQ_MAX_TAG */
+#define PG_FASTQ_MAX_TAG 255   /* bytes of a tag behind "BX:Z:" */
+int pg_fastq_barcode_tags(const uint8_t *text, int64_t n_bytes, const int64_t *line_start, int64_t n_units, int lines_per_unit /* 4 or 8 */,
+                          int64_t *tag_off /* device, [n_units] */, int32_t *tag_len /* device, [n_units] */,
+                          uint64_t *status /* device [2] */, void *stream);
+int pg_fastq_tag_keys(const uint8_t *text, int64_t n_bytes, const int64_t *tag_off, const int32_t *tag_len,
+                      const int64_t *order /* device, [n], or NULL */, int64_t n, int64_t byte_begin, uint64_t *keys /* device, [n] */,
+                      void *stream);
+int pg_fastq_tag_compare(const uint8_t *text, int64_t n_bytes, const int64_t *tag_off, const int32_t *tag_len,
+                         const int64_t *order /* device, [n], or NULL */, int64_t n, int8_t *out /* device, [n] */, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
  * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
  * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for

@@ -18,6 +18,8 @@
                        -o OUT [-o2 OUT2]                                                   (one JSON line on stdout)
     kmer_table normalize {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} --target T [--min-depth M] [-L LOWER] [--percentile P]
                          [--pair any|both|single] [--seed S] [--min-qual-char C] -o OUT [-o2 OUT2]  (one JSON line on stdout)
+    sort_barcodes {-i F | -1 F -2 F} -o OUT                                        (src/run_pangaea:237-252; one JSON line on stdout)
+    sort_barcodes --check {-i F | -1 F -2 F}                                       (exit status 0: sorted, 1: not; see ``main_sort_barcodes``)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -384,6 +386,55 @@ def _kmer_table_parser() -> _Parser:
         q.add_argument("-o", "--output", required=True)
         q.add_argument("-o2", "--output2", default="")
     return p
+
+
+def _sort_plan(a) -> tuple:
+    """the checked arguments of ``sort_barcodes``: (src1, src2 or None, out or None).  Nothing is opened but the question whether
+    the inputs exist."""
+    if bool(a.reads1) != bool(a.reads2):
+        raise ValueError("-1 and -2 go together")
+    if bool(a.interleaved) == bool(a.reads1):
+        raise ValueError("the reads to sort are -i F or -1 F -2 F (one of the two)")
+    if a.check and a.output:
+        raise ValueError("--check writes nothing: -o does not go with it")
+    if not a.check and not a.output:
+        raise ValueError("-o OUT is needed (or --check)")
+    if a.output and a.output.endswith(".gz"):
+        raise ValueError(f"{a.output}: the sorted reads are written as plain text, gzip output is not supported")
+    srcs = (a.interleaved, None) if a.interleaved else (a.reads1, a.reads2)
+    for f in srcs:
+        if f and not os.path.isfile(f):
+            raise ValueError(f"{f}: no such file")
+    return srcs[0], srcs[1], a.output or None
+
+
+def main_sort_barcodes(argv=None) -> int:
+    """``sort_barcodes {-i F | -1 F -2 F} -o OUT``: the read pairs of the input, plain or gzip, as one interleaved plain FASTQ
+    sorted by barcode (``sortreads.sort_fastq``: what step 0 of the reference's driver does, src/run_pangaea:237-252, with input
+    order and not read-name order within a barcode); one JSON line on stdout: pairs, barcodes, untagged_pairs, longest_tag,
+    passes, already_sorted, bytes, seconds, device_ms per stage.  ``sort_barcodes --check {-i F | -1 F -2 F}``: one JSON line of
+    ``sortreads.check_fastq`` -- sorted, first_descent, pairs, barcodes, untagged_pairs -- and exit status 0 when the input is
+    sorted, 1 when it is not.  Any failure: a message on stderr and exit status 1 (2 under ``--check``, where 1 has a meaning)."""
+    p = _Parser(prog="sort_barcodes")
+    p.add_argument("-1", "--reads1", default="")
+    p.add_argument("-2", "--reads2", default="")
+    p.add_argument("-i", "--interleaved", default="")
+    p.add_argument("-o", "--output", default="")
+    p.add_argument("--check", action="store_true")
+    a = p.parse_args(argv)
+    import json
+    try:
+        src1, src2, out = _sort_plan(a)
+        from . import sortreads
+        if a.check:
+            res = sortreads.check_fastq(src1, src2)
+            sys.stdout.write(json.dumps(res) + "\n")
+            return 0 if res["sorted"] else 1
+        sys.stdout.write(json.dumps(sortreads.sort_fastq(src1, out, src2)) + "\n")
+    except Exception as e:
+        sys.stderr.write(f"sort_barcodes: {e}\n")
+        return 2 if a.check else 1
+    return 0
 
 
 def main_kmer_table(argv=None) -> int:

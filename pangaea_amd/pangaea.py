@@ -8,6 +8,8 @@ it is delegated to the reference's own ``final_assemble`` when a Pangaea checkou
 (or PANGAEA_SRC), and skipped with a log line otherwise.
 
     python -m pangaea_amd.pangaea -i interleaved.sorted.fastq -o out -c 30 -st 1,2,3
+``--sort_reads`` (additive): the input -- ``-i`` or ``-1``/``-2``, in any order -- is sorted by barcode on the GPU first, what step 0
+of the reference's driver does (src/run_pangaea:237-252); see pangaea_amd/sortreads.py.
 Multi-GPU: ``torchrun --nproc-per-node N -m pangaea_amd.pangaea ...`` shards step 1 (see pangaea_amd/dist.py).
 """
 from __future__ import annotations
@@ -75,7 +77,27 @@ def build_parser() -> argparse.ArgumentParser:
                         "scripts/calculate_diversity.sh and a metaphlan db) or silhouette (a sweep over k scored by silhouette on the GPU, "
                         "from this package alone; in a multi-rank run rank 0 sweeps alone after the ranks have left the group)")
     p.add_argument("--cluster_range", type=str, default="4,100,3", help="LO,HI,STEP of the silhouette sweep over k (default 4,100,3)")
+    p.add_argument("--sort_reads", action="store_true",
+                   help="sort the read pairs of -i or -1/-2 by barcode on the GPU first (what run_pangaea's step 0 does with awk and sort): "
+                        "<output>/0.reads/interleaved.sorted.fastq is written unless it exists and taken as -i by every step")
     return p
+
+
+def sort_reads_first(args) -> None:
+    """``--sort_reads``: <output>/0.reads/interleaved.sorted.fastq from -i or -1/-2 (rank 0 writes it, unless it is there), and that
+    file as ``interleaved_reads`` for every step; the other ranks wait on the control plane"""
+    from . import dist as pdist
+    path = os.path.join(args.output, "0.reads", "interleaved.sorted.fastq")
+    if not pdist.is_distributed() or torch.distributed.get_rank() == 0:
+        if os.path.exists(path):
+            logging.info("step 0: " + path + " exists, not sorting again")
+        else:
+            from .sortreads import sort_fastq
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            res = sort_fastq(args.interleaved_reads or args.reads1, path, None if args.interleaved_reads else args.reads2)
+            logging.info(f"step 0: reads sorted by barcode: {res}")
+    pdist.wait_for_all()
+    args.interleaved_reads, args.reads1, args.reads2 = path, "", ""
 
 
 def _encode_sharded(args, feat, vae, model_path):
@@ -156,6 +178,10 @@ def _run(args, script_path):
     feat = None
 
     agreed = pdist.agreed               # rank 0's reading of the output directory decides for everybody (control plane)
+
+    # step 0 (--sort_reads only): the input sorted by barcode, which every step below takes for granted
+    if args.sort_reads and have_reads:
+        sort_reads_first(args)
 
     # step 1: feature extraction (every rank takes part: its own runs, one table exchange; rank 0 writes the caches)
     if not check_steps_required(args.steps, "1"):
