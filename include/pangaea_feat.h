@@ -689,6 +689,74 @@ int pg_fastq_tag_compare(const uint8_t *text, int64_t n_bytes, const int64_t *ta
                          const int64_t *order /* device, [n], or NULL */, int64_t n, int8_t *out /* device, [n] */, void *stream);
 
 /* ----------------------------------------------------------------------------------------------
+ * Raw stLFR and TELL-seq read pairs brought to the BX:Z: form (device; one GPU; no table).  The section above sorts reads whose
+ * barcode stands in a BX:Z: tag; the reference's driver makes that form first -- the other half of its step 0 -- with
+ * `preprocess_stlfr -n -l` (src/run_pangaea:138-149 -> preprocess_stlfr.cpp:68-113) and `preprocess_tellseq -l INDEX`
+ * (src/run_pangaea:151-162 -> preprocess_tellseq.cpp:52-84), then `seqtk mergepe` (src/run_pangaea:224).  These entries do the
+ * same rewriting ON THE TEXTS in device memory (pangaea_amd/prepreads.py: preprocess_reads; sortreads.py with short_type).
+ * Both are additive to ABI 9; every argument is checked before the first HIP call (PG_EINVAL with a pg_last_error text: a
+ * mode that is none, a null pointer by name, negative sizes, a text base that is not 16-byte aligned, an index text without
+ * PG_PREP_TELLSEQ, n_kept outside [0, n_units]).  Whatever the device arrays hold, nothing outside [0, n_bytes) of a text is read
+ * and nothing outside [0, out_bytes) of an output written; plain loads and stores.  These are BYTE rules: a line's content is
+ * the line without its '\n', a '\r' is an ordinary byte of the content.  The reference checks nothing (it writes garbage or
+ * aborts on malformed input): parity is claimed on well-formed input only.
+ *   UNIT      record u of R1 (text1) with record u of R2 (text2) and, for TELL-seq, of I1 (text_i), each four lines of a line
+ *             index of 4 * n_units + 1 entries.  h = the content of R1's header.
+ *   STLFR     (PG_PREP_STLFR; preprocess_stlfr.cpp:68-113 with -n -l)  p = the first '#' in h (none: PG_FASTQ_NO_HASH); q = the
+ *             first '/' behind p, or the end of h; B = h[p + 1 : q].  B is split at its first two '_' into f1, f2 and the rest
+ *             f3, which may hold more '_' (fewer than two '_': PG_FASTQ_FEW_FIELDS -- the reference aborts on .at()); B of more
+ *             than PG_FASTQ_MAX_TAG - 2 bytes: PG_FASTQ_LONG_TAG, so that the tag with its "-1" still fits the sort's limit.
+ *             The unit is TAGGED iff f1 != "0" and f2 != "0", compared as byte strings.  The reference tests f1 twice and never
+ *             f3 (preprocess_stlfr.cpp:89): 5_6_0 is tagged, 5_0_7, 0_6_7 and 0_0_0 are not -- kept exactly so.  The new header
+ *             of BOTH mates is h[:p], then "\tBX:Z:" + B + "-1" if tagged, then '\n': R2's own header is discarded (only its '@'
+ *             is checked).  Lines 1, 2 and 3 of each mate are copied byte for byte.  No unit is dropped.
+ *   TELLSEQ   (PG_PREP_TELLSEQ; preprocess_tellseq.cpp:52-84)  B = the content of the SEQUENCE line of I1's record u.  The unit
+ *             is KEPT iff B has exactly 18 bytes (a B with a trailing '\r' has 19 and is dropped, as the reference drops it; no
+ *             error).  s = the first space (0x20) in h, or the end of h -- a tab does not cut.  The new header of both mates is
+ *             h[:s] + "\tBX:Z:" + B + "-1" + '\n'; line 1 is copied byte for byte, line 2 becomes exactly "+\n" whatever it
+ *             held, line 3 is copied byte for byte.  The white list (PREFIX.wl) is B + '\n' per kept unit, in input order.
+ *   BOTH      a last line without '\n' gets one.  Malformed: a header without '@' (PG_FASTQ_NO_AT) or a third line without '+'
+ *             (PG_FASTQ_NO_PLUS) in ANY of the two or three files, PG_FASTQ_BAD_INDEX, and the three stLFR reasons above.  A
+ *             file that ends inside a record and files of different record counts are the caller's to refuse (they show in
+ *             the line counts).
+ *   pg_fastq_prep_plan   beside preprocess_stlfr.cpp:76-91 / preprocess_tellseq.cpp:62-72 (where the barcode lies and whether
+ *                        the unit is tagged / kept): head_len[u] = p resp. s counted from the header's first byte; bc_off[u] =
+ *                        byte offset of B in text1 (stLFR) resp. text_i (TELL-seq), bc_len[u] = its bytes; tagged[u] = 1 for a
+ *                        tagged (stLFR) resp. kept (TELL-seq) unit, else 0.  A malformed unit leaves 0, -1, 0, 0.  status
+ *                        (device uint64_t[3][2], written whole by the call): row f for file f (0 R1, 1 R2, 2 I1) as
+ *                        pg_table_read_hits writes its two words -- [0] = PG_STATUS_FASTQ_FORMAT or 0, [1] = PG_FASTQ_CLEAN or
+ *                        ((first_unit + u) << 8) | reason of the malformed record with the SMALLEST ordinal in that file; the
+ *                        stLFR reasons stand in row 0.  One wavefront per unit, 64 header bytes per turn, any header length.
+ *                        n_units == 0: PG_OK, nothing launched, nothing written.
+ *   pg_fastq_prep_write  beside preprocess_stlfr.cpp:92-108 / preprocess_tellseq.cpp:63-79 (the writing): for i < n_kept and
+ *                        u = kept[i] (kept NULL: u = i) the new record of R1 goes to out1 + dst1[i] and that of R2 to out2 +
+ *                        dst2[i].  Its bytes: head_len[u] + (tagged[u] ? 8 + bc_len[u] : 0) + 1, then stLFR: the bytes of lines
+ *                        1 .. 3, TELL-seq: those of line 1, 2, those of line 3; + 1 when the record lacks its final '\n'.  dst1 /
+ *                        dst2 are the caller's exclusive scans of these.  out1 and out2 may be ONE buffer: with dst2[i] =
+ *                        dst1[i] + (bytes of R1's new record) that is the interleaved form `seqtk mergepe` makes.  The plan
+ *                        arrays are checked again: a unit is skipped when u is out of range, an index is not monotone inside
+ *                        its text, head_len exceeds the header, B does not lie inside its text or is longer than
+ *                        PG_FASTQ_MAX_TAG - 2, a TELL-seq unit is not tagged, or a record does not fit [dst, out_bytes).  One
+ *                        wavefront per kept unit.  white_list (TELL-seq only, or NULL): B + '\n' of kept unit i at 19 i,
+ *                        inside [0, white_list_bytes).  n_kept == 0: PG_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------------- */
+#define PG_FASTQ_NO_HASH 6u     /* beside PG_FASTQ_NO_AT .. PG_FASTQ_LONG_TAG: a stLFR header without '#' */
+#define PG_FASTQ_FEW_FIELDS 7u  /* a stLFR barcode with fewer than two '_' */
+#define PG_PREP_STLFR 1
+#define PG_PREP_TELLSEQ 2
+int pg_fastq_prep_plan(int mode, const uint8_t *text1, int64_t n1_bytes, const int64_t *line_start1, const uint8_t *text2, int64_t n2_bytes,
+                       const int64_t *line_start2, const uint8_t *text_i /* PG_PREP_TELLSEQ, else NULL */, int64_t n_i_bytes,
+                       const int64_t *line_start_i, int64_t n_units, int64_t first_unit, int64_t *head_len /* device, [n_units] */,
+                       int64_t *bc_off /* device, [n_units] */, int32_t *bc_len /* device, [n_units] */,
+                       uint8_t *tagged /* device, [n_units] */, uint64_t *status /* device [3][2] */, void *stream);
+int pg_fastq_prep_write(int mode, const uint8_t *text1, int64_t n1_bytes, const int64_t *line_start1, const uint8_t *text2, int64_t n2_bytes,
+                        const int64_t *line_start2, const uint8_t *text_i /* PG_PREP_TELLSEQ, else NULL */, int64_t n_i_bytes,
+                        int64_t n_units, const int64_t *head_len, const int64_t *bc_off, const int32_t *bc_len, const uint8_t *tagged,
+                        const int64_t *kept /* device, [n_kept], or NULL */, const int64_t *dst1, const int64_t *dst2, int64_t n_kept,
+                        uint8_t *out1, int64_t out1_bytes, uint8_t *out2, int64_t out2_bytes,
+                        uint8_t *white_list /* PG_PREP_TELLSEQ, or NULL */, int64_t white_list_bytes, void *stream);
+
+/* ----------------------------------------------------------------------------------------------
  * The table as jellyfish's text dump, and back (device; one GPU, any of the five kinds).  The reference keeps
  * abundance.k{k}.dump on disk (src/feature.py:87,103: `jellyfish dump -c -t`), count_kmer -g reads it (count_kmer.cpp:139-170).
  * One line per entry, "<k-mer>\t<count>\n": the first character from the highest two bits of the canonical code, A C T G for

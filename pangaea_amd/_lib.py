@@ -27,6 +27,9 @@ FASTQ_CLEAN = (1 << 64) - 1       # PG_FASTQ_CLEAN: status[1] of pg_table_read_h
 FASTQ_NO_AT, FASTQ_NO_PLUS, FASTQ_SHORT_QUALITY, FASTQ_BAD_INDEX = 1, 2, 3, 4
 FASTQ_LONG_TAG = 5                # PG_FASTQ_LONG_TAG: pg_fastq_barcode_tags met a tag of more than FASTQ_MAX_TAG bytes behind "BX:Z:"
 FASTQ_MAX_TAG = 255               # PG_FASTQ_MAX_TAG
+FASTQ_NO_HASH, FASTQ_FEW_FIELDS = 6, 7     # PG_FASTQ_NO_HASH, PG_FASTQ_FEW_FIELDS: pg_fastq_prep_plan met a stLFR header without '#' / with fewer than two '_'
+PREP_STLFR, PREP_TELLSEQ = 1, 2   # PG_PREP_*: the library whose raw reads pg_fastq_prep_plan / pg_fastq_prep_write rewrite
+PREP_MODES = {"stlfr": PREP_STLFR, "tellseq": PREP_TELLSEQ}
 SPAN_FIRST, SPAN_LONGEST = 0, 1   # PG_SPAN_*: which run of solid positions pg_table_read_spans reports
 SPAN_MODES = {"first": SPAN_FIRST, "longest": SPAN_LONGEST}
 _LIB = None
@@ -205,6 +208,8 @@ def load() -> C.CDLL:
         "pg_fastq_barcode_tags": (i32, [vp, i64, vp, i64, i32, vp, vp, vp, vp]),
         "pg_fastq_tag_keys": (i32, [vp, i64, vp, vp, vp, i64, i64, vp, vp]),
         "pg_fastq_tag_compare": (i32, [vp, i64, vp, vp, vp, i64, vp, vp]),
+        "pg_fastq_prep_plan": (i32, [i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp]),
+        "pg_fastq_prep_write": (i32, [i32, vp, i64, vp, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp]),
         "pg_table_dump_units": (i64, [tp]),
         "pg_table_dump_sizes": (i32, [tp, i64, vp, vp, vp]),
         "pg_table_dump_text": (i32, [tp, i64, i64, i64, vp, i64, i64, vp, i64, vp]),
@@ -254,6 +259,7 @@ EXPORTS = ["pg_abi_version", "pg_build_flags", "pg_last_error", "pg_device_count
            "pg_fastq_index_workspace_bytes", "pg_fastq_index", "pg_table_read_hits", "pg_fastq_gather",
            "pg_table_read_spans", "pg_fastq_gather_trimmed", "pg_table_correct_reads", "pg_table_read_depths",
            "pg_fastq_barcode_tags", "pg_fastq_tag_keys", "pg_fastq_tag_compare",
+           "pg_fastq_prep_plan", "pg_fastq_prep_write",
            "pg_table_dump_units", "pg_table_dump_sizes", "pg_table_dump_text", "pg_dump_parse_workspace_bytes", "pg_dump_parse",
            "pg_table_merge", "pg_table_merge_aligned", "pg_table_merge_aligned_applies",
            "pg_table_combine_aligned", "pg_table_combine_items", "pg_table_compare",

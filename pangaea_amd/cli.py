@@ -18,8 +18,10 @@
                        -o OUT [-o2 OUT2]                                                   (one JSON line on stdout)
     kmer_table normalize {-g DUMP | -ti F | -t1 F -t2 F} -k K {-i F | -1 F -2 F} --target T [--min-depth M] [-L LOWER] [--percentile P]
                          [--pair any|both|single] [--seed S] [--min-qual-char C] -o OUT [-o2 OUT2]  (one JSON line on stdout)
-    sort_barcodes {-i F | -1 F -2 F} -o OUT                                        (src/run_pangaea:237-252; one JSON line on stdout)
-    sort_barcodes --check {-i F | -1 F -2 F}                                       (exit status 0: sorted, 1: not; see ``main_sort_barcodes``)
+    sort_barcodes {-i F | -1 F -2 F} -o OUT [--short_type {10x,stlfr,tellseq}] [-I INDEX]
+                                                                                  (src/run_pangaea:237-252; one JSON line on stdout)
+    sort_barcodes --check {-i F | -1 F -2 F} [--short_type ...] [-I INDEX]        (exit status 0: sorted, 1: not; see ``main_sort_barcodes``)
+    preprocess_reads --short_type {stlfr,tellseq} -1 R1 -2 R2 [-I INDEX] -o PREFIX (src/run_pangaea:138-162; one JSON line on stdout)
                                                          (what `jellyfish histo` / `jellyfish query` / `jellyfish dump -c -t` give
                                                           from the table the reference keeps on disk, feature.py:87,103; see
                                                           ``main_kmer_table``)
@@ -388,9 +390,22 @@ def _kmer_table_parser() -> _Parser:
     return p
 
 
+def _short_type_checks(short_type: str, interleaved: str, index: str, allowed: tuple) -> None:
+    """what ``--short_type`` and ``-I`` admit beside each other and beside ``-i``, before any file is looked at (ValueError)"""
+    if short_type not in allowed:
+        raise ValueError(f"--short_type must be one of {', '.join(allowed)} (got {short_type!r})")
+    if short_type == "tellseq" and not index:
+        raise ValueError("tellseq reads need their index reads: -I INDEX")
+    if short_type != "tellseq" and index:
+        raise ValueError(f"-I INDEX goes with --short_type tellseq only, not with {short_type}")
+    if short_type != "10x" and interleaved:
+        raise ValueError(f"raw {short_type} reads are given as -1 R1 -2 R2, not as -i")
+
+
 def _sort_plan(a) -> tuple:
     """the checked arguments of ``sort_barcodes``: (src1, src2 or None, out or None).  Nothing is opened but the question whether
     the inputs exist."""
+    _short_type_checks(a.short_type, a.interleaved, a.index, ("10x", "stlfr", "tellseq"))
     if bool(a.reads1) != bool(a.reads2):
         raise ValueError("-1 and -2 go together")
     if bool(a.interleaved) == bool(a.reads1):
@@ -402,8 +417,11 @@ def _sort_plan(a) -> tuple:
     if a.output and a.output.endswith(".gz"):
         raise ValueError(f"{a.output}: the sorted reads are written as plain text, gzip output is not supported")
     srcs = (a.interleaved, None) if a.interleaved else (a.reads1, a.reads2)
-    for f in srcs:
-        if f and not os.path.isfile(f):
+    given = [f for f in srcs + (a.index,) if f]
+    if a.output and os.path.realpath(a.output) in {os.path.realpath(f) for f in given}:
+        raise ValueError(f"the output must differ from the inputs (got {a.output})")
+    for f in given:
+        if not os.path.isfile(f):
             raise ValueError(f"{f}: no such file")
     return srcs[0], srcs[1], a.output or None
 
@@ -414,26 +432,75 @@ def main_sort_barcodes(argv=None) -> int:
     order and not read-name order within a barcode); one JSON line on stdout: pairs, barcodes, untagged_pairs, longest_tag,
     passes, already_sorted, bytes, seconds, device_ms per stage.  ``sort_barcodes --check {-i F | -1 F -2 F}``: one JSON line of
     ``sortreads.check_fastq`` -- sorted, first_descent, pairs, barcodes, untagged_pairs -- and exit status 0 when the input is
-    sorted, 1 when it is not.  Any failure: a message on stderr and exit status 1 (2 under ``--check``, where 1 has a meaning)."""
+    sorted, 1 when it is not.  Any failure: a message on stderr and exit status 1 (2 under ``--check``, where 1 has a meaning).
+    ``--short_type stlfr`` / ``--short_type tellseq -I INDEX`` (``-1``/``-2`` only): the input is RAW reads of that library, rewritten
+    to the ``BX:Z:`` form on the device first (``prepreads``; the JSON line then holds the preprocess counts too); ``10x``, the
+    default: barcodes that stand in a ``BX:Z:`` tag already."""
     p = _Parser(prog="sort_barcodes")
     p.add_argument("-1", "--reads1", default="")
     p.add_argument("-2", "--reads2", default="")
     p.add_argument("-i", "--interleaved", default="")
     p.add_argument("-o", "--output", default="")
     p.add_argument("--check", action="store_true")
+    p.add_argument("--short_type", default="10x")
+    p.add_argument("-I", "--index", default="")
     a = p.parse_args(argv)
     import json
     try:
         src1, src2, out = _sort_plan(a)
         from . import sortreads
+        raw = {"short_type": a.short_type, "index": a.index or None} if a.short_type != "10x" else {}
         if a.check:
-            res = sortreads.check_fastq(src1, src2)
+            res = sortreads.check_fastq(src1, src2, **raw)
             sys.stdout.write(json.dumps(res) + "\n")
             return 0 if res["sorted"] else 1
-        sys.stdout.write(json.dumps(sortreads.sort_fastq(src1, out, src2)) + "\n")
+        sys.stdout.write(json.dumps(sortreads.sort_fastq(src1, out, src2, **raw)) + "\n")
     except Exception as e:
         sys.stderr.write(f"sort_barcodes: {e}\n")
         return 2 if a.check else 1
+    return 0
+
+
+def _prep_plan(a) -> tuple:
+    """the checked arguments of ``preprocess_reads``: (R1, R2, index or None, the outputs).  Nothing is opened but the question
+    whether the inputs exist."""
+    _short_type_checks(a.short_type, "", a.index, ("stlfr", "tellseq"))
+    if not a.reads1 or not a.reads2:
+        raise ValueError("the raw reads are -1 R1 -2 R2 (both)")
+    if a.output.endswith(".gz"):
+        raise ValueError(f"{a.output}: the reads are written as plain text (PREFIX_1.fq, PREFIX_2.fq), gzip output is not supported")
+    outs = [a.output + "_1.fq", a.output + "_2.fq"] + ([a.output + ".wl"] if a.short_type == "tellseq" else [])
+    given = [f for f in (a.reads1, a.reads2, a.index) if f]
+    hit = {os.path.realpath(o) for o in outs} & {os.path.realpath(f) for f in given}
+    if hit:
+        raise ValueError(f"the outputs must differ from the inputs (got {sorted(hit)[0]})")
+    for f in given:
+        if not os.path.isfile(f):
+            raise ValueError(f"{f}: no such file")
+    return a.reads1, a.reads2, a.index or None, outs
+
+
+def main_preprocess_reads(argv=None) -> int:
+    """``preprocess_reads --short_type {stlfr,tellseq} -1 R1 -2 R2 [-I INDEX] -o PREFIX``: raw stLFR or TELL-seq reads, plain or
+    gzip, as ``PREFIX_1.fq`` / ``PREFIX_2.fq`` with the barcode in a ``BX:Z:`` tag on both mates' headers, and ``PREFIX.wl`` for
+    TELL-seq (``prepreads.preprocess_reads``: what the reference's driver does with ``preprocess_stlfr -n -l`` and
+    ``preprocess_tellseq``, src/run_pangaea:138-162); one JSON line on stdout: short_type, pairs, tagged_pairs / untagged_pairs or
+    kept_pairs / dropped_pairs, bytes, files, seconds, device_ms per stage.  Any failure: a message on stderr and exit status 1."""
+    p = _Parser(prog="preprocess_reads")
+    p.add_argument("--short_type", required=True)
+    p.add_argument("-1", "--reads1", default="")
+    p.add_argument("-2", "--reads2", default="")
+    p.add_argument("-I", "--index", default="")
+    p.add_argument("-o", "--output", required=True)
+    a = p.parse_args(argv)
+    import json
+    try:
+        r1, r2, index, _ = _prep_plan(a)
+        from . import prepreads
+        sys.stdout.write(json.dumps(prepreads.preprocess_reads(a.short_type, r1, r2, a.output, index)) + "\n")
+    except Exception as e:
+        sys.stderr.write(f"preprocess_reads: {e}\n")
+        return 1
     return 0
 
 

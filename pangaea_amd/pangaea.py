@@ -9,7 +9,9 @@ it is delegated to the reference's own ``final_assemble`` when a Pangaea checkou
 
     python -m pangaea_amd.pangaea -i interleaved.sorted.fastq -o out -c 30 -st 1,2,3
 ``--sort_reads`` (additive): the input -- ``-i`` or ``-1``/``-2``, in any order -- is sorted by barcode on the GPU first, what step 0
-of the reference's driver does (src/run_pangaea:237-252); see pangaea_amd/sortreads.py.
+of the reference's driver does (src/run_pangaea:237-252); see pangaea_amd/sortreads.py.  With ``--short_type stlfr`` or ``--short_type
+tellseq --index I1`` the ``-1``/``-2`` reads are RAW reads of that library and are brought to the ``BX:Z:`` form in the same call (the
+driver's ``-s`` / ``-I``, src/run_pangaea:138-162; see pangaea_amd/prepreads.py).
 Multi-GPU: ``torchrun --nproc-per-node N -m pangaea_amd.pangaea ...`` shards step 1 (see pangaea_amd/dist.py).
 """
 from __future__ import annotations
@@ -80,7 +82,21 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sort_reads", action="store_true",
                    help="sort the read pairs of -i or -1/-2 by barcode on the GPU first (what run_pangaea's step 0 does with awk and sort): "
                         "<output>/0.reads/interleaved.sorted.fastq is written unless it exists and taken as -i by every step")
+    p.add_argument("--short_type", default="10x",
+                   help="with --sort_reads: the library of -1/-2 -- 10x (default: barcodes in a BX:Z: tag already), stlfr or tellseq (raw reads: "
+                        "the barcode is brought into the tag on the GPU first, what run_pangaea -s does with preprocess_stlfr / preprocess_tellseq)")
+    p.add_argument("--index", default="", help="with --short_type tellseq: the index reads (run_pangaea -I)")
     return p
+
+
+def check_short_type(args) -> None:
+    """``--short_type`` / ``--index`` beside the other arguments, before any file is opened (ValueError)"""
+    from .cli import _short_type_checks
+    _short_type_checks(args.short_type, args.interleaved_reads, args.index, ("10x", "stlfr", "tellseq"))
+    if args.short_type != "10x" and not args.sort_reads:
+        raise ValueError(f"--short_type {args.short_type} gives raw reads: they are prepared and sorted by --sort_reads")
+    if args.short_type != "10x" and not (args.reads1 and args.reads2):
+        raise ValueError(f"raw {args.short_type} reads are given as -1 R1 -2 R2")
 
 
 def sort_reads_first(args) -> None:
@@ -94,7 +110,9 @@ def sort_reads_first(args) -> None:
         else:
             from .sortreads import sort_fastq
             os.makedirs(os.path.dirname(path), exist_ok=True)
-            res = sort_fastq(args.interleaved_reads or args.reads1, path, None if args.interleaved_reads else args.reads2)
+            short_type = getattr(args, "short_type", "10x")
+            raw = {"short_type": short_type, "index": getattr(args, "index", "") or None} if short_type != "10x" else {}
+            res = sort_fastq(args.interleaved_reads or args.reads1, path, None if args.interleaved_reads else args.reads2, **raw)
             logging.info(f"step 0: reads sorted by barcode: {res}")
     pdist.wait_for_all()
     args.interleaved_reads, args.reads1, args.reads2 = path, "", ""
@@ -268,7 +286,12 @@ def _run(args, script_path):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    try:
+        check_short_type(args)
+    except ValueError as e:
+        parser.error(str(e))
     run(args, os.path.dirname(os.path.abspath(__file__)))
 
 

@@ -52,11 +52,14 @@ def _free_bytes(device) -> int:
     return int(free) + int(torch.cuda.memory_reserved(device)) - int(torch.cuda.memory_allocated(device))
 
 
-def _require_room(need: int, device, what: str) -> None:
+def _require_room(need: int, device, what: str, prepared: bool = False) -> None:
     free = _free_bytes(device)
     if need > free:
+        how = ("about 2 x the prepared text's bytes -- the raw reads' and 8 + the barcode's bytes per tagged header -- + 8 per line + 64 per "
+               "read pair, and the raw texts with their line indices while the prepared text is made" if prepared
+               else "about 2 x its bytes + 8 per line + 64 per read pair")
         raise ValueError(f"{what}: {need} bytes of device memory needed, {free} free -- the whole text is sorted on the device "
-                         "(about 2 x its bytes + 8 per line + 64 per read pair); a multi-pass sort of larger files is not implemented")
+                         f"({how}); a multi-pass sort of larger files is not implemented")
 
 
 def _piece_bytes() -> int:
@@ -214,37 +217,88 @@ class _Timer:
         ms = dict.fromkeys(STAGES, 0.0)
         for stage, a, b in self.spans:
             b.synchronize()
-            ms[stage] += a.elapsed_time(b)
+            ms[stage] = ms.get(stage, 0.0) + a.elapsed_time(b)         # (a stage beside STAGES -- prep -- shows only when it ran)
         return {k: round(v, 4) for k, v in ms.items()}
 
 
 class _Loaded:
     """the input of ``sort_fastq`` / ``check_fastq`` on the device: texts, line indices, the units' tags and what they say"""
 
-    def __init__(self, src1: str, src2: str | None, device, timer: _Timer, reserve_out: bool):
+    def __init__(self, src1: str, src2: str | None, device, timer: _Timer, reserve_out: bool, short_type=None, index=None):
         self.paths = [os.fspath(src1)] + ([os.fspath(src2)] if src2 is not None else [])
         self.texts, self.sizes, self.idx = [], [], []
         self.lines_per_unit = 8 if src2 is None else 4
+        self.prep = None                                     # the counts of the rewriting in front, when there was one
+        if short_type is not None:
+            if index is not None:
+                self.paths.append(os.fspath(index))
+            self._prepare(short_type, device, timer, reserve_out)
+            src2 = None                                      # (from here on: one interleaved text)
+        else:
+            self._read(device, timer)
+        self._tags(src2, device, timer, reserve_out)
+
+    def _read_indexed(self, path: str, device, timer: _Timer) -> int:
+        """one file to the device with its line index; its records"""
+        text, n = _read_text(path, device)
+        with timer("index"):
+            idx, n_lines = line_index(text, n) if n else (torch.zeros(1, dtype=torch.int64, device=device), 0)
+        if n_lines % 4:
+            raise ValueError(f"{path}: record {n_lines // 4}: the file ends inside it ({n_lines % 4} of its 4 lines) (PG_EFORMAT)")
+        self.texts.append(text)
+        self.sizes.append(n)
+        self.idx.append(idx)
+        return n_lines // 4
+
+    def _prepare(self, short_type: str, device, timer: _Timer, reserve_out: bool) -> None:
+        """raw stLFR / TELL-seq R1, R2 (and I1) to ONE interleaved text in the BX:Z: form, in input order (prepreads: the plan and
+        write kernels); the raw texts are freed, and what follows sees an interleaved input"""
+        from . import prepreads
+        mode = prepreads._mode(short_type)
+        records = [self._read_indexed(path, device, timer) for path in self.paths]
+        for path, r in zip(self.paths[1:], records[1:]):
+            if r != records[0]:
+                raise ValueError(f"{self.paths[0]} holds {records[0]} records, {path} holds {r}: "
+                                 "the read files must have the same number of records (PG_EFORMAT)")
+        with timer("prep"):
+            plan = prepreads.Plan(mode, self.texts, self.sizes, self.idx, records[0])
+        error = prepreads.status_error(self.paths, plan.status)
+        if error:
+            raise ValueError(error)
+        with timer("prep"):
+            text, n, units = prepreads.interleaved_text(plan, lambda need: _require_room(need, device, self.paths[0], prepared=True))
+        flagged = int(plan.tagged.sum().item()) if records[0] else 0
+        self.prep = {"short_type": short_type, "raw_pairs": records[0], "prepared_pairs": units, "dropped_pairs": records[0] - units,
+                     "tagged_pairs": flagged}
+        del plan
+        self.texts, self.sizes, self.idx = [text], [n], []   # (the raw texts and their indices are given back here)
+        self.lines_per_unit = 8
+        _require_room((n if reserve_out else 0) + n // 2, device, self.paths[0], prepared=True)
+        with timer("index"):
+            idx, n_lines = line_index(text, n) if n else (torch.zeros(1, dtype=torch.int64, device=device), 0)
+        if n_lines != 8 * units:
+            raise RuntimeError(f"sort_fastq: the prepared text has {n_lines} lines, {8 * units} were written (internal error)")
+        self.idx.append(idx)
+        self.records = [2 * units]
+
+    def _read(self, device, timer: _Timer) -> None:
+        src2 = self.paths[1] if len(self.paths) == 2 else None
         records = []
         for path in self.paths:
-            text, n = _read_text(path, device)
-            with timer("index"):
-                idx, n_lines = line_index(text, n) if n else (torch.zeros(1, dtype=torch.int64, device=device), 0)
-            if n_lines % 4:
-                raise ValueError(f"{path}: record {n_lines // 4}: the file ends inside it ({n_lines % 4} of its 4 lines) (PG_EFORMAT)")
-            self.texts.append(text)
-            self.sizes.append(n)
-            self.idx.append(idx)
-            records.append(n_lines // 4)
+            records.append(self._read_indexed(path, device, timer))
         if src2 is None and records[0] % 2:
             raise ValueError(f"{self.paths[0]}: record {records[0] - 1} has no mate: {records[0]} records are an odd number "
                              "(an interleaved file holds records 2i and 2i + 1 as mates; PG_EFORMAT)")
         if src2 is not None and records[0] != records[1]:
             raise ValueError(f"{self.paths[0]} holds {records[0]} records, {self.paths[1]} holds {records[1]}: "
                              "R1 and R2 must have the same number of records (PG_EFORMAT)")
+        self.records = records
+
+    def _tags(self, src2, device, timer: _Timer, reserve_out: bool) -> None:
+        records = self.records
         self.pairs = records[0] // 2 if src2 is None else records[0]
         self.bytes = sum(self.sizes)
-        _require_room((self.bytes if reserve_out else 0) + UNIT_BYTES * self.pairs, device, self.paths[0])
+        _require_room((self.bytes if reserve_out else 0) + UNIT_BYTES * self.pairs, device, self.paths[0], self.prep is not None)
         with timer("tags"):
             self.tag_off, self.tag_len, status = barcode_tags(self.texts[0], self.idx[0], self.pairs, self.lines_per_unit, self.sizes[0])
         _raise_malformed(self.paths[0], status)
@@ -299,7 +353,23 @@ def _device_of(device):
     return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
 
 
-def sort_fastq(src1: str, out: str, src2: str | None = None, device=None) -> dict:
+def _short_type_of(short_type, src1, src2, index, outs: list):
+    """``short_type`` as ``_Loaded`` takes it: None for barcodes that stand in a BX:Z: tag already (None, "10x"), else stlfr /
+    tellseq with their files checked (ValueError)"""
+    if short_type is None or short_type == "10x":
+        if index is not None:
+            raise ValueError(f"index reads go with short_type tellseq only, not with {short_type or '10x'}")
+        return None
+    from . import prepreads
+    if short_type not in prepreads.SHORT_TYPES:
+        raise ValueError(f"short_type must be 10x, stlfr or tellseq (got {short_type!r})")
+    if src2 is None:
+        raise ValueError(f"{short_type} reads are given as -1 R1 -2 R2, not interleaved: the barcode of a pair is rewritten on both mates")
+    prepreads.check_files(short_type, src1, src2, index, outs)
+    return short_type
+
+
+def sort_fastq(src1: str, out: str, src2: str | None = None, device=None, short_type: str | None = None, index: str | None = None) -> dict:
     """write the read pairs of ``src1`` (interleaved) or of ``src1`` / ``src2`` (R1 / R2), plain or gzip, to ``out`` as one
     interleaved plain FASTQ sorted by barcode: the rule of this module's head.  The output is written under a temporary name
     beside ``out`` and moved into place at the end.  ValueError with the record's ordinal: a header without ``@``, a third line
@@ -309,17 +379,25 @@ def sort_fastq(src1: str, out: str, src2: str | None = None, device=None) -> dic
 
     Returns ``pairs``, ``barcodes`` (distinct tags), ``untagged_pairs``, ``longest_tag`` (bytes behind the prefix), ``passes``
     (sorts run: 0 when ``already_sorted``), ``already_sorted`` (the input's own order has no descent: it is copied), ``bytes``
-    (written), ``seconds`` (wall) and ``device_ms`` per stage -- index, tags, sort (keys + sorts), compare, gather."""
+    (written), ``seconds`` (wall) and ``device_ms`` per stage -- index, tags, sort (keys + sorts), compare, gather.
+
+    ``short_type`` "stlfr" or "tellseq" (``-1``/``-2`` only; ``index``: TELL-seq's index reads): the inputs are RAW reads, rewritten
+    first as ``prepreads.preprocess_reads`` rewrites them, on the device and in input order, into one interleaved text that then
+    goes through everything above unchanged -- one more pass over the text than an order made from the raw barcodes would need,
+    by code that is pinned already.  Needs about 2 x the prepared text on the device, and the raw texts while it is made.  The
+    result then also holds ``short_type``, ``raw_pairs``, ``prepared_pairs``, ``dropped_pairs`` (TELL-seq: index reads that are not
+    18 bytes), ``tagged_pairs`` and a ``prep`` entry in ``device_ms``.  None or "10x": nothing changes."""
     t0 = time.perf_counter()
     dev = _device_of(device)
     out = os.fspath(out)
     if out.endswith(".gz"):
         raise ValueError(f"{out}: the sorted reads are written as plain text, gzip output is not supported")
-    if os.path.realpath(out) in {os.path.realpath(os.fspath(p)) for p in (src1, src2) if p is not None}:
+    if os.path.realpath(out) in {os.path.realpath(os.fspath(p)) for p in (src1, src2, index) if p is not None}:
         raise ValueError(f"the output must differ from the inputs (got {out})")
+    short_type = _short_type_of(short_type, src1, src2, index, [out])
     timer = _Timer()
     with torch.cuda.device(dev):
-        L = _Loaded(src1, src2, dev, timer, reserve_out=True)
+        L = _Loaded(src1, src2, dev, timer, reserve_out=True, short_type=short_type, index=index)
         n, passes = L.pairs, 0
         order, sorted_in = None, True
         if n:
@@ -355,18 +433,25 @@ def sort_fastq(src1: str, out: str, src2: str | None = None, device=None) -> dic
             if os.path.exists(tmp):
                 os.remove(tmp)
         device_ms = timer.result()
-    return {"pairs": n, "barcodes": barcodes, "untagged_pairs": L.untagged, "longest_tag": L.longest, "passes": passes,
-            "already_sorted": sorted_in, "bytes": L.bytes, "seconds": round(time.perf_counter() - t0, 6), "device_ms": device_ms}
+    res = {"pairs": n, "barcodes": barcodes, "untagged_pairs": L.untagged, "longest_tag": L.longest, "passes": passes,
+           "already_sorted": sorted_in, "bytes": L.bytes, "seconds": round(time.perf_counter() - t0, 6), "device_ms": device_ms}
+    if L.prep is not None:
+        device_ms.setdefault("prep", 0.0)
+        res.update(L.prep)
+    return res
 
 
-def check_fastq(src1: str, src2: str | None = None, device=None) -> dict:
+def check_fastq(src1: str, src2: str | None = None, device=None, short_type: str | None = None, index: str | None = None) -> dict:
     """is the input sorted by barcode as ``sort_fastq`` sorts?  ``sorted``; ``first_descent``: the ordinal of the first unit whose
     tag stands before its predecessor's, or None; ``pairs``, ``barcodes`` (distinct tags: an unsorted input is ordered, not
-    written, to count them), ``untagged_pairs``.  The refusals are ``sort_fastq``'s."""
+    written, to count them), ``untagged_pairs``.  The refusals are ``sort_fastq``'s.  ``short_type`` / ``index`` as there: the
+    question is asked of the raw reads as they would be prepared (ordinals count the prepared units), and the preprocess
+    counts are in the result."""
     dev = _device_of(device)
+    short_type = _short_type_of(short_type, src1, src2, index, [])
     timer = _Timer()
     with torch.cuda.device(dev):
-        L = _Loaded(src1, src2, dev, timer, reserve_out=False)
+        L = _Loaded(src1, src2, dev, timer, reserve_out=False, short_type=short_type, index=index)
         first = None
         cmp_sorted = None
         if L.pairs:
@@ -377,5 +462,8 @@ def check_fastq(src1: str, src2: str | None = None, device=None) -> dict:
                 cmp_sorted = L.compare(_order_of(L.texts[0], L.sizes[0], L.tag_off, L.tag_len, L.longest)[0], timer)
             else:
                 cmp_sorted = cmp_in
-        return {"sorted": first is None, "first_descent": first, "pairs": L.pairs, "barcodes": L.barcodes(cmp_sorted) if L.pairs else 0,
-                "untagged_pairs": L.untagged}
+        res = {"sorted": first is None, "first_descent": first, "pairs": L.pairs, "barcodes": L.barcodes(cmp_sorted) if L.pairs else 0,
+               "untagged_pairs": L.untagged}
+        if L.prep is not None:
+            res.update(L.prep)
+        return res
