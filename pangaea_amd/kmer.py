@@ -14,14 +14,11 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fastqtext, readops
+from .fastqtext import stream_ptr as _stream_ptr
 from .reads import ReadStream, Rows
 
 DEFAULT_SEG_CHARS = 65536              # row segments of the lookup kernels (K1: every segment ends in 136 global adds; 16384: 0.98 ms, 65536: 0.83 ms at 10 M pairs)
-
-
-def _stream_ptr(device: torch.device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _require_gpu(t: torch.Tensor, what: str) -> None:
@@ -1498,477 +1495,12 @@ class KmerTable:
             raise RuntimeError("pg_table_depth: the workspace did not hold the long ranges (PG_STATUS_DEPTH_WORKSPACE)")
         return out
 
-    # ------------------------------------------------------------------ reads by their k-mers' counts (kmc_tools filter)
+    # ------------------------------------------------------------------ reads by their k-mers' counts (kmc_tools filter): readops.py
 
-    FILTER_PIECE_BYTES = 256 << 20         # FASTQ text per piece and input of ``filter_fastq`` (device buffer + pinned host buffer)
+    FILTER_PIECE_BYTES = fastqtext.PIECE_BYTES     # FASTQ text per piece and input of ``filter_fastq`` (PG_FILTER_PIECE_BYTES overrides)
 
-    @staticmethod
-    def _filter_piece_bytes() -> int:
-        """PG_FILTER_PIECE_BYTES overrides the piece size (tests: records across every boundary, a record larger than a piece)"""
-        want = os.environ.get("PG_FILTER_PIECE_BYTES")
-        return max(64, int(want)) if want else KmerTable.FILTER_PIECE_BYTES
-
-    def _hits_window(self, lower, upper, min_qual_char) -> tuple:
-        """(lower, upper or -1, quality threshold byte or 0) as pg_table_read_hits takes them"""
-        lower = int(lower)
-        if lower < 0:
-            raise ValueError(f"lower must be at least 0 (got {lower})")
-        if upper is not None and int(upper) < lower:
-            raise ValueError(f"upper ({upper}) is below lower ({lower})")
-        if min_qual_char is None:
-            mq = 0
-        else:
-            c = min_qual_char.encode("latin-1") if isinstance(min_qual_char, str) else bytes([min_qual_char]) if isinstance(min_qual_char, int) else bytes(min_qual_char)
-            if len(c) != 1 or c[0] == 0:
-                raise ValueError(f"min_qual_char must be one character (got {min_qual_char!r})")
-            mq = c[0]
-        return lower, -1 if upper is None else int(upper), mq
-
-    def _line_index(self, text: torch.Tensor, n_bytes: int, hold: dict) -> tuple:
-        """(line starts: int64 on the device, entries 0 .. n_lines valid; n_lines) of text[:n_bytes] (pg_fastq_index).  ``hold``
-        keeps the index buffer and the workspace for the next piece.  A host wait."""
-        L = _lib.load()
-        dev = self.device
-        need = _lib.check(L.pg_fastq_index_workspace_bytes(n_bytes))
-        if hold.get("ws") is None or hold["ws"].numel() < need:
-            hold["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-        word = torch.zeros(1, dtype=torch.int64, device=dev)
-        cap = n_bytes // 16 + 1024               # (reads have lines of 50 bytes and more; a text of shorter ones asks twice)
-        while True:
-            if hold.get("idx") is None or hold["idx"].numel() < cap:
-                hold["idx"] = torch.empty(cap, dtype=torch.int64, device=dev)
-            idx = hold["idx"]
-            _lib.check(L.pg_fastq_index(text.data_ptr(), n_bytes, idx.data_ptr(), idx.numel(), word.data_ptr(), hold["ws"].data_ptr(),
-                                        hold["ws"].numel(), _stream_ptr(dev)))
-            n_lines = int(word.item())
-            if n_lines + 1 <= idx.numel():
-                return idx, n_lines
-            cap = n_lines + 1
-
-    def _hits_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, window: tuple,
-                 lowercase_is_base: bool, status: torch.Tensor | None = None, events: tuple | None = None) -> tuple:
-        """(hits: int32 [n_records, 2] holding the 32-bit counts, status: int64 [2]) of pg_table_read_hits, both on the device.
-        ``status``: a tensor to use (the entry writes it whole); ``events``: two device events recorded right around the entry"""
-        dev = self.device
-        hits = torch.empty((n_records, 2), dtype=torch.int32, device=dev)
-        if status is None:
-            status = torch.empty(2, dtype=torch.int64, device=dev)
-        lower, upper, mq = window
-        L = _lib.load()
-        if events:
-            events[0].record()
-        rc = L.pg_table_read_hits(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, upper,
-                                  1 if lowercase_is_base else 0, mq, hits.data_ptr(), status.data_ptr(), _stream_ptr(dev))
-        if events:
-            events[1].record()
-        _lib.check(rc)
-        return hits, status
-
-    def read_hits(self, text: torch.Tensor, lower: int = 1, upper: int | None = None, lowercase_is_base: bool = True,
-                  min_qual_char=None) -> torch.Tensor:
-        """(n, h) of every record of a four-line FASTQ text: int64 [n_records, 2] on the table's device -- n = the k-mers of the
-        record's sequence line, h = those whose count c in this table (0: absent; saturated counts as stored) satisfies
-        ``lower <= c <= upper`` (``upper`` None: no upper bound; ``lower`` 0 is allowed, ``lower = upper = 0`` counts the absent
-        k-mers).  The alignment-free counterpart of the read choice of scripts/low_abd_reads.sh:10 (extract_unmapped.cpp).
-
-        ``text``: a uint8 tensor ON THE DEVICE that holds whole records.  A line ends at ``\\n``, a last line without one is a
-        line, ``\\r`` is an ordinary byte of its line (no base).  Record r is lines 4r .. 4r + 3; line 0 must begin with ``@``,
-        line 2 with ``+``.  Position i of the sequence line holds a k-mer iff i + k <= its length and bytes i .. i + k - 1 are all
-        bases: ACGT, and acgt too when ``lowercase_is_base`` (the rule the tables are counted with); with ``min_qual_char`` a
-        base whose quality byte at the same offset is below it is no base (what ``--min-qual-char`` does to -1/-2 tables), and
-        a quality line shorter than its sequence line is malformed -- otherwise the quality line is never looked at.  Malformed
-        text (a line count that is no multiple of 4 included) raises ValueError naming the first offending record; a CPU tensor
-        RuntimeError.  The table is only read (pg_fastq_index, pg_table_read_hits)."""
-        return self._rows_of_text(text, 2, lambda: self._hits_window(lower, upper, min_qual_char),
-                                  lambda t, n, idx, n_rec, window: self._hits_of(t, n, idx, n_rec, 0, window, bool(lowercase_is_base)))
-
-    def _rows_of_text(self, text: torch.Tensor, width: int, checked, rows_of) -> torch.Tensor:
-        """what ``read_hits`` and ``read_spans`` do with a text on the device: its checks, its line index, the rows
-        ``rows_of(text, n_bytes, idx, n_records, checked())`` -> (int32 [n_records, width], status) widened to int64, and the
-        ValueError for malformed text"""
-        if not isinstance(text, torch.Tensor) or text.dtype != torch.uint8 or text.dim() != 1:
-            raise TypeError("text must be a one-dimensional uint8 tensor")
-        _require_gpu(text, "the FASTQ text")
-        self._require_readable()
-        if text.device != self.device:
-            raise ValueError("text and table are on different devices")
-        args = checked()
-        n = int(text.numel())
-        if n == 0:
-            return torch.zeros((0, width), dtype=torch.int64, device=self.device)
-        text = text.contiguous()
-        if text.data_ptr() & 15:                 # (a view into a larger text: the kernels read 16-byte pieces)
-            text = text.clone()
-        with torch.cuda.device(self.device):
-            idx, n_lines = self._line_index(text, n, {})
-            rows, bad = torch.zeros((0, width), dtype=torch.int32, device=self.device), -1
-            if n_lines >= 4:
-                rows, status = rows_of(text, n, idx, n_lines // 4, args)
-                bad = int(status[1].item())
-        if bad != -1:
-            raise ValueError(_fastq_error("the text", bad & ((1 << 64) - 1)))
-        if n_lines % 4:
-            raise ValueError(f"the text: record {n_lines // 4}: the text ends inside it ({n_lines} lines, no multiple of 4) (PG_EFORMAT)")
-        return rows.to(torch.int64) & 0xFFFFFFFF
-
-    @staticmethod
-    def _span_mode(mode) -> int:
-        if mode not in _lib.SPAN_MODES:
-            raise ValueError(f"mode must be first or longest (got {mode!r})")
-        return _lib.SPAN_MODES[mode]
-
-    def _spans_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, window: tuple,
-                  lowercase_is_base: bool, mode: int, status: torch.Tensor | None = None, events: tuple | None = None) -> tuple:
-        """(spans: int32 [n_records, 4] holding the 32-bit n, h, start, length; status: int64 [2]; trimmed bytes: int64
-        [n_records]) of pg_table_read_spans, all on the device; ``status`` and ``events`` as for ``_hits_of``"""
-        dev = self.device
-        spans = torch.empty((n_records, 4), dtype=torch.int32, device=dev)
-        sizes = torch.empty(n_records, dtype=torch.int64, device=dev)
-        if status is None:
-            status = torch.empty(2, dtype=torch.int64, device=dev)
-        lower, upper, mq = window
-        L = _lib.load()
-        if events:
-            events[0].record()
-        rc = L.pg_table_read_spans(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, upper,
-                                   1 if lowercase_is_base else 0, mq, mode, spans.data_ptr(), sizes.data_ptr(), status.data_ptr(), _stream_ptr(dev))
-        if events:
-            events[1].record()
-        _lib.check(rc)
-        return spans, status, sizes
-
-    def read_spans(self, text: torch.Tensor, lower: int = 1, upper: int | None = None, mode: str = "longest", lowercase_is_base: bool = True,
-                   min_qual_char=None) -> torch.Tensor:
-        """(n, h, start, length) of every record of a four-line FASTQ text: int64 [n_records, 4] on the table's device -- n, h as
-        ``read_hits`` gives them, and the record's solid span: position i of the sequence line is SOLID iff it holds a k-mer whose
-        count c in this table satisfies ``lower <= c <= upper``; a run is a maximal interval [a, b) of solid positions and covers
-        the bases [a, b + k - 1).  ``mode`` "longest": the longest run's (start, length) = (a, b - a + k - 1), among equals the
-        leftmost; "first": the run that begins at position 0, i.e. the read up to its first k-mer outside the window
-        (`kmc_tools filter -t`, khmer's filter-abund).  (0, 0) where there is no such run.  ``text``, the k-mer rules and the
-        errors are those of ``read_hits``; in addition a quality line that does not reach as far as its sequence line (line
-        ends aside) is malformed whatever ``min_qual_char`` says, since a trimmed record cuts it too.  The table is only read
-        (pg_fastq_index, pg_table_read_spans)."""
-        return self._rows_of_text(text, 4, lambda: (self._hits_window(lower, upper, min_qual_char), self._span_mode(mode)),
-                                  lambda t, n, idx, n_rec, a: self._spans_of(t, n, idx, n_rec, 0, a[0], bool(lowercase_is_base), a[1])[:2])
-
-    def _corrections_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, window: tuple,
-                        lowercase_is_base: bool, out: torch.Tensor | None, status: torch.Tensor | None = None,
-                        events: tuple | None = None) -> tuple:
-        """(rows: int32 [n_records, 4] holding the 32-bit n, h, candidates, corrected; status: int64 [2]) of
-        pg_table_correct_reads, both on the device.  ``out``: None (rows only), a copy of ``text`` or ``text`` itself (in place);
-        ``status`` and ``events`` as for ``_hits_of``"""
-        dev = self.device
-        rows = torch.empty((n_records, 4), dtype=torch.int32, device=dev)
-        if status is None:
-            status = torch.empty(2, dtype=torch.int64, device=dev)
-        lower, upper, mq = window
-        L = _lib.load()
-        if events:
-            events[0].record()
-        rc = L.pg_table_correct_reads(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, upper,
-                                      1 if lowercase_is_base else 0, mq, None if out is None else out.data_ptr(), rows.data_ptr(),
-                                      status.data_ptr(), _stream_ptr(dev))
-        if events:
-            events[1].record()
-        _lib.check(rc)
-        return rows, status
-
-    def read_corrections(self, text: torch.Tensor, lower: int = 1, upper: int | None = None, lowercase_is_base: bool = True,
-                         min_qual_char=None) -> tuple:
-        """single-base substitutions of a four-line FASTQ text put right from this table (what khmer, Lighter, BFC and Musket do):
-        (rows: int64 [n_records, 4] -- n, h, candidates, corrected --, the corrected text: uint8, a new tensor of the text's size;
-        the argument is not modified), both on the table's device.  n and h are those of ``read_hits`` on the text as it came.
-
-        A position of a sequence line (its bytes without a final ``\\r``) is SOLID iff it holds a k-mer whose count c in this
-        table satisfies ``lower <= c <= upper``, WEAK iff it holds a k-mer whose count does not, VOID iff it holds none.  A
-        CANDIDATE is a maximal run [a, b) of weak positions between two solid ones with b - a == k, or between a solid one and
-        an end of the line with b - a <= k: the signature of ONE wrong base p (b - 1, or a + k - 1 at the right end) whose
-        k-mers are all weak.  It is CORRECTED iff exactly one other base at p makes all b - a k-mers solid; that base goes into
-        byte p in the letter case it had.  Runs beside a void position, runs of any other length (two errors closer than k) and
-        reads that are weak throughout are left alone, as are candidates with no or several fitting bases; the quality line
-        never changes.  All candidates of a record are judged on the record as it came: a second call corrects nothing more.
-        ``text``, the k-mer rules and the errors are those of ``read_spans``.  The table is only read (pg_fastq_index,
-        pg_table_correct_reads)."""
-        fixed = []
-
-        def rows_of(t, n, idx, n_rec, window):
-            fixed.append(t.clone())
-            return self._corrections_of(t, n, idx, n_rec, 0, window, bool(lowercase_is_base), fixed[0])
-
-        rows = self._rows_of_text(text, 4, lambda: self._hits_window(lower, upper, min_qual_char), rows_of)
-        return rows, fixed[0] if fixed else text.clone()
-
-    def correct_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
-                      lowercase_is_base: bool = True, min_qual_char=None) -> dict:
-        """put the single-base substitutions of a FASTQ file's reads right from this table (``read_corrections``) and write EVERY
-        record, in input order and with the length it came with, to ``out1`` (and ``out2``): the output is byte for byte the
-        input except the corrected bases, so each output has its input's size.  One file (interleaved or not: records are judged
-        on their own, an odd number of them is fine) or R1 / R2 (the same number of records).  Input forms, pieces, the plain-text
-        output under a temporary name, "after any error no output file is left" and the ValueErrors naming the record's ordinal
-        are those of ``trim_fastq``; a quality line that does not reach as far as its sequence line is malformed.
-
-        Returns ``records``, ``bases`` (bytes of the sequence lines), ``kmers``, ``hits`` (of the input), ``candidates``,
-        ``corrected``, ``reads_corrected`` (records with at least one corrected base) -- totals over all inputs, exact -- and
-        ``seconds`` (wall), ``device_ms`` (the pg_table_correct_reads and pg_fastq_gather entries of every piece, each between
-        two device events of its own)."""
-        import time
-        t0 = time.perf_counter()
-        pair = "single" if src2 is None else "both"
-        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
-        window = self._hits_window(lower, upper, min_qual_char)
-        totals, device_ms = self._fastq_pieces(srcs, outs, pair, _CorrectStep(self, window, bool(lowercase_is_base)))
-        return {"records": totals[0], "bases": totals[3], "kmers": totals[4], "hits": totals[5], "candidates": totals[8], "corrected": totals[9],
-                "reads_corrected": totals[10], "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
-
-    def _depth_args(self, lower, percentile, min_qual_char) -> tuple:
-        """(lower, percentile, quality threshold byte or 0) as pg_table_read_depths takes them"""
-        for name, v in (("lower", lower), ("percentile", percentile)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise ValueError(f"{name} must be an int (got {v!r})")
-        if lower < 1:
-            raise ValueError(f"lower must be at least 1 (got {lower})")
-        if not 0 <= percentile <= 100:
-            raise ValueError(f"percentile must lie in [0, 100] (got {percentile})")
-        return int(lower), int(percentile), self._hits_window(1, None, min_qual_char)[2]
-
-    def _depths_of(self, text: torch.Tensor, n_bytes: int, idx: torch.Tensor, n_records: int, first_record: int, args: tuple,
-                   lowercase_is_base: bool, seed: int = 0, unit_log2: int = 0, status: torch.Tensor | None = None,
-                   events: tuple | None = None) -> tuple:
-        """(rows: int32 [n_records, 4] holding the 32-bit n, present, d, w; status: int64 [2]) of pg_table_read_depths, both on the
-        device; ``args``: what ``_depth_args`` gave; ``status`` and ``events`` as for ``_hits_of``"""
-        dev = self.device
-        rows = torch.empty((n_records, 4), dtype=torch.int32, device=dev)
-        if status is None:
-            status = torch.empty(2, dtype=torch.int64, device=dev)
-        lower, percentile, mq = args
-        L = _lib.load()
-        if events:
-            events[0].record()
-        rc = L.pg_table_read_depths(self.desc(), self.k, text.data_ptr(), n_bytes, idx.data_ptr(), n_records, first_record, lower, percentile,
-                                    1 if lowercase_is_base else 0, mq, seed, unit_log2, rows.data_ptr(), status.data_ptr(), _stream_ptr(dev))
-        if events:
-            events[1].record()
-        _lib.check(rc)
-        return rows, status
-
-    def read_depths(self, text: torch.Tensor, lower: int = 1, percentile: int = 50, lowercase_is_base: bool = True,
-                    min_qual_char=None) -> torch.Tensor:
-        """(n, present, d) of every record of a four-line FASTQ text: int64 [n_records, 3] on the table's device -- n = the k-mers
-        of the record's sequence line; every k-mer has a value, its count c in this table (0: absent; saturated counts as
-        stored), taken as 0 when ``c < lower`` (``lower >= 1``); present = the values above 0; d = the value at index
-        ``((n - 1) * percentile) // 100`` of the n values in ascending order, 0 when n = 0.  ``percentile`` 50 gives the lower
-        median, as ``depth`` does over a packed stream -- the read's depth as BBNorm and khmer's normalize-by-median estimate it;
-        0 and 100 give the smallest and the largest value.  Exact for reads of any length.  ``text``, the k-mer rules and the
-        errors are those of ``read_hits``.  The table is only read (pg_fastq_index, pg_table_read_depths)."""
-        rows = self._rows_of_text(text, 4, lambda: self._depth_args(lower, percentile, min_qual_char),
-                                  lambda t, n, idx, n_rec, a: self._depths_of(t, n, idx, n_rec, 0, a, bool(lowercase_is_base)))
-        return rows[:, :3].contiguous()
-
-    def normalize_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, target: int | None = None,
-                        min_depth: int = 0, lower: int = 1, percentile: int = 50, pair: str = "any", seed: int = 0,
-                        lowercase_is_base: bool = True, min_qual_char=None) -> dict:
-        """normalise the read depth of a FASTQ file from this table (BBNorm, khmer's normalize-by-median; beside the read set of
-        scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp) and write the kept records, byte for byte and in input order, to
-        ``out1`` (and ``out2``): what the table covers more than ``target`` deep is thinned to about that depth, what it covers
-        less deep passes untouched, and reads whose depth marks them as errors can be dropped.
-
-        The depth d of a record among its n k-mers: ``read_depths`` (``lower``, ``percentile``, ``lowercase_is_base``,
-        ``min_qual_char`` as there).  Every unit -- a pair, or a record under ``pair`` "single" -- has ONE draw w in [0, 2^24), a
-        function of ``seed`` and the unit's ordinal alone (include/pangaea_feat.h, pg_table_read_depths: DRAW).  A record PASSES
-        iff n >= 1, d >= ``min_depth`` and ``w * d < target * 2^24`` (exact integers): with probability ``min(1, target / d)``;
-        a read of absent k-mers only has d = 0 and always passes the draw.  ``pair`` as for ``filter_fastq``; mates share their
-        draw, so "any" keeps a pair at its smaller depth and "both" at its larger.  ``target``: an int in [1, 2^31);
-        ``min_depth``: an int >= 0; ``seed``: an int in [0, 2^64).  The same arguments give the same output whatever the piece
-        size.  Input forms, pieces, the plain-text output under a temporary name, "after any error no output file is left" and
-        the ValueErrors naming the record's ordinal are those of ``filter_fastq``.
-
-        Returns ``records``, ``kept``, ``passed`` (records that passed on their own), ``low`` (records with n = 0 or
-        d < ``min_depth``), ``bases`` (bytes of the sequence lines), ``kmers``, ``hits`` (the sum of present), ``depth_in`` and
-        ``depth_out`` (the sum of d over all records and over the kept ones) -- totals over all inputs, exact -- and ``seconds``
-        (wall), ``device_ms`` (the pg_table_read_depths and pg_fastq_gather entries of every piece, each between two device
-        events of its own)."""
-        import time
-        t0 = time.perf_counter()
-        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
-        args = self._depth_args(lower, percentile, min_qual_char)
-        for name, v, lo, hi in (("target", target, 1, 1 << 31), ("min_depth", min_depth, 0, None), ("seed", seed, 0, 1 << 64)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v >= hi):
-                raise ValueError(f"{name} must be an int, at least {lo}" + (f" and below 2^{hi.bit_length() - 1}" if hi else "") + f" (got {v!r})")
-        unit_log2 = 1 if len(srcs) == 1 and pair != "single" else 0
-        step = _DepthsStep(self, args, bool(lowercase_is_base), int(target), int(min_depth), int(seed), unit_log2)
-        totals, device_ms = self._fastq_pieces(srcs, outs, pair, step)
-        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "low": totals[11], "bases": totals[3], "kmers": totals[4],
-                "hits": totals[5], "depth_in": totals[12], "depth_out": totals[13], "seconds": round(time.perf_counter() - t0, 6),
-                "device_ms": round(device_ms, 4)}
-
-    def filter_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
-                     min_hits=1, max_hits=None, pair: str = "any", lowercase_is_base: bool = True, min_qual_char=None) -> dict:
-        """keep or drop the reads of a FASTQ file by the counts of their k-mers in this table (`kmc_tools filter`, khmer's
-        filter-abund; the alignment-free counterpart of scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp) and write the kept
-        records, byte for byte and in input order, to ``out1`` (and ``out2``).
-
-        Input: four-line FASTQ, plain or gzip -- one file (``src1``; mates, if any, interleaved) or an R1/R2 pair (``src1``,
-        ``src2`` with ``out1``, ``out2``).  Records, k-mers and the hit count h of a read among its n k-mers: ``read_hits``
-        (``lower``, ``upper``, ``lowercase_is_base``, ``min_qual_char`` as there).  A read PASSES iff n >= 1, h >= ``min_hits`` and
-        h <= ``max_hits``; each bound is an int (absolute) or a float in [0, 1] (a share of n, compared as ``h >= f * n`` /
-        ``h <= f * n`` in IEEE double); ``max_hits`` None: no bound.  A read without k-mers never passes.  ``pair``: "any" keeps
-        both mates if either passes, "both" if both pass, "single" judges every record on its own (one input file only).  Mates
-        are records 2i and 2i + 1 of one file, or record i of R1 and of R2; names are not compared.  ValueError (PG_EFORMAT) with
-        the record's ordinal: a first line without ``@``, a third without ``+``, a file that ends inside a record, a short quality
-        line under ``min_qual_char``, an odd record count under any / both, R1 / R2 of different record counts.
-
-        Output is plain text (a path ending in ``.gz`` is refused), written under a temporary name of its own beside the output
-        and moved into place at the end: after any error no output file is left and no other file has been touched.  The
-        outputs must differ from each other and from the inputs.  The files go through the device in pieces of ``FILTER_PIECE_BYTES``
-        (PG_FILTER_PIECE_BYTES, read at call time): a piece starts at a record start, what lies behind its last complete record
-        (and, for R1 / R2, behind the records both pieces hold) is carried into the next, a record larger than a piece grows the
-        buffer.  The device holds one piece per input, its line index, the hits and one output piece.
-
-        Returns ``records``, ``kept``, ``passed`` (records that passed on their own), ``bases`` (bytes of the sequence lines),
-        ``kmers``, ``hits`` -- totals over all inputs, exact -- and ``seconds`` (wall), ``device_ms`` (the pg_table_read_hits and
-        pg_fastq_gather entries of every piece, each between two device events of its own)."""
-        import time
-        t0 = time.perf_counter()
-        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
-        window = self._hits_window(lower, upper, min_qual_char)
-        lo_bound, hi_bound = _hit_bound(min_hits, "min_hits"), None if max_hits is None else _hit_bound(max_hits, "max_hits")
-        totals, device_ms = self._fastq_pieces(srcs, outs, pair, _HitsStep(self, window, bool(lowercase_is_base), lo_bound, hi_bound))
-        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "bases": totals[3], "kmers": totals[4], "hits": totals[5],
-                "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
-
-    def trim_fastq(self, src1: str, out1: str, src2: str | None = None, out2: str | None = None, lower: int = 1, upper: int | None = None,
-                   mode: str = "longest", min_len: int | None = None, pair: str = "both", lowercase_is_base: bool = True,
-                   min_qual_char=None) -> dict:
-        """cut the reads of a FASTQ file down to the part this table vouches for (`kmc_tools filter -t`, khmer's filter-abund /
-        trim-low-abund; beside the read set of scripts/low_abd_reads.sh:10 -> extract_unmapped.cpp) and write them, in input
-        order, to ``out1`` (and ``out2``): a read with one sequencing error keeps its good bases where ``filter_fastq`` could only
-        keep the error or drop the read.
-
-        The span of a record -- ``read_spans``: ``mode`` "longest" (the longest run of solid k-mers) or "first" (the read up to its
-        first k-mer outside ``[lower, upper]``) -- is (start, length).  A record PASSES iff length >= ``min_len`` (None: k; at
-        least 1).  ``pair``: "both" (the default) keeps a pair when both mates pass, "any" when either does, "single" judges every
-        record of one file on its own.  EVERY written record is written trimmed to its span: line 0 and line 2 as they are,
-        ``seq[start : start + length]`` and ``qual[start : start + length]`` with the line ends they had (``\\r\\n`` stays
-        ``\\r\\n``, a final record without ``\\n`` leaves without one); quality bytes beyond the sequence are dropped.  That includes a
-        mate kept under "any" that did not pass, possibly with empty sequence and quality lines -- which is why "both" is the
-        default here.  A quality line that does not reach as far as its sequence line is malformed, with or without
-        ``min_qual_char``.  Input forms, pieces, the plain-text output under a temporary name, "after any error no output file is
-        left" and the ValueErrors naming the record's ordinal are those of ``filter_fastq``.
-
-        Returns ``records``, ``kept``, ``passed`` (records that passed on their own), ``trimmed`` (kept records that came out
-        shorter than they went in), ``bases`` (bytes of the sequence lines), ``bases_out`` (bases written), ``kmers``, ``hits`` --
-        totals over all inputs, exact -- and ``seconds`` (wall), ``device_ms`` (the pg_table_read_spans and
-        pg_fastq_gather_trimmed entries of every piece, each between two device events of its own)."""
-        import time
-        t0 = time.perf_counter()
-        srcs, outs = _fastq_files(src1, out1, src2, out2, pair)
-        window = self._hits_window(lower, upper, min_qual_char)
-        mode = self._span_mode(mode)
-        if min_len is None:
-            min_len = self.k
-        if isinstance(min_len, bool) or not isinstance(min_len, (int, np.integer)) or min_len < 1:
-            raise ValueError(f"min_len must be a whole number of bases, at least 1 (got {min_len!r})")
-        totals, device_ms = self._fastq_pieces(srcs, outs, pair, _SpansStep(self, window, bool(lowercase_is_base), mode, int(min_len)))
-        return {"records": totals[0], "kept": totals[1], "passed": totals[2], "trimmed": totals[6], "bases": totals[3], "bases_out": totals[7],
-                "kmers": totals[4], "hits": totals[5], "seconds": round(time.perf_counter() - t0, 6), "device_ms": round(device_ms, 4)}
-
-    def _fastq_pieces(self, srcs: list, outs: list, pair: str, step) -> tuple:
-        """the piece loop of ``filter_fastq``, ``trim_fastq``, ``correct_fastq`` and ``normalize_fastq``: (totals: records, kept, passed,
-        bases, kmers, hits, trimmed, bases written, candidates, corrected, reads corrected, low, depth in, depth out -- exact ints --,
-        device milliseconds of the timed entries).
-        ``step`` is what differs between them: its
-        ``launch`` enqueues the per-record kernel of a piece, its ``judge`` turns the kernel's rows into pass flags and totals, its
-        ``sizes`` gives the bytes each kept record leaves with and its ``gather`` writes them to their places."""
-        self._require_readable()
-        dev = self.device
-        piece = self._filter_piece_bytes()
-        mates = pair != "single"
-        tot = torch.zeros(14, dtype=torch.int64, device=dev)
-        timed = []                                                       # (event, event) around every timed entry; read at the end
-        ins, files, tmps = [], [], []
-        try:
-            with torch.cuda.device(dev):
-                for path in srcs:
-                    ins.append(_FastqPieces(path, piece))
-                for o in outs:
-                    f, tmp = _temp_beside(o)
-                    files.append(f)
-                    tmps.append(tmp)
-                status = torch.empty((len(ins), 2), dtype=torch.int64, device=dev)
-                out_dev = out_host = None
-                done = False
-                while not done:
-                    for s in ins:
-                        s.fill()
-                        s.index(self)
-                    n, pending, all_eof = _filter_round(ins, mates, pair)
-                    if n == 0 and pending is None and not all_eof:       # a buffer that is full and holds no record (pair): a longer one
-                        for s in ins:
-                            if not s.eof and s.n_rec < (2 if len(ins) == 1 and mates else 1):
-                                s.grow()
-                        continue
-                    done = all_eof or pending is not None
-                    if n:
-                        got = []
-                        for i, s in enumerate(ins):
-                            timed.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                            got.append(step.launch(s, n, status[i], timed[-1]))
-                        for s, b in zip(ins, status[:, 1].cpu().tolist()):       # (the malformed record in front comes before what is pending)
-                            if b != -1:
-                                raise ValueError(_fastq_error(s.path, b & ((1 << 64) - 1)))
-                    if pending is not None:
-                        raise ValueError(pending)
-                    if n == 0:
-                        break
-                    passed = []
-                    for s, rows in zip(ins, got):
-                        passed.append(step.judge(rows, tot))
-                        tot[0] += n
-                        tot[3] += (s.idx[2:4 * n:4] - s.idx[1:4 * n:4] - 1).sum()
-                    if len(ins) == 2:
-                        keep = passed[0] | passed[1] if pair == "any" else passed[0] & passed[1]
-                        keeps = [keep, keep]
-                    elif mates:
-                        p2 = passed[0].view(-1, 2)
-                        keeps = [(p2.any(1) if pair == "any" else p2.all(1)).repeat_interleave(2)]
-                    else:
-                        keeps = passed
-                    for s, keep, f, rows in zip(ins, keeps, files, got):
-                        kept = keep.nonzero().flatten()
-                        lens = step.sizes(s, rows, kept, tot)
-                        dst = torch.cumsum(lens, 0) - lens
-                        n_kept = int(kept.numel())
-                        total, used = (int(v) for v in torch.stack([lens.sum(), s.idx[4 * n]]).tolist())
-                        tot[1] += n_kept
-                        if total:
-                            if out_dev is None or out_dev.numel() < total:
-                                out_dev = out_host = None
-                                out_dev = torch.empty(total + total // 8, dtype=torch.uint8, device=dev)
-                                out_host = torch.empty(out_dev.numel(), dtype=torch.uint8, pin_memory=True)
-                            timed.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
-                            timed[-1][0].record()
-                            rc = step.gather(s, n, rows, kept, dst, n_kept, out_dev)
-                            timed[-1][1].record()
-                            _lib.check(rc)
-                            out_host[:total].copy_(out_dev[:total], non_blocking=True)
-                            torch.cuda.current_stream(dev).synchronize()
-                            f.write(memoryview(out_host.numpy())[:total])
-                        s.consume(used, n)
-                totals = tot.cpu().tolist()                              # (a host wait: every timed event has happened)
-                device_ms = sum(a.elapsed_time(b) for a, b in timed)
-            for f in files:
-                f.close()
-            for tmp, o in zip(tmps, outs):
-                os.replace(tmp, o)
-        finally:
-            for s in ins:
-                s.close()
-            for f in files:
-                f.close()
-            for tmp in tmps:
-                if os.path.exists(tmp):
-                    os.remove(tmp)
-        return totals, device_ms
+    read_hits, read_spans, read_corrections, read_depths = readops.read_hits, readops.read_spans, readops.read_corrections, readops.read_depths
+    filter_fastq, trim_fastq, correct_fastq, normalize_fastq = readops.filter_fastq, readops.trim_fastq, readops.correct_fastq, readops.normalize_fastq
 
     # ------------------------------------------------------------------ summing finished tables (jellyfish merge)
 
@@ -2187,287 +1719,6 @@ class KmerTable:
         return {"n_a": n_a, "n_b": n_b, "n_shared": n_shared, "sum_a": sum_a, "sum_b": sum_b, "sum_min": sum_min,
                 "jaccard": ratio(n_shared, n_a + n_b - n_shared), "containment_a": ratio(n_shared, n_a), "containment_b": ratio(n_shared, n_b),
                 "bray_curtis": 1.0 - 2.0 * sum_min / (sum_a + sum_b) if sum_a + sum_b else 0.0}
-
-
-def _fastq_error(what: str, status: int) -> str:
-    """the message for status[1] of pg_table_read_hits: the malformed record with the smallest ordinal, and why"""
-    record, reason = status >> 8, status & 0xFF
-    why = {_lib.FASTQ_NO_AT: "its first line does not begin with '@'", _lib.FASTQ_NO_PLUS: "its third line does not begin with '+'",
-           _lib.FASTQ_SHORT_QUALITY: "its quality line is shorter than its sequence line",
-           _lib.FASTQ_BAD_INDEX: "the line index does not describe the text"}.get(reason, f"reason {reason}")
-    return f"{what}: record {record}: {why} (PG_EFORMAT)"
-
-
-def _hit_bound(v, name: str) -> tuple:
-    """a hit bound of ``KmerTable.filter_fastq`` as (is a share, value): an int is absolute, a float in [0, 1] a share of n"""
-    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
-        raise ValueError(f"{name} must be an int (absolute) or a float in [0, 1] (a share of the read's k-mers), got {v!r}")
-    if isinstance(v, (int, np.integer)):
-        if v < 0:
-            raise ValueError(f"{name} must be at least 0 (got {v})")
-        return False, int(v)
-    if not 0.0 <= v <= 1.0:
-        raise ValueError(f"{name} as a share must lie in [0, 1] (got {v})")
-    return True, float(v)
-
-
-def _bound_holds(h: torch.Tensor, n: torch.Tensor, bound: tuple, at_least: bool) -> torch.Tensor:
-    """h >= bound (``at_least``) or h <= bound, element-wise; a share is compared as h against f * n in IEEE double (h, n < 2^32:
-    both sides exact before the product is rounded once, as numpy rounds it)"""
-    share, v = bound
-    ref = n.to(torch.float64) * v if share else v
-    left = h.to(torch.float64) if share else h
-    return left >= ref if at_least else left <= ref
-
-
-def _fastq_files(src1, out1, src2, out2, pair: str) -> tuple:
-    """(input paths, output paths) of ``KmerTable.filter_fastq`` / ``trim_fastq``, refused before anything is opened where they make
-    no sense"""
-    if pair not in ("any", "both", "single"):
-        raise ValueError(f"pair must be any, both or single (got {pair!r})")
-    if (src2 is None) != (out2 is None):
-        raise ValueError("src2 and out2 go together: two inputs give two outputs")
-    if pair == "single" and src2 is not None:
-        raise ValueError("pair='single' judges the records of ONE file; R1/R2 input is paired")
-    srcs = [os.fspath(src1)] + ([os.fspath(src2)] if src2 is not None else [])
-    outs = [os.fspath(out1)] + ([os.fspath(out2)] if out2 is not None else [])
-    for o in outs:
-        if o.endswith(".gz"):
-            raise ValueError(f"{o}: the kept reads are written as plain text, gzip output is not supported")
-    real_outs = [os.path.realpath(x) for x in outs]
-    if len(set(real_outs)) != len(outs) or set(real_outs) & {os.path.realpath(x) for x in srcs}:
-        raise ValueError("the outputs must differ from each other and from the inputs (got " + ", ".join(outs + srcs) + ")")
-    return srcs, outs
-
-
-class _HitsStep:
-    """what ``KmerTable.filter_fastq`` does with a piece (``KmerTable._fastq_pieces``): pg_table_read_hits, the hit bounds, the
-    records byte for byte (pg_fastq_gather)"""
-
-    def __init__(self, table, window, lenient, lo_bound, hi_bound):
-        self.table, self.window, self.lenient, self.lo_bound, self.hi_bound = table, window, lenient, lo_bound, hi_bound
-
-    def launch(self, s, n, status, events):
-        return self.table._hits_of(s.text, s.have, s.idx, n, s.done, self.window, self.lenient, status, events)[0]
-
-    def judge(self, hits, tot):
-        nk, hh = (hits[:, 0].to(torch.int64) & 0xFFFFFFFF), (hits[:, 1].to(torch.int64) & 0xFFFFFFFF)
-        ok = (nk >= 1) & _bound_holds(hh, nk, self.lo_bound, True)
-        if self.hi_bound is not None:
-            ok &= _bound_holds(hh, nk, self.hi_bound, False)
-        tot[2] += ok.sum()
-        tot[4] += nk.sum()
-        tot[5] += hh.sum()
-        return ok
-
-    def sizes(self, s, hits, kept, tot):
-        return s.idx[4 * kept + 4] - s.idx[4 * kept]
-
-    def gather(self, s, n, hits, kept, dst, n_kept, out):
-        return _lib.load().pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept, out.data_ptr(),
-                                           out.numel(), _stream_ptr(self.table.device))
-
-
-class _SpansStep:
-    """what ``KmerTable.trim_fastq`` does with a piece: pg_table_read_spans, span length >= min_len, the records cut to their spans
-    (pg_fastq_gather_trimmed)"""
-
-    def __init__(self, table, window, lenient, mode, min_len):
-        self.table, self.window, self.lenient, self.mode, self.min_len = table, window, lenient, mode, min_len
-
-    def launch(self, s, n, status, events):
-        spans, _, sizes = self.table._spans_of(s.text, s.have, s.idx, n, s.done, self.window, self.lenient, self.mode, status, events)
-        return spans, sizes
-
-    def judge(self, rows, tot):
-        wide = rows[0].to(torch.int64) & 0xFFFFFFFF
-        ok = wide[:, 3] >= self.min_len
-        tot[2] += ok.sum()
-        tot[4] += wide[:, 0].sum()
-        tot[5] += wide[:, 1].sum()
-        return ok
-
-    def sizes(self, s, rows, kept, tot):
-        lens = rows[1][kept]
-        tot[6] += (lens < s.idx[4 * kept + 4] - s.idx[4 * kept]).sum()
-        tot[7] += (rows[0][kept, 3].to(torch.int64) & 0xFFFFFFFF).sum()
-        return lens
-
-    def gather(self, s, n, rows, kept, dst, n_kept, out):
-        return _lib.load().pg_fastq_gather_trimmed(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), rows[0].data_ptr(), dst.data_ptr(),
-                                                   n_kept, out.data_ptr(), out.numel(), _stream_ptr(self.table.device))
-
-
-class _CorrectStep:
-    """what ``KmerTable.correct_fastq`` does with a piece: pg_table_correct_reads on the piece IN PLACE (the piece is the device's
-    copy; what the host keeps for the next round is untouched), every record passes, and the records leave whole
-    (pg_fastq_gather)"""
-
-    def __init__(self, table, window, lenient):
-        self.table, self.window, self.lenient = table, window, lenient
-
-    def launch(self, s, n, status, events):
-        return self.table._corrections_of(s.text, s.have, s.idx, n, s.done, self.window, self.lenient, s.text, status, events)[0]
-
-    def judge(self, rows, tot):
-        wide = rows.to(torch.int64) & 0xFFFFFFFF
-        tot[2] += wide.shape[0]
-        tot[4] += wide[:, 0].sum()
-        tot[5] += wide[:, 1].sum()
-        tot[8] += wide[:, 2].sum()
-        tot[9] += wide[:, 3].sum()
-        tot[10] += (wide[:, 3] > 0).sum()
-        return torch.ones(wide.shape[0], dtype=torch.bool, device=rows.device)
-
-    def sizes(self, s, rows, kept, tot):
-        return s.idx[4 * kept + 4] - s.idx[4 * kept]
-
-    def gather(self, s, n, rows, kept, dst, n_kept, out):
-        return _lib.load().pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept, out.data_ptr(),
-                                           out.numel(), _stream_ptr(self.table.device))
-
-
-class _DepthsStep:
-    """what ``KmerTable.normalize_fastq`` does with a piece: pg_table_read_depths (n, present, d and the unit's draw w per record),
-    n >= 1 and d >= min_depth and w * d < target * 2^24 in exact 64-bit integers, the records byte for byte (pg_fastq_gather)"""
-
-    def __init__(self, table, args, lenient, target, min_depth, seed, unit_log2):
-        self.table, self.args, self.lenient, self.target, self.min_depth = table, args, lenient, target, min_depth
-        self.seed, self.unit_log2 = seed, unit_log2
-
-    def launch(self, s, n, status, events):
-        return self.table._depths_of(s.text, s.have, s.idx, n, s.done, self.args, self.lenient, self.seed, self.unit_log2, status, events)[0]
-
-    def judge(self, rows, tot):
-        wide = rows.to(torch.int64) & 0xFFFFFFFF
-        nk, d, w = wide[:, 0], wide[:, 2], wide[:, 3]
-        low = (nk < 1) | (d < self.min_depth)
-        ok = ~low & (w * d < self.target << 24)              # (w < 2^24, d < 2^32, target < 2^31: both sides below 2^56)
-        tot[2] += ok.sum()
-        tot[4] += nk.sum()
-        tot[5] += wide[:, 1].sum()
-        tot[11] += low.sum()
-        tot[12] += d.sum()
-        return ok
-
-    def sizes(self, s, rows, kept, tot):
-        tot[13] += (rows[kept, 2].to(torch.int64) & 0xFFFFFFFF).sum()
-        return s.idx[4 * kept + 4] - s.idx[4 * kept]
-
-    def gather(self, s, n, rows, kept, dst, n_kept, out):
-        return _lib.load().pg_fastq_gather(s.text.data_ptr(), s.have, s.idx.data_ptr(), n, kept.data_ptr(), dst.data_ptr(), n_kept, out.data_ptr(),
-                                           out.numel(), _stream_ptr(self.table.device))
-
-
-def _temp_beside(path: str) -> tuple:
-    """(file open for writing, its name): a new file of a name nobody else has, in the directory of ``path`` (so that it can be
-    moved into place), with the mode a plain ``open`` would have given it"""
-    import tempfile
-    fd, tmp = tempfile.mkstemp(dir=os.path.dirname(os.path.abspath(path)), prefix=os.path.basename(path) + ".", suffix=".tmp")
-    mask = os.umask(0)
-    os.umask(mask)
-    os.chmod(tmp, 0o666 & ~mask)
-    return os.fdopen(fd, "wb"), tmp
-
-
-def _filter_round(ins: list, mates: bool, pair: str) -> tuple:
-    """what one round of ``KmerTable.filter_fastq`` takes of its indexed pieces: (records per input, the error that ends the call
-    once those records are found well-formed or None, every input has ended).  The records are the whole ones every piece
-    holds -- an even number of them for interleaved mates while the file goes on.  Pending errors: an input that ends inside a
-    record, R1 / R2 of which one ends (at a record boundary) while the other holds more, an odd record count under any / both."""
-    n = min(s.n_rec for s in ins)
-    all_eof = all(s.eof for s in ins)
-    pending = None
-    if len(ins) == 2:
-        for s, o in ((ins[0], ins[1]), (ins[1], ins[0])):
-            if pending is None and s.eof and s.n_rec == n and not s.n_lines % 4 and (o.n_rec > n or (o.eof and o.n_lines > 4 * n)):
-                pending = f"{s.path} ends after {s.done + n} records, {o.path} holds more: R1 and R2 must have the same number of records (PG_EFORMAT)"
-    for s in ins:
-        if pending is None and s.eof and s.n_rec == n and s.n_lines % 4:
-            pending = f"{s.path}: record {s.done + n}: the file ends inside it ({s.n_lines % 4} of its 4 lines) (PG_EFORMAT)"
-    if len(ins) == 1 and mates and n & 1:
-        if all_eof:
-            pending = pending or (f"{ins[0].path}: record {ins[0].done + n - 1} has no mate: {ins[0].done + n} records are an odd number "
-                                  f"(pair={pair!r} takes records 2i and 2i + 1 as mates; PG_EFORMAT)")
-        else:
-            n -= 1
-    return n, pending, all_eof
-
-
-class _FastqPieces:
-    """one input of ``KmerTable.filter_fastq``: the file (plain or gzip, told by its first two bytes), the pinned buffer its pieces
-    are read into, the piece on the device and its line index.  The buffers are no larger than the input asks: a plain file's
-    size is known, a gzip file's buffer starts at ``START`` bytes and doubles up to the piece while the file goes on"""
-    START = 1 << 20
-
-    def __init__(self, path: str, piece: int):
-        self.path = path
-        self.f = None
-        with open(path, "rb") as probe:
-            packed = probe.read(2) == b"\x1f\x8b"
-        if packed:
-            import gzip
-            self.f = gzip.open(path, "rb")
-            self.limit, piece = piece, min(piece, self.START)
-        else:
-            self.f = open(path, "rb", buffering=0)
-            piece = max(64, min(piece, os.path.getsize(path) + 1))       # (a small file: one piece of its own size, and the end seen at once)
-            self.limit = piece
-        self.cap = piece
-        self.host = torch.empty(piece, dtype=torch.uint8, pin_memory=True)
-        self.buf = self.host.numpy()
-        self.text = None
-        self.have, self.eof, self.done = 0, False, 0     # bytes in the buffer, the file has ended, records of earlier pieces
-        self.hold = {}
-        self.idx, self.n_lines, self.n_rec = None, 0, 0
-
-    def fill(self) -> None:
-        while not self.eof:
-            if self.have == self.cap:
-                if self.cap >= self.limit:
-                    break
-                self._resize(min(2 * self.cap, self.limit))          # (a buffer that began small: up to the piece)
-            got = self.f.readinto(memoryview(self.buf)[self.have:self.cap])
-            if not got:
-                self.eof = True
-            else:
-                self.have += got
-
-    def _resize(self, cap: int) -> None:
-        host = torch.empty(cap, dtype=torch.uint8, pin_memory=True)
-        host[:self.have] = self.host[:self.have]
-        self.cap, self.host, self.buf = cap, host, host.numpy()
-
-    def grow(self) -> None:
-        """twice the piece: a record (a pair of them) that no piece holds"""
-        self.limit = 2 * self.cap
-        self._resize(self.limit)
-
-    def index(self, table: "KmerTable") -> None:
-        """the piece to the device, its lines counted and indexed; n_rec = the records that are whole (before the end of the file
-        a line without its newline is not yet a line)"""
-        if self.have == 0:
-            self.n_lines = self.n_rec = 0
-            return
-        if self.text is None or self.text.numel() < self.cap + 16:
-            self.text = None
-            self.text = torch.empty(self.cap + 16, dtype=torch.uint8, device=table.device)
-        self.text[:self.have].copy_(self.host[:self.have], non_blocking=True)
-        self.idx, self.n_lines = table._line_index(self.text, self.have, self.hold)
-        whole = self.n_lines if self.eof else self.n_lines - int(self.buf[self.have - 1] != 10)
-        self.n_rec = whole // 4
-
-    def consume(self, used: int, n_records: int) -> None:
-        """the first ``used`` bytes (``n_records`` records) are dealt with: what lies behind them moves to the front"""
-        rest = self.have - used
-        if rest:
-            self.buf[:rest] = self.buf[used:self.have].copy()
-        self.have, self.done = rest, self.done + n_records
-
-    def close(self) -> None:
-        if self.f is not None:
-            self.f.close()
-            self.f = None
 
 
 def encode_kmers(strings, k: int) -> np.ndarray:

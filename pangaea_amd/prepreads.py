@@ -32,8 +32,8 @@ import time
 
 import torch
 
-from . import _lib
-from .kmer import KmerTable, _FastqPieces, _fastq_error, _stream_ptr, _temp_beside
+from . import _lib, fastqtext
+from .fastqtext import fastq_error, stream_ptr as _stream_ptr
 
 SHORT_TYPES = ("stlfr", "tellseq")
 
@@ -57,7 +57,7 @@ def status_error(paths: list, status: torch.Tensor):
            _lib.FASTQ_FEW_FIELDS: "its stLFR barcode holds fewer than two '_'",
            _lib.FASTQ_LONG_TAG: f"its barcode is longer than {_lib.FASTQ_MAX_TAG - 2} bytes"}.get(reason)
     if why is None:
-        return _fastq_error(paths[f], words[f])
+        return fastq_error(paths[f], words[f])
     return f"{paths[f]}: record {record}: {why} (PG_EFORMAT)"
 
 
@@ -140,39 +140,6 @@ def interleaved_text(plan: Plan, before_alloc=None) -> tuple:
     return out, n_bytes, int(both.numel())
 
 
-class _Indexer:
-    """what ``_FastqPieces.index`` asks of its table: the device and the line index"""
-    _line_index = KmerTable._line_index
-
-    def __init__(self, device):
-        self.device = device
-
-
-def _round(ins: list) -> tuple:
-    """what one round takes of its indexed pieces: (records per input -- the whole ones every input holds --, the error that ends
-    the call once those records are found well-formed or None, every input has ended).  Pending errors: an input that ends inside
-    a record; one that ends at a record boundary while another holds more"""
-    n = min(s.n_rec for s in ins)
-    all_eof = all(s.eof for s in ins)
-    pending = None
-    for s in ins:
-        if pending is None and s.eof and s.n_rec == n and s.n_lines % 4:
-            pending = f"{s.path}: record {s.done + n}: the file ends inside it ({s.n_lines % 4} of its 4 lines) (PG_EFORMAT)"
-    for s in ins:
-        for o in ins:
-            if pending is None and o is not s and s.eof and s.n_rec == n and (o.n_rec > n or (o.eof and o.n_lines > 4 * n)):
-                pending = (f"{s.path} ends after {s.done + n} records, {o.path} holds more: "
-                           "the read files must have the same number of records (PG_EFORMAT)")
-    return n, pending, all_eof
-
-
-def _device_of(device):
-    if not torch.cuda.is_available():
-        raise RuntimeError("preprocessing reads needs a GPU: the kernels have no CPU path")
-    dev = torch.device("cuda") if device is None else torch.device(device)
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-
-
 def check_files(short_type, reads1, reads2, index, outs: list) -> list:
     """the input paths of a call, refused before anything is opened where they make no sense (ValueError)"""
     if short_type not in SHORT_TYPES:
@@ -184,13 +151,61 @@ def check_files(short_type, reads1, reads2, index, outs: list) -> list:
     if short_type != "tellseq" and index:
         raise ValueError(f"index reads (-I) go with tellseq only, not with {short_type}")
     srcs = [os.fspath(reads1), os.fspath(reads2)] + ([os.fspath(index)] if index else [])
-    for o in outs:
-        if o.endswith(".gz"):
-            raise ValueError(f"{o}: the reads are written as plain text, gzip output is not supported")
-    real_outs = [os.path.realpath(o) for o in outs]
-    if len(set(real_outs)) != len(outs) or set(real_outs) & {os.path.realpath(x) for x in srcs}:
-        raise ValueError("the outputs must differ from each other and from the inputs (got " + ", ".join(outs + srcs) + ")")
+    fastqtext.check_outputs(outs, srcs, "the reads")
     return srcs
+
+
+class _PrepRounds:
+    """what ``preprocess_reads`` does with a round of the piece loop (``fastqtext.stream_pieces``): the plan of the round's units and
+    its status rows (``check``); the new records' lengths, their scan, the write kernel and the bytes to the files (``emit``); the
+    counts and the device milliseconds per stage (``result``)"""
+
+    def __init__(self, mode: int, srcs: list, device):
+        self.mode, self.srcs, self.device = mode, srcs, device
+        self.pairs = self.flagged = self.bytes = 0
+        self.timed = {"index": [], "plan": [], "write": []}
+        self.plan = self.used = None
+
+    def _span(self, stage):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self.timed[stage].append((a, b))
+        a.record()
+        return b
+
+    def check(self, ins, n):
+        self.used = [int(v) for v in torch.stack([s.idx[4 * n] for s in ins]).tolist()]
+        end = self._span("plan")
+        self.plan = Plan(self.mode, [s.text for s in ins], self.used, [s.idx for s in ins], n, self.pairs)
+        end.record()
+        error = status_error(self.srcs, self.plan.status)
+        if error:
+            raise ValueError(error)
+
+    def emit(self, ins, n, files, writer) -> list:
+        plan, dev, tellseq = self.plan, self.device, self.mode == _lib.PREP_TELLSEQ
+        end = self._span("write")
+        kept = plan.kept()
+        len1, len2 = plan.record_bytes(kept)
+        n1, n2 = (int(v) for v in torch.stack([len1.sum(), len2.sum()]).tolist())
+        n_kept = int(len1.numel())
+        out1 = torch.empty(n1 + 32, dtype=torch.uint8, device=dev)
+        out2 = torch.empty(n2 + 32, dtype=torch.uint8, device=dev)
+        wl = torch.empty(19 * n_kept, dtype=torch.uint8, device=dev) if tellseq and n_kept else None
+        plan.write(kept, torch.cumsum(len1, 0) - len1, torch.cumsum(len2, 0) - len2, out1, n1, out2, n2, wl)
+        end.record()
+        for f, buf, m in zip(files, (out1, out2, wl), (n1, n2, 19 * n_kept)):
+            if buf is None or not m:
+                continue
+            writer.write(f, buf, m)
+            self.bytes += m
+        self.pairs += n
+        self.flagged += int(plan.tagged.sum().item())
+        self.plan = None
+        return self.used
+
+    def result(self) -> dict:
+        torch.cuda.current_stream(self.device).synchronize()
+        return {k: round(sum(a.elapsed_time(b) for a, b in v), 4) for k, v in self.timed.items()}
 
 
 def preprocess_reads(short_type: str, reads1: str, reads2: str, out_prefix: str, index: str | None = None, device=None) -> dict:
@@ -208,94 +223,11 @@ def preprocess_reads(short_type: str, reads1: str, reads2: str, out_prefix: str,
     prefix = os.fspath(out_prefix)
     outs = [prefix + "_1.fq", prefix + "_2.fq"] + ([prefix + ".wl"] if mode == _lib.PREP_TELLSEQ else [])
     srcs = check_files(short_type, reads1, reads2, index, outs)
-    dev = _device_of(device)
-    piece = KmerTable._filter_piece_bytes()
-    indexer = _Indexer(dev)
-    pairs = flagged = total_bytes = 0
-    timed = {"index": [], "plan": [], "write": []}
-
-    def span(stage):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        timed[stage].append((a, b))
-        a.record()
-        return b
-
-    ins, files, tmps = [], [], []
-    try:
-        with torch.cuda.device(dev):
-            for path in srcs:
-                ins.append(_FastqPieces(path, piece))
-            for o in outs:
-                f, tmp = _temp_beside(o)
-                files.append(f)
-                tmps.append(tmp)
-            host = None
-            done = False
-            while not done:
-                for s in ins:
-                    s.fill()
-                end = span("index")
-                for s in ins:
-                    s.index(indexer)
-                end.record()
-                n, pending, all_eof = _round(ins)
-                if n == 0 and pending is None and not all_eof:           # a buffer that is full and holds no record: a longer one
-                    for s in ins:
-                        if not s.eof and s.n_rec < 1:
-                            s.grow()
-                    continue
-                done = all_eof or pending is not None
-                if n:
-                    used = [int(v) for v in torch.stack([s.idx[4 * n] for s in ins]).tolist()]
-                    end = span("plan")
-                    plan = Plan(mode, [s.text for s in ins], used, [s.idx for s in ins], n, pairs)
-                    end.record()
-                    error = status_error(srcs, plan.status)              # (the malformed record in front comes before what is pending)
-                    if error:
-                        raise ValueError(error)
-                if pending is not None:
-                    raise ValueError(pending)
-                if n == 0:
-                    break
-                end = span("write")
-                kept = plan.kept()
-                len1, len2 = plan.record_bytes(kept)
-                n1, n2 = (int(v) for v in torch.stack([len1.sum(), len2.sum()]).tolist())
-                n_kept = int(len1.numel())
-                out1 = torch.empty(n1 + 32, dtype=torch.uint8, device=dev)
-                out2 = torch.empty(n2 + 32, dtype=torch.uint8, device=dev)
-                wl = torch.empty(19 * n_kept, dtype=torch.uint8, device=dev) if mode == _lib.PREP_TELLSEQ and n_kept else None
-                plan.write(kept, torch.cumsum(len1, 0) - len1, torch.cumsum(len2, 0) - len2, out1, n1, out2, n2, wl)
-                end.record()
-                for f, buf, m in zip(files, (out1, out2, wl), (n1, n2, 19 * n_kept)):
-                    if buf is None or not m:
-                        continue
-                    if host is None or host.numel() < m:
-                        host = torch.empty(m + m // 8, dtype=torch.uint8, pin_memory=True)
-                    host[:m].copy_(buf[:m], non_blocking=True)
-                    torch.cuda.current_stream(dev).synchronize()
-                    f.write(memoryview(host.numpy())[:m])
-                    total_bytes += m
-                pairs += n
-                flagged += int(plan.tagged.sum().item())
-                for s, m in zip(ins, used):
-                    s.consume(m, n)
-                del plan, out1, out2, wl
-            torch.cuda.current_stream(dev).synchronize()
-            device_ms = {k: round(sum(a.elapsed_time(b) for a, b in v), 4) for k, v in timed.items()}
-        for f in files:
-            f.close()
-        for tmp, o in zip(tmps, outs):
-            os.replace(tmp, o)
-    finally:
-        for s in ins:
-            s.close()
-        for f in files:
-            f.close()
-        for tmp in tmps:
-            if os.path.exists(tmp):
-                os.remove(tmp)
+    dev = fastqtext.device_of(device, "preprocessing reads")
+    rounds = _PrepRounds(mode, srcs, dev)
+    device_ms = fastqtext.stream_pieces(srcs, outs, dev, rounds, pair=None, grow_below=1, index_events=rounds.timed["index"])
+    pairs, flagged = rounds.pairs, rounds.flagged
     counts = ({"kept_pairs": flagged, "dropped_pairs": pairs - flagged} if mode == _lib.PREP_TELLSEQ
               else {"tagged_pairs": flagged, "untagged_pairs": pairs - flagged})
-    return {"short_type": short_type, "pairs": pairs, **counts, "bytes": total_bytes, "files": outs,
+    return {"short_type": short_type, "pairs": pairs, **counts, "bytes": rounds.bytes, "files": outs,
             "seconds": round(time.perf_counter() - t0, 6), "device_ms": device_ms}

@@ -25,24 +25,17 @@ import time
 
 import torch
 
-from . import _lib
-from .kmer import KmerTable, _fastq_error, _stream_ptr, _temp_beside
+from . import _lib, fastqtext
+from .fastqtext import fastq_error, piece_bytes, stream_ptr as _stream_ptr, temp_beside
 
 UNIT_BYTES = 64        # device bytes per unit beside the text: tag_off 8, tag_len 4, compare 1, order, keys and torch.sort's two outputs 8 each
 STAGES = ("index", "tags", "sort", "compare", "gather")
 
 
-class _OnDevice:
-    """what ``KmerTable._line_index`` asks of its table: the device"""
-
-    def __init__(self, device):
-        self.device = device
-
-
 def line_index(text: torch.Tensor, n_bytes: int) -> tuple:
-    """(line starts: int64 on the text's device, n_lines + 1 entries; n_lines) of text[:n_bytes] -- ``KmerTable._line_index``,
+    """(line starts: int64 on the text's device, n_lines + 1 entries; n_lines) of text[:n_bytes] -- ``fastqtext.line_index``,
     its buffers cut down to the entries that count"""
-    idx, n_lines = KmerTable._line_index(_OnDevice(text.device), text, n_bytes, {})
+    idx, n_lines = fastqtext.line_index(text, n_bytes)
     return idx[:n_lines + 1].clone(), n_lines
 
 
@@ -62,21 +55,13 @@ def _require_room(need: int, device, what: str, prepared: bool = False) -> None:
                          f"({how}); a multi-pass sort of larger files is not implemented")
 
 
-def _piece_bytes() -> int:
-    return KmerTable._filter_piece_bytes()
-
-
 def _read_text(path: str, device) -> tuple:
     """(the file's text on the device, its bytes): plain or gzip (told by the first two bytes), staged through one pinned buffer
     of PG_FILTER_PIECE_BYTES; a last line without its newline gets one"""
-    with open(path, "rb") as probe:
-        packed = probe.read(2) == b"\x1f\x8b"
-    piece = _piece_bytes()
-    if packed:
-        import gzip
-        f, size = gzip.open(path, "rb"), None
-    else:
-        f, size = open(path, "rb", buffering=0), os.path.getsize(path)
+    f, packed = fastqtext.open_fastq(path)
+    piece, size = piece_bytes(), None
+    if not packed:
+        size = os.path.getsize(path)
         piece = max(64, min(piece, size))
         _require_room(size + size // 2, device, path)          # (the text and its index while that is made)
     host = torch.empty(piece, dtype=torch.uint8, pin_memory=True)
@@ -184,7 +169,7 @@ def barcode_order(text: torch.Tensor, idx: torch.Tensor, n_units: int, lines_per
 def _status_error(what: str, status: int) -> str:
     if status & 0xFF == _lib.FASTQ_LONG_TAG:
         return f"{what}: record {status >> 8}: its barcode tag is longer than {_lib.FASTQ_MAX_TAG} bytes behind BX:Z: (PG_EFORMAT)"
-    return _fastq_error(what, status)
+    return fastq_error(what, status)
 
 
 def _raise_malformed(what: str, status: torch.Tensor) -> None:
@@ -308,7 +293,7 @@ class _Loaded:
             bad = marks.any(1).nonzero().flatten()[:1]
             if bad.numel():
                 r = int(bad.item())
-                raise ValueError(_fastq_error(self.paths[1], r << 8 | (_lib.FASTQ_NO_AT if bool(marks[r, 0]) else _lib.FASTQ_NO_PLUS)))
+                raise ValueError(fastq_error(self.paths[1], r << 8 | (_lib.FASTQ_NO_AT if bool(marks[r, 0]) else _lib.FASTQ_NO_PLUS)))
         if self.pairs:
             self.longest, self.untagged = max(0, int(self.tag_len.max().item()) - 5), int((self.tag_len == 0).sum().item())
         else:
@@ -346,13 +331,6 @@ def _gather_run(plan: list, out_dev: torch.Tensor, out_bytes: int) -> None:
                                        out_dev.data_ptr(), out_bytes, _stream_ptr(text.device)))
 
 
-def _device_of(device):
-    if not torch.cuda.is_available():
-        raise RuntimeError("sorting reads by barcode needs a GPU: the kernels have no CPU path")
-    dev = torch.device("cuda") if device is None else torch.device(device)
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-
-
 def _short_type_of(short_type, src1, src2, index, outs: list):
     """``short_type`` as ``_Loaded`` takes it: None for barcodes that stand in a BX:Z: tag already (None, "10x"), else stlfr /
     tellseq with their files checked (ValueError)"""
@@ -388,7 +366,7 @@ def sort_fastq(src1: str, out: str, src2: str | None = None, device=None, short_
     result then also holds ``short_type``, ``raw_pairs``, ``prepared_pairs``, ``dropped_pairs`` (TELL-seq: index reads that are not
     18 bytes), ``tagged_pairs`` and a ``prep`` entry in ``device_ms``.  None or "10x": nothing changes."""
     t0 = time.perf_counter()
-    dev = _device_of(device)
+    dev = fastqtext.device_of(device, "sorting reads by barcode")
     out = os.fspath(out)
     if out.endswith(".gz"):
         raise ValueError(f"{out}: the sorted reads are written as plain text, gzip output is not supported")
@@ -415,17 +393,14 @@ def sort_fastq(src1: str, out: str, src2: str | None = None, device=None, short_
                 _gather_run(_gather_plan(L.texts, L.sizes, L.idx, perm), out_dev, L.bytes)
         else:
             barcodes, out_dev = 0, None
-        f, tmp = _temp_beside(out)
+        f, tmp = temp_beside(out)
         try:
             if L.bytes:
-                piece = max(64, min(_piece_bytes(), L.bytes))
-                host = torch.empty(piece, dtype=torch.uint8, pin_memory=True)
-                view = memoryview(host.numpy())
+                piece = max(64, min(piece_bytes(), L.bytes))
+                writer = fastqtext.PinnedWriter(dev, piece)
                 for at in range(0, L.bytes, piece):
                     m = min(piece, L.bytes - at)
-                    host[:m].copy_(out_dev[at:at + m], non_blocking=True)
-                    torch.cuda.current_stream(dev).synchronize()
-                    f.write(view[:m])
+                    writer.write(f, out_dev[at:at + m], m)
             f.close()
             os.replace(tmp, out)
         finally:
@@ -447,7 +422,7 @@ def check_fastq(src1: str, src2: str | None = None, device=None, short_type: str
     written, to count them), ``untagged_pairs``.  The refusals are ``sort_fastq``'s.  ``short_type`` / ``index`` as there: the
     question is asked of the raw reads as they would be prepared (ordinals count the prepared units), and the preprocess
     counts are in the result."""
-    dev = _device_of(device)
+    dev = fastqtext.device_of(device, "sorting reads by barcode")
     short_type = _short_type_of(short_type, src1, src2, index, [])
     timer = _Timer()
     with torch.cuda.device(dev):

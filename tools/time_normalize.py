@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from pangaea_amd import _lib, kmer, synth  # noqa: E402
+from pangaea_amd import _lib, fastqtext, kmer, synth  # noqa: E402
 from pangaea_amd.kmer import _stream_ptr  # noqa: E402
 from time_filter import stats, timed  # noqa: E402
 
@@ -39,7 +39,7 @@ def med(v):
 def both_entries(table, text, n, a, L, sp) -> dict:
     """pg_table_read_hits and pg_table_read_depths on text[:n]: their times, the ratio, and what the rows say"""
     dev, k = text.device, table.k
-    idx, n_lines = table._line_index(text, n, {})
+    idx, n_lines = fastqtext.line_index(text, n)
     n_rec = n_lines // 4
     status = torch.zeros(2, dtype=torch.int64, device=dev)
     hits = torch.empty((n_rec, 2), dtype=torch.int32, device=dev)
@@ -83,7 +83,7 @@ def main() -> int:
     n_fq = min(a.fastq_pairs, a.pairs)
     res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "fastq_pairs": n_fq, "k": k, "kind": table.kind, "log2_slots": table.log2_slots,
            "log2_bucket": table.log2_bucket, "table_bytes": table.nbytes, "seed": a.seed, "warmup": a.warmup, "reps": a.reps,
-           "piece_bytes": kmer.KmerTable._filter_piece_bytes()}
+           "piece_bytes": fastqtext.piece_bytes()}
     with tempfile.TemporaryDirectory() as tmp:
         fq, out = os.path.join(tmp, "reads.fq"), os.path.join(tmp, "normalized.fq")
         synth.write_fastq_fast(s, cfg, fq, n_fq)

@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from pangaea_amd import _lib, prepreads, sortreads, synth  # noqa: E402
+from pangaea_amd import _lib, fastqtext, prepreads, sortreads, synth  # noqa: E402
 
 
 def timed(f, warmup: int, reps: int) -> list:
@@ -224,7 +224,7 @@ def main() -> int:
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "time_prep.json"))
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "seed": a.seed, "warmup": a.warmup, "reps": a.reps,
-           "piece_bytes": sortreads._piece_bytes()}
+           "piece_bytes": fastqtext.piece_bytes()}
     with tempfile.TemporaryDirectory() as tmp:
         paths = make_inputs(a.pairs, a.seed, tmp, torch.device("cuda:0"))
         for lib in ("stlfr", "tellseq"):

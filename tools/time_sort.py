@@ -32,7 +32,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from pangaea_amd import _lib, sortreads, synth  # noqa: E402
+from pangaea_amd import _lib, fastqtext, sortreads, synth  # noqa: E402
 
 
 def timed(f, warmup: int, reps: int) -> list:
@@ -87,7 +87,7 @@ def main() -> int:
     L = _lib.load()
     cfg = synth.SynthConfig(n_pairs=a.pairs, n_barcodes=max(1, a.pairs // 200), read_len=150, seed=a.seed)
     res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "seed": a.seed, "warmup": a.warmup, "reps": a.reps,
-           "piece_bytes": sortreads._piece_bytes()}
+           "piece_bytes": fastqtext.piece_bytes()}
     with tempfile.TemporaryDirectory() as tmp:
         made, fq, out = os.path.join(tmp, "made.fq"), os.path.join(tmp, "shuffled.fq"), os.path.join(tmp, "sorted.fq")
         s = synth.generate(cfg, device=dev, chunk_pairs=1 << 17, with_names=False)

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from pangaea_amd import _lib, kmer, synth  # noqa: E402
+from pangaea_amd import _lib, fastqtext, kmer, synth  # noqa: E402
 from pangaea_amd.kmer import _stream_ptr  # noqa: E402
 from time_filter import stats, timed  # noqa: E402
 
@@ -54,7 +54,7 @@ def main() -> int:
     n_fq = min(a.fastq_pairs, a.pairs)
     res = {"device": torch.cuda.get_device_name(0), "pairs": a.pairs, "fastq_pairs": n_fq, "k": k, "kind": table.kind, "log2_slots": table.log2_slots,
            "log2_bucket": table.log2_bucket, "table_bytes": table.nbytes, "lower": a.lower, "warmup": a.warmup, "reps": a.reps,
-           "piece_bytes": kmer.KmerTable._filter_piece_bytes()}
+           "piece_bytes": fastqtext.piece_bytes()}
     med = lambda v: sorted(v)[len(v) // 2]      # noqa: E731
     with tempfile.TemporaryDirectory() as tmp:
         fq, out = os.path.join(tmp, "reads.fq"), os.path.join(tmp, "trimmed.fq")
@@ -67,7 +67,7 @@ def main() -> int:
         del data
         res["text_bytes"] = n
         sp = _stream_ptr(dev)
-        idx, n_lines = table._line_index(text, n, {})
+        idx, n_lines = fastqtext.line_index(text, n)
         n_rec = n_lines // 4
         assert n_lines == 8 * n_fq
         status = torch.zeros(2, dtype=torch.int64, device=dev)
