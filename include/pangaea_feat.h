@@ -265,7 +265,22 @@ int pg_kmer_count(const uint64_t *codes, const uint32_t *valid, int64_t word_beg
 
 /* HyperLogLog sketch of the distinct canonical k-mers of a word range, for sizing a table before counting:
  * registers = device uint32_t[PG_HLL_REGISTERS], zeroed by the caller (several ranges / GPUs combine by element-wise
- * max).  Estimate = alpha * m^2 / sum_j 2^-registers[j] with the usual small-range correction (pangaea_amd/kmer.py). */
+ * max).  The registers themselves are part of the contract -- the ranks of a multi-GPU job all-reduce them with MAX:
+ *   for every position of the words [word_begin, word_end) that ENDS a run of at least k characters valid under `valid`
+ *   (1 <= k <= 31), with code = the canonical code of the k-mer ending there (A0 C1 T2 G3, the newest base in the low bits;
+ *   complement = c ^ 2; canonical = the smaller of the forward and the reverse-complement code):
+ *     h    = mix64(code ^ 0x9E3779B97F4A7C15), mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33;
+ *            x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33  (64-bit)
+ *     idx  = h >> 52                                     (the top 12 bits)
+ *     rank = clz64((h << 12) | (1 << 11)) + 1            (the sentinel bit below the 52 remaining hash bits: 1 <= rank <= 53)
+ *     registers[idx] = max(registers[idx], rank)
+ *   A k-mer belongs to the word its LAST character lies in: one that ends in word `word_begin` and starts in the word before is
+ *   taken (word_begin - 1 is read), one that starts in the range and ends beyond it is not.  The call accumulates by max into
+ *   whatever the registers hold, so the registers of a range are the max of those of its parts, and they depend on nothing
+ *   but the SET of canonical codes.  An empty range (word_end == word_begin) launches nothing.
+ * Estimate (pangaea_amd/kmer.py: sketch_estimate), m = PG_HLL_REGISTERS: E = alpha m^2 / sum_j 2^-registers[j] with
+ * alpha = 0.7213 / (1 + 1.079 / m); where E <= 2.5 m and V > 0 registers are zero, m ln(m / V) instead (linear counting);
+ * truncated to an integer.  tests/_sketch_ref.py restates all of this, tests/test_sketch_gpu.py holds the kernel to it. */
 #define PG_HLL_REGISTERS 4096
 int pg_kmer_distinct_sketch(const uint64_t *codes, const uint32_t *valid, int64_t word_begin, int64_t word_end, int k,
                             uint32_t *registers, void *stream);
