@@ -11,8 +11,10 @@ clustering.py:14-19).  The algorithm is the vendored library's (third_parties/rp
 Where it runs: everything on the device -- projections, bucketing (``torch.unique`` over the 5-integer rows), weighted
 merges, the weighted skeleton k-means (greedy k-means++ seeding with sklearn's 2 + ln k local trials, then weighted
 Lloyd) and the Lloyd distance / assignment / update steps over all points (the [N,32]x[k,32] distance step is a GEMM +
-row argmin).  Nothing but the final labels returns to the host.  Random draws come from numpy's global generator in the
-reference's order (``init_all`` seeds it; the device generator of the k-means++ seeding is seeded from it), but bucket numbering follows
+row argmin on rows and centres with the column mean taken off, as sklearn's fit does: in float32 the GEMM form of the distance
+cancels on rows that sit away from the origin, see ``_sq_dists``).  Nothing but the final labels returns to the host (and the
+2 x 1 000 rows behind the bucket width, so that w is numpy's float64 value on every device).  Random draws come from numpy's
+global generator in the reference's order (``init_all`` seeds it; the device generator of the k-means++ seeding is seeded from it), but bucket numbering follows
 ``torch.unique`` instead of ``unordered_map`` iteration, so labels are NOT bit-comparable with the reference
  -- parity is by inertia and adjusted Rand index.
 
@@ -34,11 +36,30 @@ from .utils import run_cmd
 
 
 def _sq_dists(x: torch.Tensor, c: torch.Tensor, x2: torch.Tensor | None = None) -> torch.Tensor:
-    """squared euclidean distances [N, K] in the dtype of x (the distance step)"""
+    """squared euclidean distances [N, K] in the dtype of x (the distance step): |x|^2 - 2 x.c + |c|^2, a GEMM.  In float32 the
+    three terms are each as large as |x|^2 and |c|^2, so the result is off by ~ (dim + 3) 2^-24 (|x| + |c|)^2 whatever the
+    distance is: callers pass rows and centres with the column mean of the rows taken off (``_centred``), as scikit-learn does,
+    so that this size is the spread of the data and not its distance from the origin"""
     if x2 is None:
         x2 = (x * x).sum(1, keepdim=True)
     d = x2 - 2.0 * (x @ c.t()) + (c * c).sum(1)[None, :]
     return d.clamp_(min=0)
+
+
+def _centred(x: torch.Tensor, mean: torch.Tensor | None = None):
+    """(x - m, m): the rows with their column mean (or the ``mean`` given, float64) taken off, m rounded to the dtype of x.  Any
+    vector near the mean serves as long as the SAME one is added back: the rounding of m costs nothing"""
+    if mean is None:
+        mean = x.mean(0, dtype=torch.float64) if x.shape[0] else torch.zeros(x.shape[1], dtype=torch.float64, device=x.device)
+    m = mean.to(x.dtype)
+    return x - m, m
+
+
+def _uncentred(c: torch.Tensor, m: torch.Tensor):
+    """(centres in the caller's coordinates, the same centres with m taken off again): the second is what the LAST distance
+    step uses, so that labels and inertia belong to the centres that are handed back and not to centres 2^-24 |m| beside them"""
+    out = (c.double() + m.double()).to(c.dtype)
+    return out, (out.double() - m.double()).to(c.dtype)
 
 
 def _all_reduce(t: torch.Tensor, group, op=None) -> torch.Tensor:
@@ -57,19 +78,21 @@ def _all_reduce(t: torch.Tensor, group, op=None) -> torch.Tensor:
 @torch.no_grad()
 def lloyd(x: torch.Tensor, centers: torch.Tensor, max_iter: int = 300, tol: float = 1e-4, sample_weight: torch.Tensor | None = None,
           group=None, sharded: bool = False):
-    """sklearn ``KMeans(init=centers, n_init=1)`` semantics (algorithm "lloyd"): stop when the labels repeat or the
-    squared centre shift falls below tol * mean feature variance; an empty cluster takes the point farthest from its
-    centre.  Returns (labels int64 [N], centers [K,D], inertia float, n_iter).
+    """sklearn ``KMeans(init=centers, n_init=1)`` semantics (algorithm "lloyd"): the column mean of x is taken off the rows and
+    the centres before the first step and added back to the centres at the end (the float32 distance step cancels otherwise:
+    ``_sq_dists``); stop when the labels repeat or the squared centre shift falls below tol * mean feature variance; an empty
+    cluster takes the point farthest from its centre (the points in descending order of that distance, stable).  The inertia is
+    summed over the rows in float64.  Returns (labels int64 [N], centers [K,D] in the coordinates of x, inertia float, n_iter).
 
     ``sharded`` (rph_kmeans_.py:152-160 runs this on one matrix): ``x`` holds THIS rank's rows only.  Distances and
     assignments are local; per iteration one all-reduce sums the [K, D] coordinate sums and the [K] counts of all ranks
     (K x (D + 1) values: 5 KB for K = 40, D = 32), a second, one-word one agrees on "no label changed anywhere"; the feature
-    variance behind the tolerance, the candidates for an empty cluster and the final inertia are reduced the same way.
+    variance behind the tolerance, the candidates for an empty cluster and the final inertia are reduced the same way; the mean
+    that is taken off is the all-reduced one, the same vector on every rank.
     Every rank ends with the same centres, inertia and iteration count, and with the labels of its own rows."""
     n, dim = x.shape
     k = centers.shape[0]
     w = torch.ones(n, dtype=x.dtype, device=x.device) if sample_weight is None else sample_weight.to(x)
-    x2 = (x * x).sum(1, keepdim=True)
     if sharded:
         import torch.distributed as dist
         mom = torch.cat([x.double().sum(0), (x.double() ** 2).sum(0), torch.tensor([float(n)], dtype=torch.float64, device=x.device)])
@@ -77,9 +100,15 @@ def lloyd(x: torch.Tensor, centers: torch.Tensor, max_iter: int = 300, tol: floa
         n_all = float(mom[-1].item())
         mean = mom[:dim] / n_all
         tol_abs = float((mom[dim:2 * dim] / n_all - mean * mean).clamp(min=0).mean().item()) * tol
+        x, m = _centred(x, mean)
     else:
-        tol_abs = float(x.var(dim=0, unbiased=False).mean().item()) * tol
-    centers = centers.to(x).clone()
+        x, m = _centred(x)
+        tol_abs = float(x.var(dim=0, unbiased=False).mean().item()) * tol if n else 0.0
+    x2 = (x * x).sum(1, keepdim=True)
+    centers = (centers.to(device=x.device, dtype=torch.float64) - m.double()).to(x.dtype)
+    light = (w == 0) if sample_weight is not None and not sharded else None
+    if light is not None and not bool(light.any()):
+        light = None
     labels_old = None
     n_iter = 0
     for n_iter in range(1, max_iter + 1):
@@ -93,7 +122,7 @@ def lloyd(x: torch.Tensor, centers: torch.Tensor, max_iter: int = 300, tol: floa
             sums, cnt = both[:, :dim].contiguous(), both[:, dim].contiguous()
         empty = torch.nonzero(cnt == 0).flatten()
         if empty.numel() and not sharded:                   # relocate empty clusters to the farthest points
-            far = torch.argsort(mind, descending=True)[:empty.numel()]
+            far = torch.argsort(mind, descending=True, stable=True)[:empty.numel()]
             for e, f in zip(empty.tolist(), far.tolist()):
                 old = int(labels[f])
                 sums[old] -= x[f] * w[f]; cnt[old] -= w[f]
@@ -108,7 +137,7 @@ def lloyd(x: torch.Tensor, centers: torch.Tensor, max_iter: int = 300, tol: floa
             offer = torch.full((n_e, 5 + dim), -1.0, dtype=torch.float64, device=x.device)
             take = min(n_e, n)
             if take:
-                far = torch.argsort(mind, descending=True)[:take]
+                far = torch.argsort(mind, descending=True, stable=True)[:take]
                 offer[:take, 0] = mind[far].double(); offer[:take, 1] = w[far].double(); offer[:take, 2] = labels[far].double()
                 offer[:take, 3] = float(me); offer[:take, 4] = far.double(); offer[:take, 5:] = x[far].double()
             offers = torch.zeros((world, n_e, 5 + dim), dtype=torch.float64, device=x.device)
@@ -126,6 +155,10 @@ def lloyd(x: torch.Tensor, centers: torch.Tensor, max_iter: int = 300, tol: floa
                 if int(row[3]) == me:
                     labels[int(row[4])] = e
         new_centers = sums / cnt.clamp(min=1e-30)[:, None]
+        if light is not None and labels_old is not None and bool(((labels == labels_old) | light).all()):
+            # only rows of weight 0 changed their cluster: the sums are those of the step before, and the centres are taken from
+            # it -- atomics that add in another order would make a shift of exactly 0 into one of a few ulps, and one more step
+            new_centers = centers
         shift = float(((new_centers - centers) ** 2).sum().item())
         centers = new_centers
         same = labels_old is not None and torch.equal(labels, labels_old)
@@ -137,12 +170,13 @@ def lloyd(x: torch.Tensor, centers: torch.Tensor, max_iter: int = 300, tol: floa
         labels_old = labels
         if shift <= tol_abs:
             break
+    out, centers = _uncentred(centers, m)
     d = _sq_dists(x, centers, x2)
     mind, labels = (d.min(dim=1) if n else (x.new_zeros(0), torch.zeros(0, dtype=torch.int64, device=x.device)))
-    total = (mind * w).sum().double().reshape(1)
+    total = (mind.double() * w.double()).sum().reshape(1)
     if sharded:
         _all_reduce(total, group)
-    return labels, centers, float(total.item()), n_iter
+    return labels, out, float(total.item()), n_iter
 
 
 @torch.no_grad()
@@ -150,20 +184,21 @@ def kmeans_plusplus(x: torch.Tensor, w: torch.Tensor, k: int, gen: torch.Generat
     """greedy k-means++ seeding with sample weights, as sklearn's ``_kmeans_plusplus`` (the seeding inside the reference's
     ``KMeans(n_clusters=k).fit_predict(reduced_X, sample_weight)``, rph_kmeans_.py:121-124): the first centre is drawn in
     proportion to the weights, every further one is the best of 2 + ln k candidates drawn in proportion to weight x squared
-    distance to the nearest centre so far.  Returns centres [k, D]."""
+    distance to the nearest centre so far (distances between centred rows: ``_sq_dists``).  Returns centres [k, D], rows of x."""
     n_trials = 2 + int(math.log(k))
     centers = torch.empty((k, x.shape[1]), dtype=x.dtype, device=x.device)
     first = torch.multinomial(w / w.sum(), 1, generator=gen)
     centers[0] = x[first[0]]
-    x2 = (x * x).sum(1, keepdim=True)
-    closest = _sq_dists(x, centers[0:1], x2).squeeze(1)
+    xc, _ = _centred(x)
+    x2 = (xc * xc).sum(1, keepdim=True)
+    closest = _sq_dists(xc, xc[first], x2).squeeze(1)
     for c in range(1, k):
         p = closest * w
         total = p.sum()
         # (every point already a centre: fall back to the weights, as sklearn's searchsorted on a flat cumsum would)
         p = torch.where(total > 0, p / total.clamp(min=1e-300), w / w.sum())
         cand = torch.multinomial(p, n_trials, replacement=True, generator=gen)
-        d = torch.minimum(_sq_dists(x, x[cand], x2), closest[:, None])          # [G, n_trials]
+        d = torch.minimum(_sq_dists(xc, xc[cand], x2), closest[:, None])        # [G, n_trials]
         best = (d * w[:, None]).sum(0).argmin()
         closest = d[:, best]
         centers[c] = x[cand[best]]
@@ -173,8 +208,8 @@ def kmeans_plusplus(x: torch.Tensor, w: torch.Tensor, k: int, gen: torch.Generat
 @torch.no_grad()
 def weighted_kmeans(x: torch.Tensor, w: torch.Tensor, k: int, n_init: int = 1, max_iter: int = 300, tol: float = 1e-4,
                     gen: torch.Generator | None = None):
-    """weighted k-means on the device (the skeleton step): best of ``n_init`` k-means++ seedings + Lloyd runs.
-    Returns (centers [k,D], labels int64 [G], inertia)."""
+    """weighted k-means on the device (the skeleton step): best of ``n_init`` k-means++ seedings + Lloyd runs (both on centred
+    rows).  Returns (centers [k,D] in the coordinates of x, labels int64 [G], inertia)."""
     if gen is None:
         gen = torch.Generator(device=x.device)
         gen.manual_seed(int(np.random.randint(0, 2 ** 31 - 1)))
@@ -205,7 +240,7 @@ class RPHKMeans:
                 raise RuntimeError("RPHKMeans runs on the GPU; pass device='cpu' explicitly to run the same torch ops on the host")
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = torch.device(device)
-        self.inertia_ = self.cluster_centers_ = self.labels_ = self.n_iter_ = None
+        self.inertia_ = self.cluster_centers_ = self.labels_ = self.n_iter_ = self.mean_ = None
         self.reduced_X_ = self.reduced_X_weight_ = self.rp_labels_ = self.rp_iter_ = self.init_centers_ = None
 
     # -------------------------------------------------------------- point reduction
@@ -216,8 +251,9 @@ class RPHKMeans:
         n = x.shape[0]
         a = torch.from_numpy(np.random.choice(n, self.sample_dist_num)).to(x.device)
         b = torch.from_numpy(np.random.choice(n, self.sample_dist_num)).to(x.device)
-        dist = (x[a].double() - x[b].double()).pow(2).sum(1).sqrt()
-        self.w = float(np.median(dist.cpu().numpy()) * 0.5)
+        # the 2 x 1 000 sampled rows go to the host: numpy's float64 sum, the library's own, gives the same w on every device
+        diff = x[a].cpu().numpy().astype(np.float64) - x[b].cpu().numpy().astype(np.float64)
+        self.w = float(np.median(np.sqrt((diff ** 2).sum(1))) * 0.5)
         return self.w
 
     @torch.no_grad()
@@ -261,6 +297,7 @@ class RPHKMeans:
         if x.dtype not in (torch.float32, torch.float64):
             x = x.float()
         self.inertia_ = np.inf
+        self.mean_ = _centred(x)[1].cpu().numpy()           # what lloyd takes off the rows: predict takes off the same
         for _ in range(self.n_init):
             centers0, red, weight, rp_labels, rp_iter, _, _ = self.init_centers(x)
             labels, centers, inertia, n_iter = lloyd(x, centers0.to(x))
@@ -275,9 +312,14 @@ class RPHKMeans:
         return self.fit(X).labels_
 
     def predict(self, X):
+        """the nearest of ``cluster_centers_``, by the distance step of the fit's last iteration: rows and centres minus the
+        column mean of the fitted rows, so that ``predict(X) == labels_`` for the X that was fitted"""
         x = torch.as_tensor(X).to(self.device)
-        c = torch.from_numpy(self.cluster_centers_).to(x)
-        return _sq_dists(x, c).argmin(1).cpu().numpy().astype(np.int32)
+        if x.dtype not in (torch.float32, torch.float64):
+            x = x.float()
+        xc, m = _centred(x, None if self.mean_ is None else torch.from_numpy(self.mean_).to(self.device).double())
+        c = (torch.from_numpy(self.cluster_centers_).to(self.device).double() - m.double()).to(x.dtype)
+        return _sq_dists(xc, c).argmin(1).cpu().numpy().astype(np.int32)
 
 
 def clustering_rph_kmeans(embedding, k):

@@ -405,6 +405,13 @@ def _lloyd_worker(rank, world, port):
         want_lab, want_cen, want_inertia, want_iter = lloyd(torch.from_numpy(x), c0)
         assert torch.equal(lab, want_lab[cut[rank]:cut[rank + 1]]) and n_iter == want_iter
         assert torch.allclose(cen, want_cen, rtol=1e-4, atol=1e-4) and abs(inertia - want_inertia) <= 1e-4 * want_inertia
+        # ... and the same rows 30 away from the origin on every coordinate: every rank takes off the SAME all-reduced mean
+        x30 = (x.astype(np.float64) + 30).astype(np.float32)
+        c30 = (c0.double() + 30).float()
+        lab, cen, inertia, n_iter = lloyd(torch.from_numpy(x30[cut[rank]:cut[rank + 1]]), c30, sharded=True)
+        want_lab, want_cen, want_inertia, want_iter = lloyd(torch.from_numpy(x30), c30)
+        assert torch.equal(lab, want_lab[cut[rank]:cut[rank + 1]]) and n_iter == want_iter
+        assert torch.allclose(cen, want_cen, rtol=1e-4, atol=1e-4) and abs(inertia - want_inertia) <= 1e-4 * want_inertia
         # (b) the whole RPH-KMeans call: rank 0 reduces and seeds, every rank iterates on its rows: the one-process partition
         np.random.seed(11)
         labels = clustering_rph_kmeans_sharded(mine, x if rank == 0 else None, 6, n_init=3, device="cpu")
